@@ -12,8 +12,11 @@ Optimiser, densification and data loading are excluded (they are outside the pat
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W              # ... or under an external torchrun (RANK / WORLD_SIZE from the environment)
     python bench.py --config 3 | 4                           # BASELINE configs[3] / [4] (at --gpus 1: the per-rank workload)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full    # + repeats, roofline, pair statistics, fine_stage, cpu_baseline, density events
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
+Without --full a run sets up, warms up, times --steps steps and prints the line (+ the dump): everything it measures beyond `value` /
+`ms_per_step` is behind --full.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
 import argparse
 import json
@@ -191,6 +194,46 @@ def cpu_baseline(scene, cam, frame=0, budget_s=15.0):
                       f"{cores} torch threads of {avail} hardware threads"}
 
 
+DUMP_MAX_ELEMS = 1 << 20          # --dump-outputs: larger arrays are written as a sample of this many elements (4 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_arrays(out, model, residual=None):
+    """What a caller of the timed step receives, by name: images, radii and loss from `out` (render()'s dict + "loss", or the part of it a
+    recorded step keeps; `viewspace_points` is the leaf that holds dL/dmean2D) and the gradients of the model's parameters and residual leaves."""
+    arrays = {k: out.get(k) for k in ("render", "depth", "weight", "normal", "radii", "loss")}
+    vs = out.get("viewspace_points")
+    arrays["grad_means2D"] = None if vs is None else vs.grad
+    for name, p in model.named_parameters():
+        arrays["grad_" + name.lstrip("_")] = p.grad
+    for name, t in zip(("residual_dx", "residual_dq"), residual or ()):
+        arrays["grad_" + name] = None if t is None else t.grad
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor, None skipped) as path/<name>.npy in float32, for comparing two builds output
+    for output.  An array of more than DUMP_MAX_ELEMS elements is written flattened, as its elements at DUMP_MAX_ELEMS sorted flat indices
+    drawn without replacement by a generator of fixed seed: the same indices in every run with the same arguments."""
+    import numpy as np
+    plan = []
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        plan.append((name, t))
+    total = 4 * sum(t.numel() for _, t in plan)
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(path, exist_ok=True)
+    for name, t in plan:
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+    print(f"[bench] --dump-outputs: {len(plan)} arrays, {total / 1e6:.1f} MB -> {path}", file=sys.stderr)
+
+
 CONFIGS = {
     0: dict(name="BASELINE configs[0]: 10k static Gaussians, 256x256, projection + SH forward (plumbing)", gaussians=10_000, height=256, width=256,
             focal=272.0, actors=0, forward_only=True),
@@ -261,10 +304,18 @@ def main():
     ap.add_argument("--gaussians", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
-    ap.add_argument("--repeats", type=int, default=5, help="extra back-to-back repeats of the timed block after it (min / median / max reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fine-stage", action="store_true", help="skip the `fine_stage` block (the S3G fine-stage step at the headline size, measured after the timed "
-                    "region and outside `value`; 1 GPU, headline configuration only; ~10 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repeats of the timed block, the per-stage roofline and pair statistics (eager "
+                         "repetitions of the timed steps), the exchange phases (N > 1), config 4's density-control events, the fine_stage block and the "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (images, radii, loss, gradients) as DIR/<name>.npy in float32; arrays of "
+                         "more than %d elements as a fixed, seeded sample of them" % DUMP_MAX_ELEMS)
+    ap.add_argument("--repeats", type=int, default=None, help="extra back-to-back repeats of the timed block after it (min / median / max reported; "
+                    "default 5 with --full, else 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fine-stage", action="store_true", help="with --full: skip the `fine_stage` block (the S3G fine-stage step at the headline size, measured "
+                    "after the timed region and outside `value`; 1 GPU, headline configuration only; ~10 s)")
     ap.add_argument("--sync-count", action="store_true", help="read the duplicate count back every forward (reference behaviour)")
     ap.add_argument("--no-normal", action="store_true", help="skip the normal image (unused by the training loss)")
     ap.add_argument("--factored-sh", action="store_true", help="use the multi-GPU SH-gradient factor exchange at any world size (1 GPU: measures its local cost)")
@@ -284,7 +335,13 @@ def main():
     ap.add_argument("--densify-grad-threshold", type=float, default=None,
                     help="config 4's density-control event: view-space gradient threshold (default: the value that selects ~5 %% of the seen Gaussians of the synthetic scene)")
     args = ap.parse_args()
-    rc = self_launch(args, sys.argv[1:])            # N > 1 without torchrun: the ranks run as a fresh child process; nothing here has touched the GPU
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 0
+    argv = sys.argv[1:]
+    if args.dump_outputs:                           # (the ranks of self_launch run from the repository root)
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv = argv + ["--dump-outputs", args.dump_outputs]
+    rc = self_launch(args, argv)                    # N > 1 without torchrun: the ranks run as a fresh child process; nothing here has touched the GPU
     if rc is not None:
         sys.exit(rc)
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -395,6 +452,7 @@ def main():
             xchg.actor_pose = None if out["actor_pose"] is None else out["actor_pose"].detach()   # (no reference into the autograd graph)
         loss = l1_loss(out["render"], target)
         loss.backward(unit)
+        out["loss"] = loss.detach()
         if xchg is not None:
             xchg.finish(model._features, model._xyz, model.active_sh_degree, other_params=params)
             rec.on_backward = None
@@ -471,6 +529,13 @@ def main():
     th = model.track_heads
     k_sched = (th.min_embeddings, th.max_embeddings, th.c2f_temporal_iter) if th is not None else None
 
+    def kept(o):
+        """the outputs of a step that --dump-outputs writes, without the autograd graph behind them"""
+        d = {k: None if o[k] is None else o[k].detach() for k in ("render", "depth", "weight", "normal", "radii", "loss")}
+        d["viewspace_points"] = o["viewspace_points"]
+        return d
+    last_out = {}
+
     def settle_replays(replay):
         """replay the step (untimed) until the clocks have settled: the GPU has idled through set-up, capture and host-side checks (measured: with
         --steps 20 --warmup 5 the first timed block was 2.4 % slower than its back-to-back repeats)"""
@@ -512,9 +577,12 @@ def main():
             rec_g.on_sh_factor = cut                     # (two-graph capture: called between the halves of the rasterizer's backward)
             o = render(model, cam_g, blk[0:3], frame=frame_dev, iteration=DeviceStep(k_fine=kf_dev, t=t_dev), options=opts, record=rec_g,
                        residual=residual)
-            l1_loss(o["render"], target).backward(unit)
+            loss = l1_loss(o["render"], target)
+            loss.backward(unit)
             if S["stats"] is not None:
                 dp.add_densification_stats(o["viewspace_points"].grad, o["radii"], *S["stats"])
+            o["loss"] = loss.detach()
+            gstate["out"] = kept(o)                      # (graph-static tensors: every replay rewrites them)
             # what the gradient exchange of a multi-GPU step reads after the replay: graph-static tensors
             gstate["rec"], gstate["campos"] = rec_g, blk[35:38]
             gstate["pose"] = None if o["actor_pose"] is None else o["actor_pose"].detach()
@@ -666,6 +734,8 @@ def main():
         else:
             o = one_step(row_of(step))
             status_log[row_of(step)].copy_(o["raster_call"].status)
+            if args.dump_outputs:
+                last_out["out"] = kept(o)
 
     def timed_block(first, count):
         torch.cuda.synchronize()
@@ -690,12 +760,12 @@ def main():
 
     for s in range(args.warmup):
         timed_step(s)
-    if G is None:
+    if G is None and args.full:
         torch.cuda.synchronize()
         _lib.profile_enable(True)
         _lib.profile_read()
-    # N > 1 (or the forced one-rank exchange): HIP events around the phases of every timed step's exchange, read after the timed region
-    X["timing"], X["timed"] = bool(G is not None and opts.factored_sh_grad and (world > 1 or dp.force_exchange())), []
+    # --full, N > 1 (or the forced one-rank exchange): HIP events around the phases of every timed step's exchange, read after the timed region
+    X["timing"], X["timed"] = bool(args.full and G is not None and opts.factored_sh_grad and (world > 1 or dp.force_exchange())), []
     dt, t_enqueue, dt_own = timed_block(args.warmup, args.steps)
     exchange_times = None
     if X["timed"]:
@@ -708,9 +778,11 @@ def main():
                                   "(behind K8) and of the factor gathers (issued between K7 and K8: they travel under K8); rebuild = the local dL/dshs rebuild")
     X["timing"], X["timed"] = False, []
     prof_timed = None
-    if G is None:
+    if G is None and args.full:
         prof_timed = _lib.profile_read()
         _lib.profile_enable(False)
+    if args.dump_outputs and rank == 0:          # the last timed step's outputs, before any other step overwrites them
+        dump_outputs(args.dump_outputs, step_arrays(G.gstate["out"] if G is not None else last_out["out"], model, residual))
     # ---- the same block again, `repeats` times back to back: spread of the measurement (`value` stays the first block)
     rep = []
     for r in range(max(args.repeats, 0)):
@@ -718,39 +790,37 @@ def main():
         rep.append(d_r / args.steps * 1e3)
     flush_status_log()
     st_all = status_log[args.warmup:args.warmup + args.steps].cpu().numpy().astype("int64") & 0xFFFFFFFF          # (D, flags, V, .) of every timed step
-    stage_region = "the timed region"
-    keep_stats = None if S["stats"] is None else [t.clone() for t in S["stats"]]       # (the diagnostic steps below are not training steps)
-    if G is not None:
-        # Per-stage HIP events are recorded by host code, which does not run when a graph is replayed: the stage durations of the
-        # roofline block come from the SAME steps issued eagerly right after the timed region (same kernels, same inputs).
-        n_prof = min(args.steps, 20)
-        _lib.profile_enable(True)
-        _lib.profile_read()
-        for s in range(n_prof):
-            one_step(args.warmup + s)
-        torch.cuda.synchronize()
-        stage_region = f"{n_prof} eager repetitions of the timed steps, run right after the timed region (graph replays execute no host-side event records)"
-        prof_steps = n_prof
-        prof = _lib.profile_read()
-        _lib.profile_enable(False)
-    else:
-        prof_steps, prof = args.steps, prof_timed
-    # ---- pair statistics of the render backward (diagnostic instantiation of K7, a few of the timed views): evaluated vs contributing
-    pairs = None
-    if world == 1:
-        ps = torch.zeros(4, dtype=torch.int64, device=dev)
-        n_ps = min(args.steps, 5)
-        for s in range(n_ps):
-            rec_p = RasterCall()
-            rec_p.pair_stats = ps
-            one_step(args.warmup + s * max(args.steps // n_ps, 1), record=rec_p)
-        ev, hit, rows_k7, atoms_k7 = [int(x) for x in ps.cpu().tolist()]
-        pairs = {"evaluated_per_launch": ev / n_ps, "contributing_per_launch": hit / n_ps, "useful_fraction": round(hit / max(ev, 1), 4),
-                 "launches": n_ps, "note": "(pixel, list entry) pairs the lanes of k_render_backward_q evaluate / pairs with alpha >= 1/255 in front "
-                                           "of the pixel's last contributor; counting instantiation of the kernel (EmdBwdArgs.pair_stats), outside the timed region"}
-    if keep_stats is not None:
-        for t_, k_ in zip(S["stats"], keep_stats):
-            t_.copy_(k_)
+    stage_region, prof_steps, prof, pairs = "the timed region", args.steps, prof_timed, None
+    if args.full:
+        keep_stats = None if S["stats"] is None else [t.clone() for t in S["stats"]]       # (the diagnostic steps below are not training steps)
+        if G is not None:
+            # Per-stage HIP events are recorded by host code, which does not run when a graph is replayed: the stage durations of the
+            # roofline block come from the SAME steps issued eagerly right after the timed region (same kernels, same inputs).
+            n_prof = min(args.steps, 20)
+            _lib.profile_enable(True)
+            _lib.profile_read()
+            for s in range(n_prof):
+                one_step(args.warmup + s)
+            torch.cuda.synchronize()
+            stage_region = f"{n_prof} eager repetitions of the timed steps, run right after the timed region (graph replays execute no host-side event records)"
+            prof_steps = n_prof
+            prof = _lib.profile_read()
+            _lib.profile_enable(False)
+        # ---- pair statistics of the render backward (diagnostic instantiation of K7, a few of the timed views): evaluated vs contributing
+        if world == 1:
+            ps = torch.zeros(4, dtype=torch.int64, device=dev)
+            n_ps = min(args.steps, 5)
+            for s in range(n_ps):
+                rec_p = RasterCall()
+                rec_p.pair_stats = ps
+                one_step(args.warmup + s * max(args.steps // n_ps, 1), record=rec_p)
+            ev, hit, rows_k7, atoms_k7 = [int(x) for x in ps.cpu().tolist()]
+            pairs = {"evaluated_per_launch": ev / n_ps, "contributing_per_launch": hit / n_ps, "useful_fraction": round(hit / max(ev, 1), 4),
+                     "launches": n_ps, "note": "(pixel, list entry) pairs the lanes of k_render_backward_q evaluate / pairs with alpha >= 1/255 in front "
+                                               "of the pixel's last contributor; counting instantiation of the kernel (EmdBwdArgs.pair_stats), outside the timed region"}
+        if keep_stats is not None:
+            for t_, k_ in zip(S["stats"], keep_stats):
+                t_.copy_(k_)
     step_issue_graph, two_graphs = G is not None, (G is not None and G.two_graphs)
 
     def release_graphs(G_):
@@ -767,7 +837,7 @@ def main():
     # is what a training loop pays every `densification_interval` = 100 iterations (S3Gaussian/arguments/gaussian_options.py:112-117) -- that one
     # is `event_ms` / `re_record_ms`.  Between them the timed views run again and accumulate the statistics the second event decides on.
     density_event = None
-    if cfg.get("densify"):
+    if cfg.get("densify") and args.full:
         from emd_amd.model import density_control
         events = []
         for ev_i in range(2):
@@ -861,55 +931,57 @@ def main():
         # V and D of EVERY timed step (device status words of rank 0's views), not of one frame
         Ds, Vs = st_all[:, 0], st_all[:, 2]
         D, V = float(Ds.mean()), float(Vs.mean())
-        # the roofline's algorithmic bytes use D and V of the SAME steps the stage durations were measured over (the eager repetitions of the
-        # first `prof_steps` timed steps behind a graph run; every timed step otherwise), so achieved / frac are self-consistent for any --steps
-        Dp, Vp = float(Ds[:prof_steps].mean()), float(Vs[:prof_steps].mean())
         T = ((W + 15) // 16) * ((H + 15) // 16)
         C = 7 if opts.compute_normal else 4
         passes = (max(T - 1, 1).bit_length() + 7) // 8            # radix passes over the D duplicates (tile bits)
-        ab = algorithmic_bytes(N, Vp, Dp, H * W, T, C, passes, residual=residual is not None, C_bwd=4)   # the L1 loss sends no gradient into the normal image
-        stages = {}
-        for name, (ms, cnt) in prof.items():
-            if cnt and name in ab:
-                avg = ms / prof_steps                                # per iteration (a stage may open twice per step)
-                stages[name] = {"ms": round(avg, 4), "alg_GB": round(ab[name] / 1e9, 4),
-                                "GBps": round(ab[name] / 1e9 / (avg * 1e-3), 1)}
-        dom = max(stages, key=lambda k: stages[k]["ms"])
-        kernel_ms = sum(v["ms"] for v in stages.values())
-        total_alg = sum(ab.values())
-        full = (N, H, W, args.config) == (2_000_000, 1066, 1600, 2)
-        traffic = pmc_traffic(dom, passes) if full else None
-        if full:                                             # fabric bytes per stage from the same committed counter file (static)
-            for name in stages:
-                tb = pmc_traffic(name, passes)
-                if tb:
-                    stages[name]["fabric_GB_static"] = round(tb / 1e9, 4)
-                    stages[name]["fabric_over_algorithmic"] = round(tb / ab[name], 2)
-        if pairs is not None:
-            pairs["atomic_rows_per_launch"] = rows_k7 / pairs["launches"]
-            pairs["float_atomics_per_launch"] = atoms_k7 / pairs["launches"]
-            pairs["atomic_row_bytes_per_launch"] = 48.0 * rows_k7 / pairs["launches"]
-            pairs["compulsory_row_bytes_per_launch"] = 48.0 * Vp
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": stages[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(stages[dom]["GBps"] / HBM_PEAK_GBS, 4),
-                    "traffic": traffic, "traffic_ratio": None if not traffic else round(traffic / ab[dom], 3),
-                    "traffic_static": {"static": True, "source": None if _pmc_path(PMC_TRAFFIC_CSV) is None else "profiles/" + os.path.basename(_pmc_path(PMC_TRAFFIC_CSV)),
-                                       "note": "rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE of `bench.py --steps 20 --warmup 5 --eager` (the driver's flags: the same frames "
-                                               "as the timed region of a default driver run), bytes per launch; a committed file constant, not measured in this run"},
-                    "secondary_bound": "fp32 vector issue rate: the render kernels are issue-bound (DESIGN.md section 6)",
-                    "issue": issue_bound(dom, stages[dom]["ms"]) if full else None,
-                    "pairs": pairs,
-                    "algorithmic_bytes_per_launch": ab[dom], "avg_launch_ms": stages[dom]["ms"],
-                    "stage_durations_measured_over": stage_region,
-                    "per_step": {"steps": int(len(Ds)), "D_min": int(Ds.min()), "D_mean": round(D, 1), "D_max": int(Ds.max()),
-                                 "V_min": int(Vs.min()), "V_mean": round(V, 1), "V_max": int(Vs.max()),
-                                 "D_mean_profiled_steps": round(Dp, 1), "V_mean_profiled_steps": round(Vp, 1),
-                                 "note": "list entries D (the (tile, Gaussian) pairs inside the Gaussians' alpha >= 1/255 boxes) and visible Gaussians V of every timed step, read from "
-                                         "the device status words after the timed region; the algorithmic bytes use the means over the steps the stage durations were measured on"},
-                    "whole_iter": {"algorithmic_GB": round(total_alg / 1e9, 3), "kernel_ms": round(kernel_ms, 3),
-                                   "GBps": round(total_alg / 1e9 / (kernel_ms * 1e-3), 1),
-                                   "frac": round(total_alg / 1e9 / (kernel_ms * 1e-3) / HBM_PEAK_GBS, 4)},
-                    "stages": stages}
+        headline = (N, H, W, args.config) == (2_000_000, 1066, 1600, 2)
+        roofline = None
+        if args.full:
+            # the roofline's algorithmic bytes use D and V of the SAME steps the stage durations were measured over (the eager repetitions of the
+            # first `prof_steps` timed steps behind a graph run; every timed step otherwise), so achieved / frac are self-consistent for any --steps
+            Dp, Vp = float(Ds[:prof_steps].mean()), float(Vs[:prof_steps].mean())
+            ab = algorithmic_bytes(N, Vp, Dp, H * W, T, C, passes, residual=residual is not None, C_bwd=4)   # the L1 loss sends no gradient into the normal image
+            stages = {}
+            for name, (ms, cnt) in prof.items():
+                if cnt and name in ab:
+                    avg = ms / prof_steps                                # per iteration (a stage may open twice per step)
+                    stages[name] = {"ms": round(avg, 4), "alg_GB": round(ab[name] / 1e9, 4),
+                                    "GBps": round(ab[name] / 1e9 / (avg * 1e-3), 1)}
+            dom = max(stages, key=lambda k: stages[k]["ms"])
+            kernel_ms = sum(v["ms"] for v in stages.values())
+            total_alg = sum(ab.values())
+            traffic = pmc_traffic(dom, passes) if headline else None
+            if headline:                                           # fabric bytes per stage from the same committed counter file (static)
+                for name in stages:
+                    tb = pmc_traffic(name, passes)
+                    if tb:
+                        stages[name]["fabric_GB_static"] = round(tb / 1e9, 4)
+                        stages[name]["fabric_over_algorithmic"] = round(tb / ab[name], 2)
+            if pairs is not None:
+                pairs["atomic_rows_per_launch"] = rows_k7 / pairs["launches"]
+                pairs["float_atomics_per_launch"] = atoms_k7 / pairs["launches"]
+                pairs["atomic_row_bytes_per_launch"] = 48.0 * rows_k7 / pairs["launches"]
+                pairs["compulsory_row_bytes_per_launch"] = 48.0 * Vp
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": stages[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(stages[dom]["GBps"] / HBM_PEAK_GBS, 4),
+                        "traffic": traffic, "traffic_ratio": None if not traffic else round(traffic / ab[dom], 3),
+                        "traffic_static": {"static": True, "source": None if _pmc_path(PMC_TRAFFIC_CSV) is None else "profiles/" + os.path.basename(_pmc_path(PMC_TRAFFIC_CSV)),
+                                           "note": "rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE of `bench.py --steps 20 --warmup 5 --eager` (the flags of the headline run: the "
+                                                   "same frames as its timed region), bytes per launch; a committed file constant, not measured in this run"},
+                        "secondary_bound": "fp32 vector issue rate: the render kernels are issue-bound (DESIGN.md section 6)",
+                        "issue": issue_bound(dom, stages[dom]["ms"]) if headline else None,
+                        "pairs": pairs,
+                        "algorithmic_bytes_per_launch": ab[dom], "avg_launch_ms": stages[dom]["ms"],
+                        "stage_durations_measured_over": stage_region,
+                        "per_step": {"steps": int(len(Ds)), "D_min": int(Ds.min()), "D_mean": round(D, 1), "D_max": int(Ds.max()),
+                                     "V_min": int(Vs.min()), "V_mean": round(V, 1), "V_max": int(Vs.max()),
+                                     "D_mean_profiled_steps": round(Dp, 1), "V_mean_profiled_steps": round(Vp, 1),
+                                     "note": "list entries D (the (tile, Gaussian) pairs inside the Gaussians' alpha >= 1/255 boxes) and visible Gaussians V of every timed step, read from "
+                                             "the device status words after the timed region; the algorithmic bytes use the means over the steps the stage durations were measured on"},
+                        "whole_iter": {"algorithmic_GB": round(total_alg / 1e9, 3), "kernel_ms": round(kernel_ms, 3),
+                                       "GBps": round(total_alg / 1e9 / (kernel_ms * 1e-3), 1),
+                                       "frac": round(total_alg / 1e9 / (kernel_ms * 1e-3) / HBM_PEAK_GBS, 4)},
+                        "stages": stages}
         if world == 1:
             mapping = ("1 GPU: camera 0 of frame (step mod 50)" if num_actors else "1 GPU: camera 0 of frame 0 (static scene)") if num_cams == 1 else \
                       f"1 GPU walking the {num_cams}-camera rig: step s renders camera (s mod {num_cams}) of frame (s div {num_cams}) -- the per-rank workload of this configuration"
@@ -958,13 +1030,14 @@ def main():
                                              "pose tables, dense average rebuilt locally; one RCCL all-reduce (AVG) of the remaining 44 B per Gaussian "
                                              "(one slab, started inside backward()) + actor poses / track heads"),
                        "exchange_rows_per_view": int(X.get("mean_cap") or 0) if X.get("uses_rows") else None},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            res["roofline"] = roofline
         if exchange_times is not None:
             res["exchange"] = exchange_times
         if density_event is not None:
             res["density_control_event"] = density_event
-        if world == 1 and full and not args.no_fine_stage:
+        if world == 1 and headline and args.full and not args.no_fine_stage:
             # the step S3Gaussian runs for 50 000 of its 55 000 iterations (deformation network in front of the rasterizer, full loss, sky): measured
             # AFTER the timed region and reported beside it -- `value` stays BASELINE.json's metric (profiles/fine_stage.py)
             try:
@@ -975,7 +1048,7 @@ def main():
                 res["fine_stage"] = fine_stage.measure(dev, N, H, W)
             except Exception as e:          # the headline line must not depend on the extra block
                 res["fine_stage"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:      # the CPU leg is timed on rank 0 of the 1-GPU run only
+        if world == 1 and args.full and not args.no_cpu_baseline:      # the CPU leg is timed on rank 0 of the 1-GPU run only
             f0, _, cam0 = cam_for(0)
             res["cpu_baseline"] = cpu_baseline(scene, cam0, frame=f0)
         print(json.dumps(res), flush=True)
@@ -1003,6 +1076,8 @@ def bench_forward_only(args, cfg, scene, model, render, cam_for, bg, opts, _lib,
         dt = time.perf_counter() - t0
     prof = _lib.profile_read()
     _lib.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_arrays(o, model))
     st = o["raster_call"].last_status()
     V, D = st["num_visible"], st["num_rendered"]
     T = ((W + 15) // 16) * ((H + 15) // 16)
@@ -1020,7 +1095,7 @@ def bench_forward_only(args, cfg, scene, model, render, cam_for, bg, opts, _lib,
                "roofline": {"bound": "hbm", "kernel": "preprocess", "achieved": round(ab["preprocess"] / 1e9 / (k1_ms * 1e-3), 1), "peak": HBM_PEAK_GBS,
                             "unit": "GB/s", "frac": round(ab["preprocess"] / 1e9 / (k1_ms * 1e-3) / HBM_PEAK_GBS, 5), "traffic": None,
                             "algorithmic_bytes_per_launch": ab["preprocess"], "avg_launch_ms": round(k1_ms, 5)}}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             f0, _, cam0 = cam_for(0)
             res["cpu_baseline"] = cpu_baseline(scene, cam0, frame=f0)
         print(json.dumps(res), flush=True)
@@ -1052,6 +1127,8 @@ def bench_exchange_only(args, dp, model, params, one_step, cam_for, campos_dev, 
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:          # the exchanged gradients of the last timed exchange
+        dump_outputs(args.dump_outputs, step_arrays({}, model))
     if world > 1:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)

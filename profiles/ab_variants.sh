@@ -2,7 +2,7 @@
 # A/B of library builds inside ONE gpurun call (boxes differ by +-2.5 %): bash profiles/ab_variants.sh [bench flags --] NAME1 NAME2 ...
 # Each NAME is emd_amd/csrc/variants/lib_NAME.so (EMD_LIB_PATH selects the build); "base" is the in-tree library.  The list is run in the
 # order given; put "base" first and last to see the drift of the box.  Everything in front of a literal `--` is passed to bench.py.
-FLAGS="--steps 20 --warmup 5 --no-cpu-baseline --no-fine-stage"
+FLAGS="--steps 20 --warmup 5 --full --no-cpu-baseline --no-fine-stage"
 NAMES=()
 seen_sep=0
 for a in "$@"; do [ "$a" = "--" ] && seen_sep=1; done

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 # repeats, 20 of the 26 forward and 20 of the 26 backward dispatches of a pass are the timed steps (the rest: one sizing step and five warm-up steps on
 # frames 0..4; the five pair-statistics steps run a differently named instantiation of K7 and re-run timed frames for the other kernels)
 # (--no-fine-stage under rocprofv3: the fine_stage block uses torch.profiler, i.e. roctracer, which must not run inside a traced process)
-B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-fine-stage"
+B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-fine-stage"
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o stats -- $B > "$OUT/bench_profiled.json" 2> "$OUT/stats.err"
 timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o stats_eager -- $B --eager > "$OUT/bench_profiled_eager.json" 2> "$OUT/stats_eager.err"
 P="$B --eager --settle-ms 0 --repeats 0"
@@ -25,8 +25,8 @@ timeout 420 rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INST
 python3 profiles/make_pmc_summary.py "$OUT" > "$OUT/${R}_pmc_hbm_traffic.csv"
 python3 profiles/make_valu_summary.py "$OUT" > "$OUT/${R}_pmc_valu.csv"
 cp "$OUT/${R}_pmc_hbm_traffic.csv" "$OUT/${R}_pmc_valu.csv" profiles/
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_line_driver_flags.json" 2> "$OUT/bench_line.err"
-timeout 600 python3 bench.py > "$OUT/bench_line.json" 2>> "$OUT/bench_line.err"
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_line_driver_flags.json" 2> "$OUT/bench_line.err"
+timeout 600 python3 bench.py --full > "$OUT/bench_line.json" 2>> "$OUT/bench_line.err"
 # keep the merge-back small: the raw traces are large
 rm -f "$OUT"/*_kernel_trace.csv "$OUT"/*_counter_collection.csv
 ls -la "$OUT"

@@ -81,7 +81,7 @@ def test_bench_config4_two_ranks_agree_through_the_density_control_event():
     (bench.py asserts the point counts agree), the step recorded again, more steps."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(EMD_BENCH_SHARE_GPU="1", EMD_DP_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "4", "--steps", "4", "--warmup", "1", "--repeats", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "4", "--steps", "4", "--warmup", "1", "--repeats", "0", "--full",
            "--gaussians", "300000", "--height", "160", "--width", "240"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2500:]

@@ -49,7 +49,7 @@ def test_bench_step_with_the_exchange_over_rccl_on_one_gpu(one_graph):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), EMD_DP_FORCE="1", EMD_DP_INIT_WORLD1="1", RANK="0",
                WORLD_SIZE="1", LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--factored-sh", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-           "--gaussians", "60000", "--height", "128", "--width", "192"] + (["--one-graph"] if one_graph else [])
+           "--full", "--gaussians", "60000", "--height", "128", "--width", "192"] + (["--one-graph"] if one_graph else [])
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

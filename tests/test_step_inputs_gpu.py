@@ -76,7 +76,7 @@ def test_bench_multi_gpu_presets_run_as_the_per_rank_workload(config, extra):
     """BASELINE configs[3] (4-camera rig, deformation residual as an input of the fused transform) and configs[4] (6-camera rig, 48 actors,
     densification statistics every step + one density-control event behind the timed steps) at --gpus 1 = the per-rank workload."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--steps", "6", "--warmup", "2", "--repeats", "1",
-                        "--no-cpu-baseline"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2500:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     c = d["config"]
@@ -92,3 +92,33 @@ def test_bench_multi_gpu_presets_run_as_the_per_rank_workload(config, extra):
         for e in (first, ev):
             assert e["cloned"] + e["split"] > 0 and e["n_after"] == e["n_before"] + e["cloned"] + e["split"] - e["pruned"]
             assert e["overflow_after"] == 0 and e["ms_per_step_after"] > 0 and e["re_record_ms"] > 0
+
+
+def test_bench_dump_outputs_of_a_replayed_and_an_eager_run_agree(tmp_path):
+    """`--dump-outputs`: two processes with the same arguments, one replaying the recorded step and one issuing it from Python (--eager), write
+    the outputs of the same last timed step -- images and radii bit for bit, loss and gradients within the float-atomic tolerance of the replay
+    self-check.  A run without --full prints the headline line only."""
+    import numpy as np
+    runs = {}
+    for name, extra in (("replay", []), ("eager", ["--eager"])):
+        out = tmp_path / name
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--gaussians", "60000",
+                            "--height", "128", "--width", "192", "--dump-outputs", str(out)] + extra, cwd=ROOT, capture_output=True, text=True,
+                           timeout=600)
+        assert p.returncode == 0, p.stderr[-2500:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+        assert not {"roofline", "cpu_baseline", "fine_stage"} & set(d) and d["repeats_ms_per_step"] is None
+        assert d["config"]["step_issue"].startswith("hipGraph replay" if name == "replay" else "eager")
+        runs[name] = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    a, b = runs["replay"], runs["eager"]
+    assert set(a) == set(b) and {"render", "depth", "weight", "normal", "radii", "loss", "grad_means2D", "grad_xyz", "grad_features",
+                                 "grad_instances_quats", "grad_embeddings"} <= set(a), sorted(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+        if k in ("render", "depth", "weight", "normal", "radii"):
+            assert np.array_equal(a[k], b[k]), k
+        else:
+            assert np.abs(a[k] - b[k]).max() <= 1e-4 * max(float(np.abs(b[k]).max()), 1e-12), k
+    assert float(np.abs(a["grad_xyz"]).max()) > 0
