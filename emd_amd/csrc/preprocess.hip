@@ -695,7 +695,11 @@ __device__ __forceinline__ void motion_point_backward(int i, int a_id, const flo
 }
 
 // Segmented reduction of per-point pose gradients into dL_dactor_pose.  Actor points are stored contiguously
-// per instance (rigid.py:53-145), so most waves hold one actor id: DPP wave sum, one atomic row per wave.
+// per instance (rigid.py:53-145), so most waves hold one actor id: DPP wave sum, one atomic row per wave -- as ONE
+// wave-instruction with twelve lanes.  Float atomics execute at the memory side, one 64-byte request per wave-instruction, and
+// all of an actor's adds land on the same line or two: twelve one-lane adds per wave (30 000 requests onto 12 lines in the
+// headline step) held K8 at 0.19 ms, 0.15 without any (profiles/r07_preprocess_ab.txt).  A wave holding several ids adds lane by lane.
+// (the sums reach lanes 0..11 through readlane: the same thing through LDS costs K8 six spilled registers)
 __device__ __forceinline__ void reduce_pose_grad(int a_id, const float pose_g[12], float* __restrict__ dL_dpose) {
     const unsigned long long has = __ballot(a_id >= 0);
     if (!has) return;
@@ -703,11 +707,15 @@ __device__ __forceinline__ void reduce_pose_grad(int a_id, const float pose_g[12
     const int a0 = __builtin_amdgcn_readlane(a_id, first);
     const bool uniform = __ballot(a_id >= 0 && a_id != a0) == 0ull;
     if (uniform) {
+        const int lane = threadIdx.x & 63;
+        float mine = 0.f;                   // lane k < 12: component k of the wave's sum
 #pragma unroll
         for (int k = 0; k < 12; k++) {
-            float v = wave_reduce_to_lane63(a_id >= 0 ? pose_g[k] : 0.f);
-            if ((threadIdx.x & 63) == 63) atomicAdd(dL_dpose + (size_t)a0 * EMD_ACTOR_STRIDE + k, v);
+            const float v = wave_reduce_to_lane63(a_id >= 0 ? pose_g[k] : 0.f);
+            const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+            mine = lane == k ? t : mine;
         }
+        if (lane < 12) atomicAdd(dL_dpose + (size_t)a0 * EMD_ACTOR_STRIDE + lane, mine);
     } else if (a_id >= 0) {
 #pragma unroll
         for (int k = 0; k < 12; k++) atomicAdd(dL_dpose + (size_t)a_id * EMD_ACTOR_STRIDE + k, pose_g[k]);
