@@ -55,8 +55,13 @@ POSE_TERM_RTOL = 2e-6
 
 
 def make_case(n=2000, H=64, W=96, seed=0, sh_degree=3, colors_precomp=False, cov_precomp=False, motion=False,
-              residual=False, bg=(0.1, 0.2, 0.3), scale_mult=3.0, actors=3, yaw=0.0):
-    """A street-like scene squeezed into the frustum of a small camera so that most Gaussians are visible."""
+              residual=False, bg=(0.1, 0.2, 0.3), scale_mult=3.0, actors=3, yaw=0.0, scale_modifier=1.0, near_plane=0.2,
+              clamp01=False, normal_loss=False):
+    """A street-like scene squeezed into the frustum of a small camera so that most Gaussians are visible.
+
+    `scale_modifier` / `near_plane` are the settings of the call; `clamp01` sets the OmniRe colour clamp (F_CLAMP01 /
+    RasterOptions.clamp_rgb01); `normal_loss` draws a loss gradient for the normal image (case["dL_dnormal"], else None) from a
+    generator of its own, so that every other input is the same as without it."""
     sc = scenes.make_static_scene(n, seed=seed)
     cam = scenes.small_camera(H, W, yaw=yaw)
     means = sc.means.clone()
@@ -73,7 +78,8 @@ def make_case(n=2000, H=64, W=96, seed=0, sh_degree=3, colors_precomp=False, cov
                 means3D=means, opacities=torch.sigmoid(sc.opacity_logits),
                 scales=torch.exp(sc.log_scales) * scale_mult, rotations=sc.quats.clone(), shs=sc.shs.clone(),
                 colors_precomp=None, cov3D_precomp=None, actor_ids=None, actor_pose=None, residual_dx=None,
-                residual_dq=None, flags=co.F_NORMAL)
+                residual_dq=None, flags=co.F_NORMAL | (co.F_CLAMP01 if clamp01 else 0), scale_modifier=float(scale_modifier),
+                near_plane=float(near_plane))
     if colors_precomp:
         case["colors_precomp"] = torch.rand(n, 3, generator=g)
         case["shs"] = None
@@ -116,7 +122,39 @@ def make_case(n=2000, H=64, W=96, seed=0, sh_degree=3, colors_precomp=False, cov
     case["dL_dcolor"] = gg.standard_normal((3, H, W)).astype(np.float32)
     case["dL_ddepth"] = (0.1 * gg.standard_normal((1, H, W))).astype(np.float32)
     case["dL_dalpha"] = gg.standard_normal((1, H, W)).astype(np.float32)
+    case["dL_dnormal"] = np.random.default_rng(seed + 6).standard_normal((3, H, W)).astype(np.float32) if normal_loss else None
     return case
+
+
+def place_in_depth_band(case, idx, lo, hi, seed=0):
+    """Move the Gaussians `idx` to view-space depths drawn uniformly in (lo, hi), inside the camera's frustum, and shrink their scales
+    with the depth so that their footprints stay a few pixels wide.  Draws from a generator of its own."""
+    g = torch.Generator().manual_seed(seed + 3000)
+    V = case["cam"].world_view_transform.float()
+    c = case["cam"].camera_center.float()
+    k = len(idx)
+    z = lo + (hi - lo) * (0.05 + 0.9 * torch.rand(k, generator=g))
+    x = z * case["cam"].tanfovx * (1.6 * torch.rand(k, generator=g) - 0.8)
+    y = z * case["cam"].tanfovy * (1.6 * torch.rand(k, generator=g) - 0.8)
+    case["means3D"][idx] = c[None] + z[:, None] * V[:3, 2][None] + x[:, None] * V[:3, 0][None] + y[:, None] * V[:3, 1][None]
+    if case["scales"] is not None:
+        case["scales"][idx] = (0.04 + 0.08 * torch.rand(k, 3, generator=g)) * z[:, None]
+    case["opacities"][idx] = 0.5 + 0.4 * torch.rand(k, *case["opacities"].shape[1:], generator=g)
+    return z
+
+
+def boost_dc(case, seed=0, mean=0.9, std=1.2):
+    """Add a random offset to the DC term of every Gaussian's SH colour, so that many channels leave [0, 1] on both sides (the
+    colour clamps).  Draws from a generator of its own."""
+    g = torch.Generator().manual_seed(seed + 4000)
+    case["shs"][:, 0, :] += mean + std * torch.randn(case["N"], 3, generator=g)
+
+
+def clamp_counts(orc):
+    """(visible colour channels clamped down to 1, visible colour channels clamped up to 0) of an oracle result."""
+    pre = orc["pre"]
+    cl = (pre["clamped"] != 0) & (pre["radii"] > 0)[:, None]
+    return int((cl & (pre["rgb"] == 1.0)).sum()), int((cl & (pre["rgb"] == 0.0)).sum())
 
 
 def _quat_mul_np(a, b):
@@ -126,11 +164,12 @@ def _quat_mul_np(a, b):
                      w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2], 1).astype(np.float32)
 
 
-def oracle_settings(case, near_plane=0.2):
+def oracle_settings(case, near_plane=None):
     cam = case["cam"]
     return co.make_settings(case["H"], case["W"], cam.tanfovx, cam.tanfovy, case["bg"].numpy(),
                             cam.world_view_transform.numpy(), cam.full_proj_transform.numpy(), case["sh_degree"],
-                            cam.camera_center.numpy(), 1.0, near_plane)
+                            cam.camera_center.numpy(), case.get("scale_modifier", 1.0),
+                            case.get("near_plane", 0.2) if near_plane is None else near_plane)
 
 
 def oracle_scene(case):
@@ -147,19 +186,54 @@ def run_oracle(case, backward=False):
     pre, b, img = co.forward(S, sc, case["flags"])
     out = dict(pre=pre, bin=b, img=img, S=S, scene=sc)
     if backward:
-        out["grads"] = co.backward(S, sc, pre, b, img, case["dL_dcolor"], case["dL_ddepth"], case["dL_dalpha"], None,
-                                   case["flags"])
+        out["grads"] = co.backward(S, sc, pre, b, img, case["dL_dcolor"], case["dL_ddepth"], case["dL_dalpha"],
+                                   case.get("dL_dnormal"), case["flags"])
     return out
 
 
-def run_hip(case, backward=False, device="cuda:0", absgrad=False, factored_sh_grad=False, keep_all_pairs=False):
-    """The product path: emd_amd.GaussianRasterizer -> C ABI -> HIP kernels."""
+SHARED_GRADS = ("means3D", "means2D", "opacities", "scales", "rotations", "cov3D", "actor_pose", "residual_dx", "residual_dq",
+                "means2D_abs")
+
+
+def run_oracle_extra_sets(case, feats, dL_dextra):
+    """The reference of one call that composites the colour sets `feats` ([N,3] each) on the side of the main pass (`colors_extra=`):
+    the main pass plus one colors_precomp pass per set, as separate calls compute them (loss: dL_dextra[k] on that set's image, no
+    depth / alpha / normal loss).  Returns the main pass's result with
+      * "extra": the oracle result of every feature pass (their images, and their dL/dcolors as the reference of dL/dcolors_extra);
+      * "grads": the gradients of the inputs the passes share summed over all passes, dL/dshs of the main pass, and "render_grads"
+        summed the same way (the render backward's rgb rows are the main set's; the feature passes' are in their own results)."""
+    orc = run_oracle(case, backward=True)
+    g = orc["grads"]
+    total = {k: (None if g.get(k) is None else np.asarray(g[k], np.float64).copy()) for k in SHARED_GRADS}
+    rg = {k: np.asarray(v, np.float64).copy() for k, v in g["render_grads"].items()}
+    passes = []
+    for f, G in zip(feats, dL_dextra):
+        case_f = dict(case, shs=None, colors_precomp=f, dL_dcolor=G, dL_ddepth=None, dL_dalpha=None, dL_dnormal=None)
+        of = run_oracle(case_f, backward=True)
+        passes.append(of)
+        for k in SHARED_GRADS:
+            if total[k] is not None and of["grads"].get(k) is not None:
+                total[k] += np.asarray(of["grads"][k], np.float64).reshape(total[k].shape)
+        for k in rg:
+            if k != "rgb":
+                rg[k] += np.asarray(of["grads"]["render_grads"][k], np.float64).reshape(rg[k].shape)
+    grads = dict(g)
+    grads.update({k: v for k, v in total.items() if v is not None})
+    grads["render_grads"] = rg
+    return dict(orc, grads=grads, extra=passes)
+
+
+def run_hip(case, backward=False, device="cuda:0", absgrad=False, factored_sh_grad=False, keep_all_pairs=False, colors_extra=None,
+            dL_dextra=None, **options):
+    """The product path: emd_amd.GaussianRasterizer -> C ABI -> HIP kernels.  The call's scale modifier, near plane, colour clamp and
+    normal image follow the case; `colors_extra` (a list of [N,3] tensors) are composited by the same call, `dL_dextra` (numpy
+    [3,H,W] each) their images' loss gradients; further keyword arguments are RasterOptions fields (aux_stream=, no_sync=, ...)."""
     from emd_amd import GaussianRasterizationSettings, GaussianRasterizer
     cam = case["cam"]
     dev = torch.device(device)
     d = lambda t, rg=backward: None if t is None else t.to(dev).clone().requires_grad_(rg and t.is_floating_point())
     rs = GaussianRasterizationSettings(image_height=case["H"], image_width=case["W"], tanfovx=cam.tanfovx,
-                                       tanfovy=cam.tanfovy, bg=case["bg"].to(dev), scale_modifier=1.0,
+                                       tanfovy=cam.tanfovy, bg=case["bg"].to(dev), scale_modifier=case.get("scale_modifier", 1.0),
                                        viewmatrix=cam.world_view_transform.to(dev),
                                        projmatrix=cam.full_proj_transform.to(dev), sh_degree=case["sh_degree"],
                                        campos=cam.camera_center.to(dev), prefiltered=False, debug=True)
@@ -167,19 +241,23 @@ def run_hip(case, backward=False, device="cuda:0", absgrad=False, factored_sh_gr
              opacities=d(case["opacities"]), scales=d(case["scales"]), rotations=d(case["rotations"]),
              cov3Ds_precomp=d(case["cov3D_precomp"]), actor_pose=d(case["actor_pose"]),
              residual_dx=d(case["residual_dx"]), residual_dq=d(case["residual_dq"]))
+    X = None if colors_extra is None else [d(x) for x in colors_extra]
     means2D = torch.zeros(case["N"], 3, device=dev, requires_grad=backward)
-    rast = GaussianRasterizer(rs, compute_normal=True, absgrad=absgrad, factored_sh_grad=factored_sh_grad, keep_render_grads=backward,
-                              keep_all_pairs=keep_all_pairs)   # options belong to this instance
+    rast = GaussianRasterizer(rs, compute_normal=bool(case["flags"] & co.F_NORMAL), absgrad=absgrad, factored_sh_grad=factored_sh_grad,
+                              keep_render_grads=backward, keep_all_pairs=keep_all_pairs, near_plane=case.get("near_plane", 0.2),
+                              clamp_rgb01=bool(case["flags"] & co.F_CLAMP01), **options)   # options belong to this instance
     kw = {}
     if case["flags"] & co.F_MOTION:
         kw = dict(actor_ids=None if case["actor_ids"] is None else case["actor_ids"].to(dev), actor_pose=T["actor_pose"],
                   residual_dx=T["residual_dx"], residual_dq=T["residual_dq"])
-    color, depth, normal, alpha, radii, _ = rast(means3D=T["means3D"], means2D=means2D, shs=T["shs"],
-                                                 colors_precomp=T["colors_precomp"], opacities=T["opacities"],
-                                                 scales=T["scales"], rotations=T["rotations"],
-                                                 cov3Ds_precomp=T["cov3Ds_precomp"], extra_attrs=None, **kw)
+    color, depth, normal, alpha, radii, extra = rast(means3D=T["means3D"], means2D=means2D, shs=T["shs"],
+                                                     colors_precomp=T["colors_precomp"], opacities=T["opacities"],
+                                                     scales=T["scales"], rotations=T["rotations"],
+                                                     cov3Ds_precomp=T["cov3Ds_precomp"], extra_attrs=None, colors_extra=X, **kw)
     out = dict(color=color.detach().cpu().numpy(), depth=depth.detach().cpu().numpy(),
                normal=normal.detach().cpu().numpy(), alpha=alpha.detach().cpu().numpy(), radii=radii.cpu().numpy())
+    if X is not None:
+        out["extra"] = [e.detach().cpu().numpy() for e in extra]
     keys, ids, ranges, masks = rast.export_binning(with_masks=True)
     out["keys"] = keys.cpu().numpy().view(np.uint64)
     out["ids"] = ids.cpu().numpy().view(np.uint32)
@@ -193,12 +271,18 @@ def run_hip(case, backward=False, device="cuda:0", absgrad=False, factored_sh_gr
         tc = lambda a: torch.from_numpy(a).to(dev)
         loss = (color * tc(case["dL_dcolor"])).sum() + (depth * tc(case["dL_ddepth"])).sum() + \
                (alpha * tc(case["dL_dalpha"])).sum()
+        if case.get("dL_dnormal") is not None:
+            loss = loss + (normal * tc(case["dL_dnormal"])).sum()
+        if X is not None:
+            loss = loss + sum((e * tc(G)).sum() for e, G in zip(extra, dL_dextra))
         loss.backward()
         g = lambda t: None if t is None or t.grad is None else t.grad.detach().cpu().numpy()
         out["grads"] = dict(means3D=g(T["means3D"]), means2D=g(means2D), shs=g(T["shs"]), colors=g(T["colors_precomp"]),
                             opacities=g(T["opacities"]), scales=g(T["scales"]), rotations=g(T["rotations"]),
                             cov3D=g(T["cov3Ds_precomp"]), actor_pose=g(T["actor_pose"]), residual_dx=g(T["residual_dx"]),
                             residual_dq=g(T["residual_dq"]))
+        if X is not None:
+            out["grads"]["colors_extra"] = [g(x) for x in X]
         if absgrad:
             out["grads"]["means2D_abs"] = rast.last_call.absgrad.cpu().numpy()
             assert means2D.absgrad is rast.last_call.absgrad          # gsplat convention: also published on the grad sink
@@ -378,8 +462,11 @@ CONDITIONED = ("scales", "rotations", "cov3D", "residual_dq", "log_scales", "raw
 def hip_render_grads(call, W, H):
     """The render backward's accumulator rows of a call made with keep_render_grads=True, in the oracle's dict layout."""
     r = call.render_grads.detach().cpu().numpy()
-    return dict(mean2D=r[:, 0:2].copy(), depth=r[:, 2].copy(), opacity=r[:, 3].copy(), conic=r[:, 4:7].copy(), rgb=r[:, 7:10].copy(),
-                abs=r[:, 10:12].copy(), normal=np.zeros((r.shape[0], 3), np.float32))
+    out = dict(mean2D=r[:, 0:2].copy(), depth=r[:, 2].copy(), opacity=r[:, 3].copy(), conic=r[:, 4:7].copy(), rgb=r[:, 7:10].copy(),
+               abs=r[:, 10:12].copy(), normal=np.zeros((r.shape[0], 3), np.float32))
+    for k in range((r.shape[1] - 12) // 4):            # (r, g, b, -) of every extra colour set
+        out[f"rgb_extra{k}"] = r[:, 12 + 4 * k:15 + 4 * k].copy()
+    return out
 
 
 def compare_render_grads(hip_g, orc_g, names=("mean2D", "conic", "opacity", "rgb", "depth")):
@@ -464,8 +551,9 @@ def raw_params_parity(case, log_s, raw_q, logit, device="cuda:0", check_images_e
     ocase["rotations"] = rots
     orc = run_oracle(ocase, backward=True)
     cam = case["cam"]
-    rs = GaussianRasterizationSettings(case["H"], case["W"], cam.tanfovx, cam.tanfovy, case["bg"], 1.0, cam.world_view_transform,
-                                       cam.full_proj_transform, case["sh_degree"], cam.camera_center, False, False)
+    rs = GaussianRasterizationSettings(case["H"], case["W"], cam.tanfovx, cam.tanfovy, case["bg"], case.get("scale_modifier", 1.0),
+                                       cam.world_view_transform, cam.full_proj_transform, case["sh_degree"], cam.camera_center, False, False)
+    opts = dict(near_plane=case.get("near_plane", 0.2), clamp_rgb01=bool(case["flags"] & co.F_CLAMP01))
     means = case["means3D"].to(dev).requires_grad_(True)
     shs = case["shs"].to(dev).requires_grad_(True)
     m2 = torch.zeros(N, 3, device=dev, requires_grad=True)
@@ -479,7 +567,7 @@ def raw_params_parity(case, log_s, raw_q, logit, device="cuda:0", check_images_e
         rdx = kw["residual_dx"] = case["residual_dx"].to(dev).requires_grad_(True)
     if case.get("residual_dq") is not None:
         rdq = kw["residual_dq"] = case["residual_dq"].to(dev).requires_grad_(True)
-    rast = GaussianRasterizer(rs, compute_normal=True, keep_render_grads=True)
+    rast = GaussianRasterizer(rs, compute_normal=True, keep_render_grads=True, **opts)
     color, depth, normal, alpha, radii, _ = rast(means3D=means, means2D=m2, shs=shs, opacities=logit, scales=log_s,
                                                  rotations=raw_q, raw_params=True, **kw)
     keys, ids, ranges, masks = rast.export_binning(with_masks=True)
@@ -492,7 +580,7 @@ def raw_params_parity(case, log_s, raw_q, logit, device="cuda:0", check_images_e
     cull = hb["cull_stats"]
     # ... and upstream's list itself, entry for entry, with keep_all_pairs (forward only; same images bit for bit)
     with torch.no_grad():
-        rast_all = GaussianRasterizer(rs, compute_normal=True, keep_all_pairs=True)
+        rast_all = GaussianRasterizer(rs, compute_normal=True, keep_all_pairs=True, **opts)
         c_all, d_all, n_all, a_all, r_all, _ = rast_all(means3D=means.detach(), means2D=m2.detach(), shs=shs.detach(), opacities=logit.detach(),
                                                         scales=log_s.detach(), rotations=raw_q.detach(), raw_params=True,
                                                         **{k_: (v.detach() if v.is_floating_point() else v) for k_, v in kw.items()})

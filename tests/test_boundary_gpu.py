@@ -159,7 +159,7 @@ def test_one_binning_many_colour_sets(n_extra):
     call's projection, sort and list walk: every extra image equals the separate call's image BIT FOR BIT (and the oracle's), and
     the gradients equal those of the three separate calls / the sum of three oracle backward passes."""
     from emd_amd import GaussianRasterizer
-    from tests.helpers import run_oracle, assert_grad_close
+    from tests.helpers import assert_grad_close
     case = make_case(n=7000, H=96, W=128, seed=23)
     rs = _settings(case)
     gen = torch.Generator().manual_seed(2)
@@ -187,22 +187,20 @@ def test_one_binning_many_colour_sets(n_extra):
     loss1 = (img1 * G[0].to(DEV)).sum() + (depth1 * Gd.to(DEV)).sum() + (alpha1 * Ga.to(DEV)).sum() + sum((i * g.to(DEV)).sum() for i, g in zip(extra, G[1:]))
     loss1.backward()
     # (c) the oracle: three forward / backward passes, gradients of the shared inputs summed
+    from tests.helpers import run_oracle_extra_sets
     case_o = dict(case, dL_dcolor=G[0].numpy(), dL_ddepth=Gd.numpy(), dL_dalpha=Ga.numpy())
-    orc = run_oracle(case_o, backward=True)
-    total = {k: np.asarray(orc["grads"][k], np.float64).copy() for k in ("means3D", "means2D", "opacities", "scales", "rotations")}
-    for k, f in enumerate(feats):
-        case_f = dict(case, shs=None, colors_precomp=f, dL_dcolor=G[1 + k].numpy(), dL_ddepth=None, dL_dalpha=None)
-        of = run_oracle(case_f, backward=True)
+    orc = run_oracle_extra_sets(case_o, feats, [g.numpy() for g in G[1:]])
+    for k, of in enumerate(orc["extra"]):
         got_img = extra[k].detach().cpu().numpy()
         assert int((got_img.view(np.uint32) != of["img"]["color"].view(np.uint32)).sum()) == 0, "extra image differs from the oracle's"
         assert_grad_close(f_one[k].grad.cpu().numpy(), of["grads"]["colors"], f"colors_extra[{k}]")
         assert_grad_close(f_one[k].grad.cpu().numpy(), f_sep[k].grad.cpu().numpy(), f"colors_extra[{k}] vs separate call")
-        for name in total:
-            total[name] += np.asarray(of["grads"][name], np.float64).reshape(total[name].shape)
     from tests.helpers import END2END_ATOL_FRAC, END2END_REL_L2
-    for name in total:          # (scales / rotations: end-to-end floor of the ill-conditioned conic -> covariance chain, tests/helpers.py)
+    for name in ("means3D", "means2D", "opacities", "scales", "rotations"):
+        # (scales / rotations: end-to-end floor of the ill-conditioned conic -> covariance chain, tests/helpers.py)
         loose = name in ("scales", "rotations")
-        assert_grad_close(t1[name].grad.cpu().numpy(), total[name], name, atol_frac=END2END_ATOL_FRAC if loose else None, rel_l2=END2END_REL_L2 if loose else None)
+        assert_grad_close(t1[name].grad.cpu().numpy(), orc["grads"][name], name, atol_frac=END2END_ATOL_FRAC if loose else None,
+                          rel_l2=END2END_REL_L2 if loose else None)
     assert_grad_close(t1["shs"].grad.cpu().numpy(), orc["grads"]["shs"], "shs")
 
 
