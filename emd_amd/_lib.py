@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libemd_raster.so")
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 MAX_EXTRA = 2
 SETTINGS_DEV_FLOATS = 38
 TILE = 16
@@ -222,7 +222,10 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_refine_decide", "emd_refine_index", "emd_after_train_stats", "emd_densify_scan",
                     "emd_mlp_trunk_forward", "emd_mlp_trunk_backward", "emd_mlp_branch_forward", "emd_mlp_branch_backward",
                     "emd_abs_mean_backward", "emd_residual_l1_backward", "emd_tracked_pose_forward", "emd_tracked_pose_backward",
-                    "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws")
+                    "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
+                    "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward")
+KNN_MAX_K = 32
+EMBED_REG_SCRATCH_WORDS = 2048
 PROF_STAGES = 8
 
 _lib = None
@@ -308,6 +311,14 @@ def load():
     lib.emd_tracked_pose_backward.argtypes = [C.POINTER(EmdTrackedPoseArgs), C.POINTER(EmdTrackedPoseGrads), C.c_void_p]
     lib.emd_sky_forward.argtypes = [C.POINTER(EmdSkyArgs), C.c_void_p]
     lib.emd_sky_backward.argtypes = [C.POINTER(EmdSkyBwdArgs), C.c_void_p]
+    lib.emd_knn_workspace.argtypes = [C.c_int32, C.c_int32]
+    lib.emd_knn_workspace.restype = C.c_size_t
+    lib.emd_knn.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_knn_reverse_workspace.argtypes = [C.c_int32, C.c_int32]
+    lib.emd_knn_reverse_workspace.restype = C.c_size_t
+    lib.emd_knn_reverse.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_embed_reg_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
+    lib.emd_embed_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p

@@ -697,3 +697,17 @@ int emd_launch_export_keys(int64_t D, const GeomWs& g, const BinWs& b, uint64_t*
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }
+
+// The radix passes above for callers outside the rasterizer (knn.hip): stable LSD sort of (key, element index) pairs by the low 8 * passes bits
+// of n 32-bit keys.  The first pass drops the keys equal to 0xFFFFFFFF and publishes the number kept in *count (device); the sorted pairs end
+// in keys[(passes - 1) & 1] / vals[(passes - 1) & 1].  hist: 256 * ceil(n / EMD_SORT_TILE) words.
+int emd_launch_sort_pairs(const uint32_t* keys_in, uint32_t n, int passes, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t* hist,
+                          uint32_t* count, hipStream_t st) {
+    if (n == 0 || passes < 1) return EMD_OK;
+    const SortN c0 = {nullptr, nullptr, n}, cv = {count, nullptr, 0u};
+    int rc = radix_pass<8, true>(keys_in, nullptr, keys[0], vals[0], c0, (size_t)n, 0, 8, 0u, hist, false, 32, nullptr, count, st);
+    for (int p = 1; p < passes && !rc; p++)
+        rc = radix_pass<8, false>(keys[(p - 1) & 1], vals[(p - 1) & 1], keys[p & 1], vals[p & 1], cv, (size_t)n, 8 * p, 8, 0u, hist, false, 32, nullptr,
+                                  nullptr, st);
+    return rc;
+}

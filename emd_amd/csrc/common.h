@@ -172,6 +172,8 @@ int emd_launch_preprocess(const PreArgs& a, int part, hipStream_t st);       // 
 int emd_launch_binning(const EmdSettings& s, int flags, int N, const GeomWs& g, const BinWs& b, int64_t capacity, EmdStatus* status,
                        hipStream_t st);                                       // binning.hip
 int emd_launch_export_keys(int64_t D, const GeomWs& g, const BinWs& b, uint64_t* keys, uint32_t* ids, uint32_t* quad_masks, hipStream_t st);  // binning.hip
+int emd_launch_sort_pairs(const uint32_t* keys_in, uint32_t n, int passes, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t* hist,
+                          uint32_t* count, hipStream_t st);   // binning.hip: the radix passes for other callers (knn.hip)
 // extra colour sets composited by the same list walk as the main colours (EmdFwdArgs.colors_extra ...)
 struct EmdExtra {
     int num;

@@ -181,6 +181,7 @@ class GaussianModel:
         self.spatial_lr_scale = 0.0
         self.densify_seed = int(densify_seed)      # Philox key of the split samples (identical on all ranks)
         self.densify_events = 0                    # mixed into the key: a fresh draw per event
+        self._knn_table = None                     # cached neighbour table of the embedding regulariser (knn_table)
 
     # ---- accessors (gaussian_model.py:120-146) ------------------------------------------------------------------------------------
     get_xyz = property(lambda self: self._xyz)
@@ -212,6 +213,28 @@ class GaussianModel:
         self._embedding = P(torch.zeros(n, self.gaussian_embedding_dim))
         self.max_radii2D = torch.zeros(n, device=dev)
         self._deformation_table = torch.ones(n, dtype=torch.bool, device=dev)
+        self._knn_table = None
+
+    def create_from_pcd(self, xyz, rgb, spatial_lr_scale=1.0):
+        """create_from_pcd (gaussian_model.py:152-181) from the cloud's positions [N,3] and colours [N,3] in 0..1 (tensors or arrays):
+        dist2 = clamp_min(distCUDA2(xyz), 1e-7), scales = log(sqrt(dist2)) on all three axes, then `create_from_tensors`.  distCUDA2 is
+        emd_amd.knn.distCUDA2 (the exact 3-nearest-neighbour search of csrc/knn.hip) in place of the CUDA-only simple_knn package."""
+        from .knn import distCUDA2
+        xyz = torch.as_tensor(xyz).to(self.device).float().contiguous()
+        dist2 = torch.clamp_min(distCUDA2(xyz), 0.0000001)
+        scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+        self.create_from_tensors(xyz, torch.as_tensor(rgb), scales, spatial_lr_scale)
+
+    def knn_table(self, k=20, weight_fn=None):
+        """The neighbour table of the embedding regulariser (emd_amd.knn.KnnTable over the current positions), cached until the point count
+        changes: densify / prune drop it and the next call builds a new one -- WHEN that happens is the trainer's decision, density control
+        never rebuilds it.  A table the caller still holds from before such an event is refused by `embedding_reg` (ValueError).  Moving points
+        do not invalidate the cache: call `knn_table(...).refresh(self.get_xyz)` to follow them."""
+        from .knn import KnnTable
+        t = self._knn_table
+        if t is None or t.N != self._xyz.shape[0] or t.k != int(k) or t.weight_fn is not weight_fn:
+            t = self._knn_table = KnnTable(self._xyz, k=k, weight_fn=weight_fn)
+        return t
 
     def training_setup(self, training_args):
         """The ten named groups of gaussian_model.py:188-201 (deformation / grid / sky only when those modules are attached); the
@@ -434,6 +457,7 @@ class GaussianModel:
             del old
         if mode == L.DENSIFY_MODE_DENSIFY:
             self.densify_events += 1
+        self._knn_table = None                     # the rows moved: the cached neighbour table describes another point set
         return n_keep, n_clone, n_split
 
     def densify(self, max_grad, min_opacity, extent, max_screen_size, density_threshold=None, displacement_scale=None, model_path=None,

@@ -29,6 +29,8 @@
  *   emd_deform_input_forward/backward   <- get_embedder + get_deformation OmniRe/models/modules.py:318-366, nodes/deformable.py:35-47
  *   emd_densification_stats             <- add_densification_stats       S3Gaussian/scene/gaussian_model.py:728-730, train.py:403-406
  *   emd_adam_step                       <- optimizer.step()              S3Gaussian/scene/gaussian_model.py:188-201, train.py:428
+ *   emd_knn / emd_knn_reverse           <- simple_knn distCUDA2, o3d_knn S3Gaussian/scene/gaussian_model.py:152-181 (create_from_pcd), train.py:326-337
+ *   emd_embed_reg_forward / backward    <- weighted_l2_loss_v2 over the neighbour table   S3Gaussian/train.py:326-337
  *   emd_sh_grad_from_factors            (multi-GPU: rebuilds the SH gradient from all-gathered rank-one factors; no reference counterpart)
  *   emd_compact_rows / emd_scatter_rows (multi-GPU: visibility-compacted gradient rows for 2 / 4 ranks; no reference counterpart)
  *
@@ -55,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EMD_ABI_VERSION 27
+#define EMD_ABI_VERSION 28
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
 #define EMD_TILE_X 16
@@ -868,6 +870,47 @@ typedef struct EmdAdamArgs {
 } EmdAdamArgs;
 
 int emd_adam_step(const EmdAdamArgs* args, void* hip_stream);
+
+/* ---- ABI 28: exact k nearest neighbours in 3-D, and the embedding regulariser over the neighbour table ---------------------------
+ * Replaces `simple_knn._C.distCUDA2` (create_from_pcd's initial scales: mean squared distance to the 3 nearest neighbours,
+ * S3Gaussian/scene/gaussian_model.py:152-181) and the `o3d_knn` + `weighted_l2_loss_v2` pair of the fine stage (train.py:326-337).
+ *
+ * emd_knn: for every point n of pts [N,3] the k nearest OTHER points (1 <= k <= EMD_KNN_MAX_K), rows ascending in d2:
+ *   idx [N,k] int32 (may be NULL), d2 [N,k] fp32 (may be NULL), mean_d2 [N] = (d2[n,0] + ... + d2[n,k-1]) / k (may be NULL; k = 3: distCUDA2).
+ *   - exact: row n holds the k smallest d2(n,m), m != n.  Self is excluded by index, so coincident points are neighbours at distance 0.
+ *   - d2(n,m) = dx*dx + dy*dy + dz*dz in fp32 from the fp32 coordinates (fused multiply-adds).  Which of several equidistant points is
+ *     returned is unspecified; the call is deterministic (same input, same output).
+ *   - fewer than k other points: the missing slots hold idx = -1, d2 = +inf (and mean_d2 = +inf).
+ *   - a point with a NaN or infinite coordinate gets a row of -1 / +inf and is nobody's neighbour.
+ * No host synchronisation; `workspace` holds emd_knn_workspace(N, k) bytes (0 is returned for invalid arguments).
+ * Method: 30-bit Z-order keys over the finite points' bounding box, the radix sort of the binning stage, leaves of 64 consecutive sorted
+ * points and groups of 64 leaves with their min / max corners; a wave owns the 64 queries of one leaf, seeds their candidate lists
+ * (registers) from the neighbouring leaves and then visits only the leaves whose box lies nearer than the current k-th distance. */
+#define EMD_KNN_MAX_K 32
+size_t emd_knn_workspace(int32_t num_points, int32_t k);
+int emd_knn(int32_t num_points, int32_t k, const float* pts, int32_t* idx, float* d2, float* mean_d2, void* workspace, size_t workspace_bytes,
+            void* hip_stream);
+/* The transposed adjacency of idx [N,k] in CSR form: rev_start [N+1], rev_slot [N*k] = the flat positions m*k + j of the entries with
+ * idx[m,j] == n, for n = 0 .. N-1 one after the other, ascending inside every n (entries < 0 are left out: rev_start[N] of the N*k slots
+ * are written).  Built once per table, so that the regulariser's backward gathers instead of scattering with float atomics. */
+size_t emd_knn_reverse_workspace(int32_t num_points, int32_t k);
+int emd_knn_reverse(int32_t num_points, int32_t k, const int32_t* idx, int32_t* rev_start, int32_t* rev_slot, void* workspace,
+                    size_t workspace_bytes, void* hip_stream);
+/* loss[0] = (1 / P) sum over the P pairs with idx[n,j] >= 0 of sqrt(w[n,j] * |e[n] - e[idx[n,j]]|^2 + 1e-20); loss[1] = 1 / P (0 when P = 0).
+ * e [N,E] fp32 with E in {4, 8, 16, 32}, 16-byte aligned; w [N,k] or NULL (= 1).  c [N,k] (optional) receives w / sqrt(...) per pair (0 where
+ * idx < 0) for the backward.  One launch; the sum is formed in a fixed order through the granule table `scratch`
+ * (EMD_EMBED_REG_SCRATCH_WORDS 4-byte words, 8-byte aligned, zero at the first call and left zero by every call, one stream at a time), as
+ * emd_l1_loss_ws does: no zero fill, no float atomics. */
+#define EMD_EMBED_REG_SCRATCH_WORDS 2048
+int emd_embed_reg_forward(int32_t num_points, int32_t k, int32_t embed_dim, const float* e, const int32_t* idx, const float* w, float* c,
+                          float* loss /*[2]*/, uint32_t* scratch, void* hip_stream);
+/* grad_e[n] (+)= g[0] * inv_pairs[0] * ( sum_j c[n,j] (e[n] - e[idx[n,j]])  +  sum over the slots s = m*k + j of rev(n) of c[s] (e[n] - e[m]) ),
+ * both sums gathers in a fixed order: bit-identical from run to run.  g [1] = dL/dloss and inv_pairs [1] = loss[1] of the forward, on the
+ * device.  c == NULL: the factors are recomputed from w and e.  accumulate != 0 adds to grad_e, otherwise grad_e is overwritten.
+ * No gradient flows to w or to the positions. */
+int emd_embed_reg_backward(int32_t num_points, int32_t k, int32_t embed_dim, const float* e, const int32_t* idx, const float* w, const float* c,
+                           const int32_t* rev_start, const int32_t* rev_slot, const float* g, const float* inv_pairs, float* grad_e,
+                           int32_t accumulate, void* hip_stream);
 
 #ifdef __cplusplus
 }
