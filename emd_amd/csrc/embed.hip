@@ -396,7 +396,7 @@ __global__ void __launch_bounds__(EMD_WAVE) k_track_heads(EmdTrackArgs a, EmdTra
 // float atomics into a 296-float accumulator that the FORWARD launch of the same step cleared (EmdTrackedPoseArgs.head_acc; a
 // last-workgroup reduction with release / acquire fences was measured first: 28 us for the backward launch against 9), so no
 // output needs a fill launch.  The pose arithmetic is the one of k_actor_pose_*
-// (preprocess.hip), evaluated without contraction so that both produce the same bits.
+// (standalone_ops.hip), evaluated without contraction so that both produce the same bits.
 // ---------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tp_quat_mul(const float a[4], const float b[4], float o[4]) {
 #pragma clang fp contract(off)

@@ -280,7 +280,7 @@ __device__ __forceinline__ void load_row(const float* __restrict__ e, uint32_t n
 }
 
 // One pair per thread and trip.  The sum and the pair count leave every workgroup as two 8-byte {value, tag} granules; workgroup 0 adds them in
-// workgroup order (the scheme of k_l1_loss, preprocess.hip: nobody but workgroup 0 waits, so it cannot deadlock) and writes loss, 1 / pairs.
+// workgroup order (the scheme of k_l1_loss, standalone_ops.hip: nobody but workgroup 0 waits, so it cannot deadlock) and writes loss, 1 / pairs.
 template <int E>
 __global__ void __launch_bounds__(REG_THREADS) k_embed_reg_fwd(uint32_t N, uint32_t k, const float* __restrict__ e, const int32_t* __restrict__ idx,
                                                                const float* __restrict__ w, float* __restrict__ c, float* __restrict__ loss,

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Machine-code identity of the projection unit across its split into preprocess.hip + standalone_ops.hip.
+
+    python profiles/compare_kernel_isa.py OLD_TREE NEW_TREE > profiles/preprocess_split_isa.txt      # CPU only: hipcc -S cross-compiles gfx950
+
+OLD_TREE is a checkout of the commit before the split (`git worktree add` / `git archive`), NEW_TREE a checkout at or after it.  OLD_TREE's
+emd_amd/csrc/preprocess.hip and NEW_TREE's preprocess.hip + standalone_ops.hip are compiled to assembly the way profiles/make_isa_mix.py does
+(hipcc -S --cuda-device-only), with the flags NEW_TREE's Makefile gives for the unit (`make print-flags-<unit>`; both units carry
+-ffp-contract=off -fno-slp-vectorize, as preprocess.hip did before).  For every `.amdhsa_kernel` symbol the instruction text of the function and
+its `.amdhsa_*` descriptor block are compared after exactly these normalisations:
+
+    * the function index inside local labels (.LBB<n>_<m> -> .LBB_<m>, .Lfunc_begin<n> / .Lfunc_end<n> likewise): a kernel's position in its unit;
+    * the __hip_cuid_* symbol (a hash of the compilation);
+    * .file / .loc / .ident lines, comments and blank lines.
+
+Passes (exit status 0) when the kernel symbols of the two new units together are exactly those of the old unit, no symbol is in both, and
+every kernel is identical.  One line per kernel: name, VGPRs, SGPRs, LDS bytes, scratch bytes, verdict."""
+import difflib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+OLD_UNITS = ("preprocess",)
+NEW_UNITS = ("preprocess", "standalone_ops")
+
+
+def unit_flags(tree, unit):
+    csrc = os.path.join(tree, "emd_amd", "csrc")
+    out = subprocess.run(["make", "-s", "--no-print-directory", "-C", csrc, f"print-flags-{unit}"], check=True, capture_output=True, text=True).stdout
+    return [f for f in out.split() if not f.startswith("-I")]
+
+
+def assemble(tree, unit, flags):
+    csrc = os.path.join(tree, "emd_amd", "csrc")
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, unit + ".s")
+        cmd = ["/opt/rocm/bin/hipcc", *flags, f"-I{os.path.join(tree, 'include')}", "-S", "--cuda-device-only", os.path.join(csrc, unit + ".hip"), "-o", out]
+        r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True, cwd=csrc)
+        if r.returncode:
+            sys.exit(f"{' '.join(cmd)}\n{r.stderr}")
+        return open(out).read().splitlines()
+
+
+def normalise(lines):
+    out = []
+    for l in lines:
+        s = l.split(";")[0].strip()
+        if not s or s.startswith((".file", ".loc", ".ident")):
+            continue
+        s = re.sub(r"\.(LBB|Lfunc_begin|Lfunc_end)\d+", r".\1", s)
+        s = re.sub(r"__hip_cuid_\w+", "__hip_cuid", s)
+        out.append(" ".join(s.split()))
+    return out
+
+
+def kernels_of(lines):
+    """-> {symbol: dict(body, desc, vgpr, sgpr, lds, scratch)}"""
+    res = {}
+    for k, l in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l)
+        if not m:
+            continue
+        sym = m.group(1)
+        end = next(j for j in range(k, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
+        desc = lines[k + 1:end]
+        start = next(j for j, x in enumerate(lines) if x.startswith(sym + ":"))
+        fend = next(j for j in range(start, len(lines)) if lines[j].startswith(".Lfunc_end"))
+        # the register / memory figures the compiler prints behind the function
+        info = {}
+        for j in range(fend, min(fend + 40, len(lines))):
+            mm = re.match(r";\s*(TotalNumSgprs|TotalNumVgprs|ScratchSize|LDSByteSize):\s*(\d+)", lines[j])
+            if mm:
+                info[mm.group(1)] = int(mm.group(2))
+        res[sym] = dict(body=normalise(lines[start + 1:fend]), desc=normalise(desc), vgpr=info["TotalNumVgprs"], sgpr=info["TotalNumSgprs"],
+                        lds=info["LDSByteSize"], scratch=info["ScratchSize"])
+    return res
+
+
+def demangle(syms):
+    try:
+        out = subprocess.run(["c++filt"], input="\n".join(syms), check=True, capture_output=True, text=True).stdout.split("\n")
+        return {s: re.sub(r"^void |\(anonymous namespace\)::|\(.*", "", d) for s, d in zip(syms, out)}
+    except (OSError, subprocess.CalledProcessError):
+        return {s: s for s in syms}
+
+
+def main():
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    old_tree, new_tree = (os.path.abspath(p) for p in sys.argv[1:3])
+    flags = {u: unit_flags(new_tree, u) for u in NEW_UNITS}
+    old, new, where = {}, {}, {}
+    for u in OLD_UNITS:
+        old.update(kernels_of(assemble(old_tree, u, flags[u])))
+    ok = True
+    for u in NEW_UNITS:
+        ks = kernels_of(assemble(new_tree, u, flags[u]))
+        for s in ks:
+            if s in new:
+                print(f"# FAIL: {s} is in {where[s]}.hip and in {u}.hip")
+                ok = False
+            where[s] = u
+        new.update(ks)
+    names = demangle(sorted(set(old) | set(new)))
+    print("# profiles/compare_kernel_isa.py: every kernel of the old emd_amd/csrc/preprocess.hip against the same kernel of the new preprocess.hip /")
+    print("# standalone_ops.hip; `hipcc -S --cuda-device-only`, gfx950, flags: " + " ".join(flags["preprocess"]))
+    print("# compared: the instruction text of the function and its .amdhsa_* descriptor, modulo local-label function indices, __hip_cuid_*, comments")
+    print(f"# {'kernel':28s} {'unit':15s} {'VGPRs':>5s} {'SGPRs':>5s} {'LDS B':>6s} {'scratch B':>9s}  verdict")
+    for s in sorted(set(old) | set(new), key=lambda s: (where.get(s, "~"), names[s], s)):
+        if s not in new or s not in old:
+            print(f"{names[s]:30s} {where.get(s, '-'):15s} {'':>5s} {'':>5s} {'':>6s} {'':>9s}  {'MISSING in the new units' if s not in new else 'NOT in the old unit'}  ({s})")
+            ok = False
+            continue
+        o, n = old[s], new[s]
+        same = o["body"] == n["body"] and o["desc"] == n["desc"]
+        ok &= same
+        anon = "_GLOBAL__N_" in s
+        print(f"{names[s]:30s} {where[s]:15s} {n['vgpr']:5d} {n['sgpr']:5d} {n['lds']:6d} {n['scratch']:9d}  {'identical' if same else 'DIFFERENT'}"
+              f"{'' if anon else '  (outside the anonymous namespace)'}")
+        if not same:
+            for what in ("desc", "body"):
+                for d in list(difflib.unified_diff(o[what], n[what], "old", "new", lineterm="", n=1))[:40]:
+                    print("#     " + d)
+    print(f"# {len(old)} kernels in the old unit, {len(new)} in the new units ({', '.join(f'{u}.hip {sum(1 for s in new if where[s] == u)}' for u in NEW_UNITS)}): "
+          + ("ALL IDENTICAL" if ok else "FAILED"))
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
