@@ -28,8 +28,8 @@
 //   - the duplicate count D stays on the device (EmdStatus.num_rendered); every kernel here is launched on the
 //     caller-provided capacity and bounds itself by D, so the forward pass needs no host read-back to proceed.
 //   - duplication is balanced over output slots, not Gaussians: a 256-thread block scans the tile counts of its
-//     256 Gaussians (DPP wave scan + LDS), then lane e writes slot e, finding its Gaussian by binary search in
-//     LDS -- consecutive lanes write consecutive pairs (coalesced 4 B + 4 B stores) regardless of footprint size.
+//     256 Gaussians (DPP wave scan + LDS), then lane e writes slot e, reading its Gaussian from a max-scan of head
+//     marks in LDS -- consecutive lanes write consecutive pairs (coalesced 4 B + 4 B stores) regardless of footprint size.
 //   - ranking inside a radix block is wave-ballot based (8 ballots per key give the set of lanes with the same digit;
 //     no LDS atomics in the ranking loop), which keeps every pass stable.
 #include <string.h>
@@ -43,9 +43,6 @@
 // of the three depth scatters grows by 7 us (16 KB more LDS per block, 8 more bytes per element each way): 798 against 803 it/s on one box.
 #ifndef EMD_BIN_CARRY
 #define EMD_BIN_CARRY 0
-#endif
-#ifndef EMD_DUP_SCAN_OWNER
-#define EMD_DUP_SCAN_OWNER 1
 #endif
 
 namespace {
@@ -102,7 +99,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_sorted_counts(int N, const uint32
 // Balanced over OUTPUT slots: workgroup b writes slots [2048 b, 2048 (b + 1)) and walks the blocks of 256 depth-ordered
 // Gaussians that own them (the nearest Gaussians cover thousands of tiles each and all sit at the front of the order, so
 // a Gaussian-block-per-workgroup split would leave a long tail).  Inside a Gaussian block the owner of a slot is found
-// by binary search over the block's exclusive offsets in LDS; consecutive lanes write consecutive pairs.
+// by a running maximum over head marks in LDS (see the loop); consecutive lanes write consecutive pairs.
 // An output block of 2048 slots IS a block of the first tile-sort pass, so the digit histogram of that pass is built here, from
 // the tile ids while they are in registers (hist0: [bin][block], bin-major over the capacity block count): the pass's own
 // histogram launch (a second read of all D tile ids) is gone.
@@ -132,10 +129,8 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_duplicate(int N, int gx, const ui
     __shared__ uint32_t s_id[EMD_BLOCK];
     __shared__ uint32_t s_hs[EMD_BLOCK];       // height | skip-top << 10 | skip-bottom << 11
     __shared__ uint32_t s_h0[EMD_BLOCK];       // digit histogram of tile pass 0 (at most 8 bits per pass)
-#if EMD_DUP_SCAN_OWNER
     __shared__ __attribute__((aligned(16))) uint16_t s_own[DUP_SLOTS];      // owner (index in the Gaussian block + 1) of every slot of the window: head marks, then their running maximum
     __shared__ uint32_t s_wmax[8];             // per-wave maxima of the owner scan [0..3], of the first-slot owner [4..7]
-#endif
     s_h0[threadIdx.x] = 0;
     // ---- every workgroup scans the pair counts of the 256-Gaussian blocks itself (the last depth pass left them in block_sums; 7812
     //      words at 2 M Gaussians, from L2): D, and where its own 2048 slots start.  This replaces a single-workgroup scan kernel whose
@@ -198,13 +193,11 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_duplicate(int N, int gx, const ui
         const uint32_t pid_raw = perm[i < V ? i : 0u];                          // (requested with the record, not behind its count)
         const uint2 br = (i < V) ? br_raw : make_uint2(0u, 0u);
         const uint32_t cnt = ((br.x >> 20) & 1023u) * (br.y & 1023u);
-#if EMD_DUP_SCAN_OWNER
         // Round 5: the owner of a slot comes from a running maximum over head marks instead of an 8-step binary search per slot (64 dependent
         // LDS reads per thread and Gaussian block: the kernel's longest chain).  Every Gaussian of the block with pairs marks the slot its run
         // starts at (distinct slots), the Gaussian that covers the window's first slot marks slot 0, and one block-wide max-scan over the window
         // (8 consecutive slots per thread + a DPP scan of the threads' maxima) leaves every slot's owner in LDS.
         reinterpret_cast<uint4*>(s_own)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);                 // (ordered before the marks by the scan's barriers)
-#endif
         uint32_t total;
         const uint32_t inc = block_scan_add_u32(cnt, s_scan, &total);
         const uint32_t end = base + total;
@@ -213,7 +206,6 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_duplicate(int N, int gx, const ui
         s_id[threadIdx.x] = cnt ? pid_raw : 0u;
         s_hs[threadIdx.x] = br.y & 4095u;
         const uint32_t lo_slot = max(S0, base), hi_slot = min(S1, end);
-#if EMD_DUP_SCAN_OWNER
         {
             const uint32_t st = base + inc - cnt;                                                    // first slot of this Gaussian's run
             if (cnt && st >= lo_slot && st < hi_slot) s_own[st - lo_slot] = (uint16_t)(threadIdx.x + 1u);
@@ -238,22 +230,10 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_duplicate(int N, int gx, const ui
             for (int k = 0; k < 8; k++) o[k] = max(o[k], pre);
             reinterpret_cast<uint4*>(s_own)[threadIdx.x] = make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
         }
-#endif
         __syncthreads();
         for (uint32_t eg = lo_slot + threadIdx.x; eg < hi_slot; eg += EMD_BLOCK) {
             const uint32_t e = eg - base;
-#if EMD_DUP_SCAN_OWNER
             const int lo = (int)s_own[eg - lo_slot] - 1;
-#else
-            // largest j with s_excl[j] <= e  (entries with cnt == 0 share offsets with their successor; the search
-            // lands on the last of an equal run, which is the one that owns slot e)
-            int lo = 0, hi = EMD_BLOCK - 1;
-#pragma unroll
-            for (int step = 0; step < 8; step++) {
-                int mid = (lo + hi + 1) >> 1;
-                if (s_excl[mid] <= e) lo = mid; else hi = mid - 1;
-            }
-#endif
             const uint32_t local_e = e - s_excl[lo];
             const uint32_t r = s_rect[lo];
             const uint32_t w = (r >> 20) & 1023u, x0 = r & 1023u, y0 = (r >> 10) & 1023u, hs = s_hs[lo];

@@ -271,10 +271,8 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_hexplane_time_tables(EmdHexArgs a
         }
 }
 
-#ifndef HEX_NT
-#define HEX_NT 1          /* round 5: the [N, 128] feature / gradient streams bypass the caches, the planes stay (fine-stage step 13.87 -> 13.72 ms; the same hint on the
-                             MLP kernels' tile loads costs 1.1 ms: 16-byte pieces of rows) */
-#endif
+// Round 5: the [N, 128] feature / gradient streams bypass the caches (nontemporal stores here, nontemporal loads of dL/dout in the backward), the planes
+// stay (fine-stage step 13.87 -> 13.72 ms; the same hint on the MLP kernels' tile loads costs 1.1 ms: 16-byte pieces of rows)
 typedef float hex_v4f __attribute__((ext_vector_type(4)));
 template <int C>
 __global__ void __launch_bounds__(EMD_BLOCK) k_hexplane_fwd4(EmdHexArgs a, unsigned chunks) {
@@ -352,11 +350,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_hexplane_fwd4(EmdHexArgs a, unsig
                 prod.z = prod.z * (nw.z * w.x + ne.z * w.y + sw.z * w.z + se.z * w.w);
                 prod.w = prod.w * (nw.w * w.x + ne.w * w.y + sw.w * w.z + se.w * w.w);
             }
-#if HEX_NT
             __builtin_nontemporal_store((hex_v4f){prod.x, prod.y, prod.z, prod.w}, reinterpret_cast<hex_v4f*>(a.out + ((size_t)s_n[j] * (S * C) + s * C + c4)));
-#else
-            *(float4*)(a.out + ((size_t)s_n[j] * (S * C) + s * C + c4)) = prod;
-#endif
         }
         __syncthreads();
     }
@@ -403,32 +397,18 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_hexplane_fwd4(EmdHexArgs a, unsig
 //  * a point's three plane positions and its index share one LDS row (s_pn): one read in front of the three deferred-row stores.
 //  * TWO workgroups of 512 threads per CU (256 points, 7 x 7 spatial windows, 80 KB each) instead of one of 1024: one computes while the other meets at
 //    its flush (3.69 -> 3.49 ms for the whole backward at 2 M points).
+//  * the staged tap offset, row stride and dx are in BYTES: four address instructions per plane in the gathers instead of seven (4.31 -> 4.25 ms);
+//  * the deferred rows (2.3 GB written by the main kernel, read once by the per-plane pass) bypass the caches: they evicted the planes the gathers and
+//    the cell-row atomics work on -- backward 3.55 -> 3.39 ms at 2 M points, fine-stage step 11.08 -> 10.99 ms.
 //  The numbers in the paragraphs above (12 x 12 / 32-cell windows, two iterations per staging call, one 1024-thread block owning 152 KB) describe the
 //  rounds they are dated with; the geometry now is HEX_AGG_THREADS / HEX_AGG_POINTS / HEX_SW / HEX_TW below.
-#ifndef HEX_STAGE_BYTES
-#define HEX_STAGE_BYTES 1  /* the staged tap offset, row stride and dx in BYTES: four address instructions per plane in the gathers instead of seven (4.31 -> 4.25 ms) */
-#endif
-#ifndef HEX_NT_ROWS
-#define HEX_NT_ROWS 1     /* the deferred rows (2.3 GB written by the main kernel, read once by the per-plane pass) bypass the caches: they evicted the planes the gathers
-                              and the cell-row atomics work on -- backward 3.55 -> 3.39 ms at 2 M points, fine-stage step 11.08 -> 10.99 ms */
-#endif
-#ifndef HEX_STAGE_ITERS
-#define HEX_STAGE_ITERS 0  /* iterations staged per stage() call: 0 = as many as fit the wave's lanes (4 at 32 channels, 2 at 16) */
-#endif
-#ifndef HEX_NEXT_SCALE_EARLY
-#define HEX_NEXT_SCALE_EARLY 1
-#endif
-#ifndef HEX_AGG_THREADS
 #define HEX_AGG_THREADS 512              /* round 5 (end): TWO workgroups of 512 threads per CU (80 KB of LDS each at 32 channels; four waves per SIMD as before) instead of one of
                                             1024 -- while one meets at its flush (barrier, atomics, the next scale's first round trip) the other one computes, and a barrier holds
                                             8 waves instead of 16: backward 3.69 -> 3.49 ms at 2 M points, fine-stage step 11.50 -> 11.25 ms */
 #define HEX_AGG_POINTS 256               /* points per workgroup: 16 iterations per wave between two flushes (one workgroup of 1024 threads: 512 points were worth 0.16 ms over 256) */
 #define HEX_SW 7                         /* spatial window: HEX_SW x HEX_SW cells (finer scales go through the per-plane pass) */
-#endif
-#ifndef HEX_TW
 #define HEX_TW 19                        /* time-plane window of a scale with spatial windows: HEX_TW marginal cells, or (HEX_TW / 2) x 2 cells; a deferred scale gives each time
                                             plane a third of all cells (68: a run of 256 points spans 35 - 50 cells of a 512-cell axis) */
-#endif
 #define HEX_SCELLS (HEX_SW * HEX_SW)
 #define HEX_WIN_CELLS (3 * HEX_SCELLS + 3 * HEX_TW)
 
@@ -442,10 +422,10 @@ __device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0
 template <int C, int DT>
 __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexArgs a, EmdHexGrads g, unsigned chunk_stride) {
     constexpr int WAVES = HEX_AGG_THREADS / 64, GW = 64 / C, PER_WAVE = HEX_AGG_POINTS / WAVES, ITERS = PER_WAVE / GW, GROUPS = HEX_AGG_THREADS / C;
-    // staging: one stage() call prepares the rows of SK iterations (lane = (iteration, point, plane): 48 of 64 lanes busy at 32 channels) into a ring of
-    // SK + 1 iteration slots -- when the call for the next SK iterations runs, at the top of the last iteration of the current group, that
-    // iteration's rows are the only live ones
-    constexpr int IROWS = GW * 6, SK = HEX_STAGE_ITERS ? HEX_STAGE_ITERS : (64 / IROWS >= 4 ? 4 : 2), RING = SK + 1, SROWS = RING * IROWS;
+    // staging: one stage() call prepares the rows of SK iterations (as many as fit the wave's lanes: 4 at 32 channels, 2 at 16; lane =
+    // (iteration, point, plane): 48 of 64 lanes busy at 32 channels) into a ring of SK + 1 iteration slots -- when the call for the next SK
+    // iterations runs, at the top of the last iteration of the current group, that iteration's rows are the only live ones
+    constexpr int IROWS = GW * 6, SK = 64 / IROWS >= 4 ? 4 : 2, RING = SK + 1, SROWS = RING * IROWS;
     static_assert(SK * IROWS <= 64 && C <= 32 && PER_WAVE % GW == 0 && ITERS % SK == 0, "staging geometry");
     __shared__ double win[HEX_WIN_CELLS * C];           // fp64 cells: ds_add_f64 is the one native LDS float add that runs at rate on gfx950
     __shared__ uint4 s_a[WAVES * SROWS];                // per wave, a ring of (point, plane) rows: BYTE offset of tap (x0, y0), row stride to y1 in bytes, window address, dx * 4 | sy << 8
@@ -507,7 +487,7 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
     const int sb = wave * SROWS;                        // the wave's staging rows
     // ---- the scale the waves are staging and gathering for (`cs`): its resolutions, the block's anchor cells, its window layout.  It runs ONE
     // stage() + gather() ahead of the scale `s` being scattered and flushed: the first gathers of scale s + 1 are requested before the block
-    // meets at the flush of scale s (HEX_NEXT_SCALE_EARLY), so their latency passes under the barrier and the flush instead of in front of an
+    // meets at the flush of scale s, so their latency passes under the barrier and the flush instead of in front of an
     // idle CU -- after a flush all sixteen waves sit in the same phase and nothing hides a round trip
     int cs = 0, anc[4], rs[4], tw = 0, tbase = 0, twx = 0;
     bool deferred = false;
@@ -556,8 +536,7 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
                     int slot = it % RING + k2;
                     slot -= slot >= RING ? RING : 0;
                     const int row = sb + slot * IROWS + rem;
-                    constexpr int SH = HEX_STAGE_BYTES ? 2 : 0;
-                    s_a[row] = make_uint4(tap_at(tx.i0, ty.i0, W, C, 0) << SH, ((uint32_t)(ty.i1 - ty.i0) * (uint32_t)W * (uint32_t)C) << SH, lds, (dx << SH) | (sy << 8));
+                    s_a[row] = make_uint4(tap_at(tx.i0, ty.i0, W, C, 0) << 2, ((uint32_t)(ty.i1 - ty.i0) * (uint32_t)W * (uint32_t)C) << 2, lds, (dx << 2) | (sy << 8));
                     // grid_sampler_2d: nw * (1-fx)(1-fy) + ne * fx (1-fy) + sw * (1-fx) fy + se * fx fy; the clamped neighbour
                     // (x1 == x0 at the border) contributes no slope: its weight is 0 and the clip mask is 0
                     s_w[row] = make_float4(tx.f, ty.f, tx.ds, ty.ds);
@@ -570,16 +549,12 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
         auto gather = [&](int it) {
             n = s_pn[wave * PER_WAVE + it * GW + gw].w;
             if (n >= 0) {
-                go = HEX_NT ? __builtin_nontemporal_load(g.dL_dout + ((size_t)n * (S * C) + cs * C + c)) : g.dL_dout[(size_t)n * (S * C) + cs * C + c];
+                go = __builtin_nontemporal_load(g.dL_dout + ((size_t)n * (S * C) + cs * C + c));
 #pragma unroll
                 for (int p = 0; p < 6; p++) {
                     const uint4 A = s_a[sb + (it % RING) * IROWS + gw * 6 + p];
                     const char* __restrict__ pl = HEX_PL(p);
-#if HEX_STAGE_BYTES
                     const uint32_t dx = A.w & 0xffu, o00 = A.x + ((uint32_t)c << 2), dy = A.y;          // (bytes, as staged)
-#else
-                    const uint32_t dx = (A.w & 0xffu) << 2, o00 = (A.x + c) << 2, dy = A.y << 2;
-#endif
                     nw[p] = *(const float*)(pl + o00); ne[p] = *(const float*)(pl + (o00 + dx));
                     sw[p] = *(const float*)(pl + (o00 + dy)); se[p] = *(const float*)(pl + (o00 + dy + dx));
                 }
@@ -661,11 +636,7 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
                     if (p == 2 || !HEX_GP(p)) continue;
                     const int pidx = p == 3 ? 2 : p;                      // the row itself, at the point's position in that plane's order (plain store)
                     char* rows = (char*)(g.defer_rows + (defer_base + pidx) * (size_t)a.num_points * C);
-#if HEX_NT_ROWS
                     __builtin_nontemporal_store(gi[p], (float*)(rows + (((uint32_t)(pidx == 0 ? P.x : (pidx == 1 ? P.y : P.z)) * C + c) << 2)));
-#else
-                    *(float*)(rows + (((uint32_t)(pidx == 0 ? P.x : (pidx == 1 ? P.y : P.z)) * C + c) << 2)) = gi[p];
-#endif
                 }
             }
 #else
@@ -694,7 +665,7 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
                     const uint4 A = s_a[rowb + p];                       // (read again: cheaper than live registers)
                     const float4 F = s_w[rowb + p];
                     const float gx1 = gi[p] * F.x, gx0 = gi[p] - gx1;      // gi (1 - fx), gi fx: the x-marginals of the four weights
-                    const uint32_t dx = (A.w & 0xffu) >> (HEX_STAGE_BYTES ? 2 : 0), sy = A.w >> 8;
+                    const uint32_t dx = (A.w & 0xffu) >> 2, sy = A.w >> 8;       // (dx is staged in bytes; the windows are indexed in cells)
                     if (A.z != 0xffffffffu) {
                         double* w0 = &win[A.z + c];
                         if (marg) {                                       // the x-marginals: the two time rows summed
@@ -709,8 +680,7 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
                         }
                     } else {
                         char* g0 = (char*)gp;
-                        constexpr int USH = HEX_STAGE_BYTES ? 0 : 2;
-                        const uint32_t b00 = (A.x << USH) + ((uint32_t)c << 2), bdx = (A.w & 0xffu) << USH, bdy = A.y << USH;
+                        const uint32_t b00 = A.x + ((uint32_t)c << 2), bdx = A.w & 0xffu, bdy = A.y;
                         const float s0 = gx0 * F.y, s1 = gx1 * F.y;
                         atomicAdd((float*)(g0 + b00), gx0 - s0);
                         atomicAdd((float*)(g0 + (b00 + bdx)), gx1 - s1);
@@ -731,9 +701,7 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
         float* gpl[6];
 #pragma unroll
         for (int p = 0; p < 6; p++) gpl[p] = g.dL_dplanes[s][p];
-#if HEX_NEXT_SCALE_EARLY
         if (s + 1 < S) first_rows(s + 1);
-#endif
         __syncthreads();
         // ---- flush: every touched cell row goes to HBM once; the windows are left clean for the next scale.  The plane of a cell varies
         // over the lane groups: its gradient pointer and its width are SELECTED from scalars (indexing the kernel arguments by a lane value
@@ -763,9 +731,6 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
             }
         }
         __syncthreads();
-#if !HEX_NEXT_SCALE_EARLY
-        if (s + 1 < S) first_rows(s + 1);
-#endif
     }
     // dL/dpts through normalize_aabb (the time coordinate is used as given)
     if (want_dq)
@@ -797,15 +762,9 @@ __global__ void __launch_bounds__(HEX_AGG_THREADS, 4) k_hexplane_bwd_agg(EmdHexA
 // row (sequential in defer_rows, all loads of a lane group in flight at once), four LDS adds, then the flush.  Round 4: 1.30 -> 0.74 ms
 // at 2 M points (Hilbert orders 1.08; a workgroup per scale instead of a loop over the scales 1.05; 12 x 12 windows, i.e. 3 -> 4 resident
 // workgroups per CU: the chain load -> taps -> adds -> flush is latency, and what hides it is the number of chains in flight).
-#ifndef HEX_PL_THREADS
 #define HEX_PL_THREADS 512
-#endif
-#ifndef HEX_PL_POINTS
 #define HEX_PL_POINTS 256
-#endif
-#ifndef HEX_PW
 #define HEX_PW 12                        /* 12 x 12 fp64 cells + staging = 39.9 KB: four workgroups (32 waves) per CU */
-#endif
 template <int C>
 __global__ void __launch_bounds__(HEX_PL_THREADS) k_hexplane_bwd_plane(EmdHexArgs a, EmdHexGrads g) {
     constexpr int GROUPS = HEX_PL_THREADS / C, PER = HEX_PL_POINTS / GROUPS, WCELLS = HEX_PW * HEX_PW;
@@ -840,11 +799,7 @@ __global__ void __launch_bounds__(HEX_PL_THREADS) k_hexplane_bwd_plane(EmdHexArg
 #pragma unroll
         for (int k = 0; k < PER; k++) {
             const int j = group + GROUPS * k;
-#if HEX_NT_ROWS
-            gis[k] = __builtin_nontemporal_load(rows + ((size_t)min(first + j, (long)a.num_points - 1) * C + c));
-#else
-            gis[k] = rows[(size_t)min(first + j, (long)a.num_points - 1) * C + c];     // (clamped, not guarded: rows past the end are skipped below)
-#endif
+            gis[k] = __builtin_nontemporal_load(rows + ((size_t)min(first + j, (long)a.num_points - 1) * C + c));     // (clamped, not guarded: rows past the end are skipped below)
         }
         if (tid < 2) cmin[tid] = INT_MAX;
         __syncthreads();

@@ -38,20 +38,18 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define TS 36             // LDS row stride of a transposed 32 x 32 tile
 #define MLP_THREADS 256
 #define MLP_WAVES (MLP_THREADS / 64)
-// Two waves per SIMD (<= 256 registers each) where the accumulators allow it: a single wave exposes every LDS / HBM wait to the MFMA
-// pipe (measured: SQ_VALU_MFMA_BUSY_CYCLES = 45-59 % of the kernel time with one wave per SIMD).
-#ifndef MLP_FWD_WAVES
-#define MLP_FWD_WAVES 1
-#endif
-#ifndef MLP_BWD_WAVES
-#define MLP_BWD_WAVES 1
-#endif
 #define MLP_OCC(n) __attribute__((amdgpu_waves_per_eu(n, n)))
-// Kernels whose tiles fit 256 registers run two waves per SIMD (measured round 3: k_mlp_branch_fwd<1,1> 228 -> 219 us, k_mlp_trunk_bwd<0>
-// 504 -> 457 us at 2 M rows; the others spill at half the register file and lose).
-#define MLP_W_F11 2
-#define MLP_W_T0 2
-#define MLP_W_TB0 2
+// Waves per SIMD of every kernel family, written HERE only: the kernel's MLP_OCC(...) and its launcher both read it (a workgroup is four waves, one per
+// SIMD, so the value is also the number of persistent workgroups per CU: mlp_grid).  Two (<= 256 registers each) where the accumulators allow it: a
+// single wave exposes every LDS / HBM wait to the MFMA pipe (measured: SQ_VALU_MFMA_BUSY_CYCLES = 45-59 % of the kernel time with one wave per SIMD).
+// Measured round 3: k_mlp_branch_fwd<1,1> 228 -> 219 us, k_mlp_trunk_bwd<0> 504 -> 457 us at 2 M rows; the others spill at half the register file and
+// lose.  The narrow heads' forward keeps two WITH the folded L1 sum as well (195 -> 182 us at 2 M rows; 152 without the sum).
+// The trunk's forward and backward happen to agree today; they are two decisions about two kernels with different register needs, not one.
+constexpr int branch_fwd_waves(int depth, int nto) { return depth == 1 && nto == 1 ? 2 : 1; }
+constexpr int branch_bwd_waves = 1;
+constexpr int trunk_fwd_waves(int kta) { return kta == 0 ? 2 : 1; }
+constexpr int trunk_bwd_waves(int kta) { return kta == 0 ? 2 : 1; }
+constexpr int embed_bwd_waves = 1;
 
 __device__ __forceinline__ f32x16 zero16() {
     f32x16 z;
@@ -78,26 +76,11 @@ __device__ __forceinline__ f32x16 mask16(f32x16 g, f32x16 y) {
 // of the wave time): the forward kernels gain 12-15 % from the straight form.  (The backward kernels lost as much with it when this was written --
 // the product behind the load put the wait AT the load -- and kept the branch until round 5: they now use load_tile_raw / mask_tile below.)
 // `width` (a multiple of 4): columns >= width do not exist and read as 0 (the last tile of a narrow xa)
-// A/B knob (round 5): the [N, 64..128] activation / gradient streams of these kernels are each far larger than the 256 MiB Infinity Cache and
-// are touched once or twice per step; nontemporal accesses keep them from evicting what IS reused (the HexPlane planes, the weights).
-#ifndef MLP_NT
-#define MLP_NT 0
-#endif
-#ifndef MLP_L1_F11_TWO
-#define MLP_L1_F11_TWO 1      /* the narrow heads' forward WITH the folded L1 sum also runs two waves per SIMD (195 -> 182 us at 2 M rows; 152 without the sum) */
-#endif
-#ifndef MLP_NARROW_OUT
-#define MLP_NARROW_OUT 1      /* output layers of <= 4 features run on the vector pipe instead of a padded 32-row MFMA tile (forward) */
-#endif
-typedef float mlp_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4(const float* p) {
-    if (MLP_NT) { const mlp_v4f v = __builtin_nontemporal_load(reinterpret_cast<const mlp_v4f*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
-    return *(const float4*)p;
-}
-__device__ __forceinline__ void st4(float* p, float4 v) {
-    if (MLP_NT) __builtin_nontemporal_store((mlp_v4f){v.x, v.y, v.z, v.w}, reinterpret_cast<mlp_v4f*>(p));
-    else *(float4*)p = v;
-}
+// Plain loads and stores (round 5, measured): the [N, 64..128] activation / gradient streams of these kernels are each far larger than the 256 MiB
+// Infinity Cache and are touched once or twice per step, but nontemporal accesses on these 16-byte pieces of rows cost 1.1 ms of the fine-stage step
+// (hexplane.hip keeps the hint for its whole-row streams).  ld4 is a plain forwarder and stays one: with the load spelt out in load_tile's guarded arm the
+// compiler orders the backward kernels that use that arm (GO = 2, MULTI) differently.
+__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
 template <bool STRAIGHT = false>
 __device__ __forceinline__ f32x16 load_tile(const float* __restrict__ src, size_t ld, size_t row, bool ok, int c0, int hh, int width = 1 << 30) {
     f32x16 t;
@@ -137,7 +120,7 @@ __device__ __forceinline__ void store_tile(float* __restrict__ dst, size_t ld, s
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const int c = c0 + 8 * a + 4 * hh;
-        if (c < width) st4(dst + row * ld + c, make_float4(t[4 * a], t[4 * a + 1], t[4 * a + 2], t[4 * a + 3]));
+        if (c < width) *(float4*)(dst + row * ld + c) = make_float4(t[4 * a], t[4 * a + 1], t[4 * a + 2], t[4 * a + 3]);
     }
 }
 __device__ __forceinline__ void store_tile_narrow(float* __restrict__ dst, int width, size_t row, bool ok, int c0, int hh, f32x16 t) {
@@ -218,29 +201,10 @@ __device__ __forceinline__ void layer_fwd(f32x16 (&acc)[NT], const f32x16 (&in)[
 // {0-3, 8-11 | 4-7, 12-15} of the tile, k-block 1 = registers 8..15), so the accumulator of a layer is still the B operand of the next
 // one after its registers have been split (5.5 vector instructions per value), and the weights are staged in LDS as ready-made A fragments:
 //     image[term 0..2][out tile][k-block][lane] = uint4 of eight bf16 = term(M[32 tile + lane % 32][feature(k-block, lane / 32, 0..7)])
-// Per kernel (bit 0: the layers' products W x on split bf16, bit 1: the weight gradients' outer products): chosen from measurements at 2 M
+// Per kernel (mode bit 0: the layers' products W x on split bf16, bit 1: the weight gradients' outer products): chosen from measurements at 2 M
 // rows (profiles/r04_mlp_split_variants.txt) -- the split costs 176 vector instructions per 32 x 32 tile, which a kernel with few MFMAs per
-// tile (the forward of the narrow heads) does not earn back.
-#ifndef MLP_SP_F11
-#define MLP_SP_F11 1          /* forward, one output tile (dx / do / feat heads); round 5: 1 -- with the narrow output layer on the vector pipe the hidden
-                                 layer is what is left on the matrix pipe, and there the split wins (fine stage 13.61 -> 13.46 ms; 0 before: the split cost more
-                                 than it saved while a third of the MFMAs were a padded output tile) */
-#endif
-#ifndef MLP_SP_F12
-#define MLP_SP_F12 1          /* forward, two output tiles (the dshs head) */
-#endif
-#ifndef MLP_SP_B11
-#define MLP_SP_B11 3          /* backward, one output tile */
-#endif
-#ifndef MLP_SP_B12
-#define MLP_SP_B12 1          /* backward, two output tiles */
-#endif
-#ifndef MLP_SP_TF
-#define MLP_SP_TF 1           /* trunk forward (xa block) */
-#endif
-#ifndef MLP_SP_TB
-#define MLP_SP_TB 3           /* trunk backward (xa block) */
-#endif
+// tile does not earn back.  The heads' modes are branch_mode's table; the trunk's xa block (KTA > 0) runs its forward in mode 1 and its backward in
+// mode 3 (TrunkLds), the embedding-only trunk (KTA = 0) stays on fp32.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 struct Split { uint4 t[3][2]; };          // [term][k-block of the tile]
 __device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
@@ -438,26 +402,7 @@ __device__ __forceinline__ void stage_vector(float* __restrict__ dst, int n_pad,
     for (int idx = threadIdx.x; idx < n_pad; idx += MLP_THREADS) dst[idx] = (src && idx < n) ? src[idx] : 0.f;
 }
 
-// the xb block as ONE k-chunk of 8: register j of lane half hh holds xb[row][4 hh + j]
-template <bool STRAIGHT>
-__device__ __forceinline__ void load_xb(const float* __restrict__ xb, int kb, size_t row, bool ok, int hh, float (&v)[4]) {
-    if (STRAIGHT && xb && kb > 0) {
-        const float* p = xb + (ok ? row : 0) * (size_t)kb;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int c = 4 * hh + j;
-            const float x = p[c < kb ? c : 0];                   // (unconditional load, see load_tile)
-            v[j] = (ok && c < kb) ? x : 0.f;
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int c = 4 * hh + j;
-        v[j] = (ok && xb && c < kb) ? xb[row * (size_t)kb + c] : 0.f;
-    }
-}
-
+// The xb block is ONE k-chunk of 8: register j of lane half hh holds xb[row][4 hh + j].
 // The heads that recompute h: the next tile's embedding values travel RAW across the loop iteration (clamped address, unconditional loads) and are
 // masked where they are used -- masking at the load (a select, or a product) makes the compiler wait for the load right there, inside the tile loop.
 __device__ __forceinline__ void load_xb_raw(const float* __restrict__ xb, int kb, size_t row, bool ok, int hh, float (&v)[4]) {
@@ -487,13 +432,17 @@ __device__ __forceinline__ void embed_h(const float* __restrict__ wb, const floa
 // branch: [relu] -> Linear(64, 64) -> relu [-> Linear(64, 64) -> relu] -> Linear(64, out_dim)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // LDS (floats): W1 [64][WS] | W2 [64][WS] (DEPTH 2) | Wo [32 NTO][WS] | b1 [64] | b2 [64] | bo [64] | scratch [waves][32][TS] (backward)
-#ifndef MLP_SP_F2
-#define MLP_SP_F2 1           /* forward of the two-hidden-layer feature head: both hidden layers on split bf16 (round 5, late) */
-#endif
+// the split-bf16 mode of every head kernel (measurements: profiles/r04_mlp_split_variants.txt, docs/history/DESIGN_rounds_1-5.md)
 constexpr int branch_mode(int depth, int nto, bool bwd) {
-    // (the BACKWARD of the two-hidden-layer feature head keeps fp32 MFMA: its six images + transposes would need 167 KB of LDS; its forward has
-    //  three images only)
-    return depth != 1 ? (bwd ? 0 : MLP_SP_F2) : (bwd ? (nto == 1 ? MLP_SP_B11 : MLP_SP_B12) : (nto == 1 ? MLP_SP_F11 : MLP_SP_F12));
+    // two hidden layers (the feature head): the forward runs both hidden layers on split bf16 (round 5, late); the BACKWARD keeps fp32 MFMA -- its six
+    // images + transposes would need 167 KB of LDS, the forward has three images only
+    if (depth != 1) return bwd ? 0 : 1;
+    // one hidden layer, forward: products on split bf16 for one output tile (dx / do / feat heads) and for two (dshs).  One tile since round 5: with the
+    // narrow output layer on the vector pipe the hidden layer is what is left on the matrix pipe, and there the split wins (fine stage 13.61 -> 13.46 ms;
+    // before, the split cost more than it saved while a third of the MFMAs were a padded output tile)
+    if (!bwd) return 1;
+    // one hidden layer, backward: one output tile has the registers for split outer products too, two output tiles split the products only
+    return nto == 1 ? 3 : 1;
 }
 template <int DEPTH, int NTO, int MODE = 0>
 struct BranchLds {
@@ -561,7 +510,7 @@ __device__ __forceinline__ void branch_stage(float* lds, const EmdMlpBranch& a) 
         stage_split(lds + L::w1, 2, 4, a.w_hidden[0], 64, 0, 64, 64, false);
         if (DEPTH == 2) stage_split(lds + L::w2, 2, 4, a.w_hidden[1], 64, 0, 64, 64, false);        // (forward only: branch_mode)
         // (a narrow output layer runs on the vector pipe in the forward and reads plain fp32 rows: they fit the image's allocation)
-        if (!BWD && MLP_NARROW_OUT && NTO == 1 && a.out_dim <= 4) stage_matrix(lds + L::wo, WS, 32, 64, a.w_out, 64, 0, a.out_dim, 64);
+        if (!BWD && NTO == 1 && a.out_dim <= 4) stage_matrix(lds + L::wo, WS, 32, 64, a.w_out, 64, 0, a.out_dim, 64);
         else stage_split(lds + L::wo, NTO, 4, a.w_out, 64, 0, a.out_dim, 64, false);
     } else {
         if (BWD) {
@@ -583,7 +532,7 @@ __device__ __forceinline__ void branch_stage(float* lds, const EmdMlpBranch& a) 
 // the usual kernels as they were
 // RC: the head forms h = b_in + W_in xb itself (EmdMlpBranch.xb, a level without HexPlane features) instead of reading a [N,64] tensor
 template <int DEPTH, int NTO, bool L1 = false, bool RC = false>
-__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC((DEPTH == 1 && NTO == 1 && (!L1 || MLP_L1_F11_TWO)) ? MLP_W_F11 : MLP_FWD_WAVES) k_mlp_branch_fwd(EmdMlpBranch a) {
+__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(branch_fwd_waves(DEPTH, NTO)) k_mlp_branch_fwd(EmdMlpBranch a) {
     typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, false)> L;
     extern __shared__ float lds[];
     branch_stage<DEPTH, NTO, false, RC>(lds, a);
@@ -625,7 +574,7 @@ __global__ void __launch_bounds__(MLP_THREADS) MLP_OCC((DEPTH == 1 && NTO == 1 &
             mm<L::SP, 2, 2>(m2, m, lds + L::w2, WS, 0, 2, 4, r, hh, lane);
             m[0] = relu16(m2[0]); m[1] = relu16(m2[1]);
         }
-        if constexpr (MLP_NARROW_OUT && NTO == 1) {
+        if constexpr (NTO == 1) {
             // Round 5: an output layer of at most four features (dx: 3, do: 1) on the VECTOR pipe.  As an MFMA tile it is padded to 32 output rows --
             // 32 of the kernel's 96 MFMAs per 32-row tile for 3 or 1 useful rows -- while the contraction itself is 64 multiply-adds per output and
             // row: a lane holds 32 of its row's 64 activations (the two lane halves hold the two feature halves), so it forms 4 x 32 products
@@ -696,7 +645,7 @@ __global__ void __launch_bounds__(MLP_THREADS) MLP_OCC((DEPTH == 1 && NTO == 1 &
 // paths, the compiler's wait for the PREVIOUS iteration's prefetch has to assume the smaller one, and that wait lands on the loads just issued.
 // GO 0 / 1 therefore take every such decision at compile time (and need g_out; without it the launcher picks GO 2).
 template <int DEPTH, int NTO, bool L1 = false, bool RC = false, int GO = 2, bool CHAIN = false>
-__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(MLP_BWD_WAVES) k_mlp_branch_bwd(EmdMlpBranch a, EmdMlpBranchGrads g) {
+__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(branch_bwd_waves) k_mlp_branch_bwd(EmdMlpBranch a, EmdMlpBranchGrads g) {
     typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, true)> L;
     extern __shared__ float lds[];
     branch_stage<DEPTH, NTO, true, RC>(lds, a);
@@ -908,29 +857,26 @@ __global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(MLP_BWD_WAVES) k_mlp_bran
 // ---------------------------------------------------------------------------------------------------------------------------------
 // trunk: h = b + W[:, col_a : col_a + ka] xa + W[:, col_b : col_b + kb] xb           (ka = 32 KTA, kb <= 8)
 // ---------------------------------------------------------------------------------------------------------------------------------
-// LDS: Wa [64][SA] | Wb [64][12] | b [64] | scratch (backward)
-template <int KTA, int MODE = 0>
+// LDS: Wa (split-bf16 image of [64][32 KTA]; nothing for KTA = 0) | Wb [64][12] | b [64] | scratch (backward)
+// The xa block runs on split bf16 -- the products in both directions and the backward's outer products (profiles/r04_mlp_split_variants.txt) -- , the
+// embedding block and the embedding-only trunk (KTA = 0) on fp32 MFMA.
+template <int KTA>
 struct TrunkLds {
-    static constexpr bool SP = (MODE & 1) != 0 && KTA > 0, SPO = (MODE & 2) != 0 && KTA > 0;
-    static constexpr int SA = 32 * KTA + 4;                 // 4 x odd
     static constexpr int wa = 0;
-    static constexpr int wb = wa + (KTA ? (SP ? split_floats(2, 2 * KTA) : 64 * SA) : 0);
+    static constexpr int wb = wa + split_floats(2, 2 * KTA);
     static constexpr int b = wb + 64 * 12;
     static constexpr int fwd_floats = b + 64;
-    // backward: only the transposed images Wa^T [32 KTA][WS], Wb^T [32][WS] (rows >= kb zero) and one transpose tile per wave
+    // backward: only the transposed images Wa^T (split bf16), Wb^T [32][WS] (rows >= kb zero) and one transpose tile per wave
     static constexpr int wat = 0;
-    static constexpr int wbt = wat + (SP ? split_floats(KTA, 4) : 32 * KTA * WS);
+    static constexpr int wbt = wat + split_floats(KTA, 4);
     static constexpr int scratch = wbt + 32 * WS;
     static constexpr int bwd_floats = scratch + MLP_WAVES * 32 * TS;
 };
 
 template <int KTA>
 __device__ __forceinline__ void trunk_stage(float* lds, const EmdMlpTrunk& a) {
-    typedef TrunkLds<KTA, MLP_SP_TF> L;
-    if (KTA) {
-        if constexpr (L::SP) stage_split(lds + L::wa, 2, 2 * KTA, a.w, a.ld_w, a.col_a, 64, a.ka, false);
-        else stage_matrix(lds + L::wa, L::SA, 64, 32 * KTA, a.w, a.ld_w, a.col_a, 64, a.ka);
-    }
+    typedef TrunkLds<KTA> L;
+    if (KTA) stage_split(lds + L::wa, 2, 2 * KTA, a.w, a.ld_w, a.col_a, 64, a.ka, false);
     stage_matrix(lds + L::wb, 12, 64, 8, a.kb > 0 ? a.w : nullptr, a.ld_w, a.col_b, 64, a.kb);
     stage_vector(lds + L::b, 64, a.b, 64);
     __syncthreads();
@@ -939,9 +885,9 @@ __device__ __forceinline__ void trunk_stage(float* lds, const EmdMlpTrunk& a) {
 // this tile's xa / xb rows (already in registers) -> h
 template <int KTA>
 __device__ __forceinline__ void trunk_forward_tile(const float* lds, int r, int hh, const f32x16 (&xa)[KTA ? KTA : 1], const float (&xb)[4], f32x16 (&h)[2]) {
-    typedef TrunkLds<KTA, MLP_SP_TF> L;
+    typedef TrunkLds<KTA> L;
     h[0] = bias_tile(lds + L::b, 0, hh); h[1] = bias_tile(lds + L::b, 32, hh);
-    if (KTA) mm<L::SP, (KTA ? KTA : 1), 2>(h, xa, lds + L::wa, L::SA, 0, 2, 2 * KTA, r, hh, r + 32 * hh);
+    if constexpr (KTA > 0) layer_fwd_s<KTA, 2>(h, xa, reinterpret_cast<const uint4*>(lds + L::wa), 2, 2 * KTA, 0, r + 32 * hh);
     embed_h(lds + L::wb, lds + L::b, r, hh, xb, h, false);
 }
 
@@ -961,17 +907,9 @@ __device__ __forceinline__ void trunk_load_x_raw(const EmdMlpTrunk& a, size_t ro
         for (int j = 0; j < 4; j++) xb[j] = 0.f;
     }
 }
-template <int KTA, bool STRAIGHT>
-__device__ __forceinline__ void trunk_load_x(const EmdMlpTrunk& a, size_t row, bool ok, int hh, f32x16 (&xa)[KTA ? KTA : 1], float (&xb)[4]) {
-    if (KTA) {
-#pragma unroll
-        for (int t = 0; t < KTA; t++) xa[t] = load_tile<STRAIGHT>(a.xa, a.ka, row, ok, 32 * t, hh, a.ka);
-    }
-    load_xb<STRAIGHT>(a.xb, a.kb, row, ok, hh, xb);
-}
 
 template <int KTA>
-__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(KTA == 0 ? MLP_W_T0 : MLP_FWD_WAVES) k_mlp_trunk_fwd(EmdMlpTrunk a) {
+__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(trunk_fwd_waves(KTA)) k_mlp_trunk_fwd(EmdMlpTrunk a) {
     extern __shared__ float lds[];
     trunk_stage<KTA>(lds, a);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
@@ -1006,13 +944,10 @@ __global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(KTA == 0 ? MLP_W_T0 : MLP
 // past the end read row 0, and dL/dh is zeroed for them where it is used, which zeroes all they could add.  MULTI: more than one dL/dh tensor (a
 // two-hidden-layer head keeps its own): the others are loaded inside the loop, guarded as before.
 template <int KTA, bool MULTI = false>
-__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(KTA == 0 ? MLP_W_TB0 : MLP_BWD_WAVES) k_mlp_trunk_bwd(EmdMlpTrunk a, EmdMlpTrunkGrads g) {
-    typedef TrunkLds<KTA, MLP_SP_TB> L;
+__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(trunk_bwd_waves(KTA)) k_mlp_trunk_bwd(EmdMlpTrunk a, EmdMlpTrunkGrads g) {
+    typedef TrunkLds<KTA> L;
     extern __shared__ float lds[];
-    if (KTA) {
-        if constexpr (L::SP) stage_split(lds + L::wat, KTA, 4, a.w, a.ld_w, a.col_a, 64, a.ka, true);
-        else stage_matrix_t(lds + L::wat, WS, 64, 32 * KTA, a.w, a.ld_w, a.col_a, 64, a.ka);
-    }
+    if (KTA) stage_split(lds + L::wat, KTA, 4, a.w, a.ld_w, a.col_a, 64, a.ka, true);
     stage_matrix_t(lds + L::wbt, WS, 64, 32, a.kb > 0 ? a.w : nullptr, a.ld_w, a.col_b, 64, a.kb);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
@@ -1057,30 +992,21 @@ __global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(KTA == 0 ? MLP_W_TB0 : ML
         }
         const f32x16 gf[2] = {transpose_tile(gh[0], T, r, hh), transpose_tile(gh[1], T, r, hh)};
         db[0] += frag_sum(gf[0]); db[1] += frag_sum(gf[1]);
-        if (KTA) {
+        if constexpr (KTA > 0) {
             if (g.d_xa) {
-                f32x16 gx[KTA ? KTA : 1];
+                f32x16 gx[KTA];
 #pragma unroll
                 for (int t = 0; t < KTA; t++) gx[t] = zero16();
-                mm<L::SP, 2, (KTA ? KTA : 1)>(gx, gh, lds + L::wat, WS, 0, KTA, 4, r, hh, lane);
+                layer_fwd_s<2, KTA>(gx, gh, reinterpret_cast<const uint4*>(lds + L::wat), KTA, 4, 0, lane);
 #pragma unroll
                 for (int t = 0; t < KTA; t++) store_tile(g.d_xa, a.ka, row, ok, 32 * t, hh, gx[t], a.ka);
             }
-            if constexpr (L::SPO) {
-                const Split gs[2] = {split_tile(gf[0]), split_tile(gf[1])};
+            const Split gs[2] = {split_tile(gf[0]), split_tile(gf[1])};
 #pragma unroll
-                for (int t = 0; t < KTA; t++) {
-                    const Split as = split_tile(transpose_tile(xa[t], T, r, hh));
-                    dWa[0][t] = outer_acc_s(dWa[0][t], gs[0], as);
-                    dWa[1][t] = outer_acc_s(dWa[1][t], gs[1], as);
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < KTA; t++) {
-                    const f32x16 af = transpose_tile(xa[t], T, r, hh);
-                    dWa[0][t] = outer_acc(dWa[0][t], gf[0], af);
-                    dWa[1][t] = outer_acc(dWa[1][t], gf[1], af);
-                }
+            for (int t = 0; t < KTA; t++) {
+                const Split as = split_tile(transpose_tile(xa[t], T, r, hh));
+                dWa[0][t] = outer_acc_s(dWa[0][t], gs[0], as);
+                dWa[1][t] = outer_acc_s(dWa[1][t], gs[1], as);
             }
         }
         if (a.kb > 0) {
@@ -1133,16 +1059,13 @@ __global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(KTA == 0 ? MLP_W_TB0 : ML
 // cross-lane add) and keeps dWb[feature][c] += dL/dh[feature] xb[c] and db[feature] += dL/dh[feature] in 32 (kb + 1) per-lane accumulators that
 // are summed over the lanes once, at the end: no MFMA, no transpose, bound by the read of dL/dh.
 // ---------------------------------------------------------------------------------------------------------------------------------
-#ifndef MLP_EMBED_BWD_VALU
-#define MLP_EMBED_BWD_VALU 1
-#endif
 // One wave per SIMD: the 512-entry register file holds the lane's 32 x kb weights (no LDS round trip in the tile loop), the 32 (kb + 1)
 // accumulators and the next two tiles' registers (8 KB per wave and tile; the rotation's register copy waits for the nearer one).  Every load of
 // the loop is unconditional (rows past the end read row 0 and are zeroed by load_tile's product; xb of such a row meets a zero dL/dh): a guarded load
 // makes the compiler wait for ALL outstanding loads -- the prefetches too -- at the join.  MULTI: more than one dL/dh tensor (a two-hidden-layer head
 // keeps its own): the others are added inside the loop.
 template <int KB, bool MULTI>          // KB = kb = 4
-__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(1) k_mlp_embed_bwd(EmdMlpTrunk a, EmdMlpTrunkGrads g) {
+__global__ void __launch_bounds__(MLP_THREADS) MLP_OCC(embed_bwd_waves) k_mlp_embed_bwd(EmdMlpTrunk a, EmdMlpTrunkGrads g) {
     __shared__ float wt[KB][64];                                  // Wb^T: wt[c][feature]
     __shared__ float red[MLP_WAVES][2][32][KB + 1];
     for (int idx = threadIdx.x; idx < KB * 64; idx += MLP_THREADS) {
@@ -1309,37 +1232,36 @@ int mlp_launch(int floats, int num_points, hipStream_t st, Args... args) {
 
 }  // namespace
 
+// the launchers derive the LDS floats, the recomputed-h addend and the workgroups per CU from the kernel's template arguments
+template <int DEPTH, int NTO, bool L1, bool RC>
+int launch_branch_fwd(const EmdMlpBranch* a, hipStream_t st) {
+    typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, false)> L;
+    return mlp_launch<k_mlp_branch_fwd<DEPTH, NTO, L1, RC>, branch_fwd_waves(DEPTH, NTO)>(L::fwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a);
+}
+
 extern "C" int emd_mlp_branch_forward(const EmdMlpBranch* a, void* hip_stream) {
     int rc = check_branch(a, "mlp_branch_forward");
     if (rc || a->num_points == 0) return rc;
     if (!a->out) { emd_set_error("mlp_branch_forward: null output"); return EMD_ERR_INVALID; }
     hipStream_t st = (hipStream_t)hip_stream;
     const int nto = a->out_dim > 32 ? 2 : 1;
-    if (a->xb) {
-        typedef BranchLds<1, 1, branch_mode(1, 1, false)> L1_; typedef BranchLds<1, 2, branch_mode(1, 2, false)> L2_;
-        if (a->l1_sum) {
-            if (nto == 1) return mlp_launch<k_mlp_branch_fwd<1, 1, true, true>, (MLP_L1_F11_TWO ? MLP_W_F11 : MLP_FWD_WAVES)>(L1_::fwd_floats + L1_::rc_floats, a->num_points, st, *a);
-            return mlp_launch<k_mlp_branch_fwd<1, 2, true, true>, MLP_FWD_WAVES>(L2_::fwd_floats + L2_::rc_floats, a->num_points, st, *a);
-        }
-        if (nto == 1) return mlp_launch<k_mlp_branch_fwd<1, 1, false, true>, MLP_W_F11>(L1_::fwd_floats + L1_::rc_floats, a->num_points, st, *a);
-        return mlp_launch<k_mlp_branch_fwd<1, 2, false, true>, MLP_FWD_WAVES>(L2_::fwd_floats + L2_::rc_floats, a->num_points, st, *a);
+    const bool l1 = a->l1_sum != nullptr;
+    if (a->xb) {          // recomputed h: one hidden layer (check_branch)
+        if (nto == 1) return l1 ? launch_branch_fwd<1, 1, true, true>(a, st) : launch_branch_fwd<1, 1, false, true>(a, st);
+        return l1 ? launch_branch_fwd<1, 2, true, true>(a, st) : launch_branch_fwd<1, 2, false, true>(a, st);
     }
-    if (a->l1_sum) {
-        if (a->depth == 1 && nto == 1) return mlp_launch<k_mlp_branch_fwd<1, 1, true>, (MLP_L1_F11_TWO ? MLP_W_F11 : MLP_FWD_WAVES)>(BranchLds<1, 1, branch_mode(1, 1, false)>::fwd_floats, a->num_points, st, *a);
-        if (a->depth == 1) return mlp_launch<k_mlp_branch_fwd<1, 2, true>, MLP_FWD_WAVES>(BranchLds<1, 2, branch_mode(1, 2, false)>::fwd_floats, a->num_points, st, *a);
-        if (nto == 1) return mlp_launch<k_mlp_branch_fwd<2, 1, true>, MLP_FWD_WAVES>(BranchLds<2, 1, branch_mode(2, 1, false)>::fwd_floats, a->num_points, st, *a);
-        return mlp_launch<k_mlp_branch_fwd<2, 2, true>, MLP_FWD_WAVES>(BranchLds<2, 2, branch_mode(2, 2, false)>::fwd_floats, a->num_points, st, *a);
+    if (a->depth == 1) {
+        if (nto == 1) return l1 ? launch_branch_fwd<1, 1, true, false>(a, st) : launch_branch_fwd<1, 1, false, false>(a, st);
+        return l1 ? launch_branch_fwd<1, 2, true, false>(a, st) : launch_branch_fwd<1, 2, false, false>(a, st);
     }
-    if (a->depth == 1 && nto == 1) return mlp_launch<k_mlp_branch_fwd<1, 1>, MLP_W_F11>(BranchLds<1, 1, branch_mode(1, 1, false)>::fwd_floats, a->num_points, st, *a);
-    if (a->depth == 1) return mlp_launch<k_mlp_branch_fwd<1, 2>, MLP_FWD_WAVES>(BranchLds<1, 2, branch_mode(1, 2, false)>::fwd_floats, a->num_points, st, *a);
-    if (nto == 1) return mlp_launch<k_mlp_branch_fwd<2, 1>, MLP_FWD_WAVES>(BranchLds<2, 1, branch_mode(2, 1, false)>::fwd_floats, a->num_points, st, *a);
-    return mlp_launch<k_mlp_branch_fwd<2, 2>, MLP_FWD_WAVES>(BranchLds<2, 2, branch_mode(2, 2, false)>::fwd_floats, a->num_points, st, *a);
+    if (nto == 1) return l1 ? launch_branch_fwd<2, 1, true, false>(a, st) : launch_branch_fwd<2, 1, false, false>(a, st);
+    return l1 ? launch_branch_fwd<2, 2, true, false>(a, st) : launch_branch_fwd<2, 2, false, false>(a, st);
 }
 
 template <int DEPTH, int NTO, bool L1, bool RC, int GO, bool CHAIN = false>
 int launch_branch_bwd(const EmdMlpBranch* a, const EmdMlpBranchGrads* g, hipStream_t st) {
     typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, true)> L;
-    return mlp_launch<k_mlp_branch_bwd<DEPTH, NTO, L1, RC, GO, CHAIN>, MLP_BWD_WAVES>(L::bwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a, *g);
+    return mlp_launch<k_mlp_branch_bwd<DEPTH, NTO, L1, RC, GO, CHAIN>, branch_bwd_waves>(L::bwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a, *g);
 }
 // one-hidden-layer heads: by output tiles, regulariser, recomputed h, the form dL/dout is loaded in and the chained dL/dh (k_mlp_branch_bwd's GO / CHAIN)
 template <int NTO, bool L1, bool RC>
@@ -1387,23 +1309,28 @@ extern "C" int emd_mlp_branch_backward(const EmdMlpBranch* a, const EmdMlpBranch
     return nto == 1 ? launch_branch_bwd<2, 1, false, false, 2>(a, g, st) : launch_branch_bwd<2, 2, false, false, 2>(a, g, st);
 }
 
+template <int KTA>
+int launch_trunk_fwd(const EmdMlpTrunk* a, hipStream_t st) {
+    return mlp_launch<k_mlp_trunk_fwd<KTA>, trunk_fwd_waves(KTA)>(TrunkLds<KTA>::fwd_floats, a->num_points, st, *a);
+}
+
 extern "C" int emd_mlp_trunk_forward(const EmdMlpTrunk* a, void* hip_stream) {
     int rc = check_trunk(a, "mlp_trunk_forward");
     if (rc || a->num_points == 0) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     switch ((a->ka + 31) / 32) {            // input tiles of 32 columns (the last one zero-padded)
-        case 0: return mlp_launch<k_mlp_trunk_fwd<0>, MLP_W_T0>(TrunkLds<0, MLP_SP_TF>::fwd_floats, a->num_points, st, *a);
-        case 1: return mlp_launch<k_mlp_trunk_fwd<1>, MLP_FWD_WAVES>(TrunkLds<1, MLP_SP_TF>::fwd_floats, a->num_points, st, *a);
-        case 2: return mlp_launch<k_mlp_trunk_fwd<2>, MLP_FWD_WAVES>(TrunkLds<2, MLP_SP_TF>::fwd_floats, a->num_points, st, *a);
-        case 3: return mlp_launch<k_mlp_trunk_fwd<3>, MLP_FWD_WAVES>(TrunkLds<3, MLP_SP_TF>::fwd_floats, a->num_points, st, *a);
-        default: return mlp_launch<k_mlp_trunk_fwd<4>, MLP_FWD_WAVES>(TrunkLds<4, MLP_SP_TF>::fwd_floats, a->num_points, st, *a);
+        case 0: return launch_trunk_fwd<0>(a, st);
+        case 1: return launch_trunk_fwd<1>(a, st);
+        case 2: return launch_trunk_fwd<2>(a, st);
+        case 3: return launch_trunk_fwd<3>(a, st);
+        default: return launch_trunk_fwd<4>(a, st);
     }
 }
 
-template <int KTA, int PER_CU>
+template <int KTA>
 int launch_trunk_bwd(const EmdMlpTrunk* a, const EmdMlpTrunkGrads* g, hipStream_t st) {
-    if (g->num_gh == 1) return mlp_launch<k_mlp_trunk_bwd<KTA, false>, PER_CU>(TrunkLds<KTA, MLP_SP_TB>::bwd_floats, a->num_points, st, *a, *g);
-    return mlp_launch<k_mlp_trunk_bwd<KTA, true>, PER_CU>(TrunkLds<KTA, MLP_SP_TB>::bwd_floats, a->num_points, st, *a, *g);
+    if (g->num_gh == 1) return mlp_launch<k_mlp_trunk_bwd<KTA, false>, trunk_bwd_waves(KTA)>(TrunkLds<KTA>::bwd_floats, a->num_points, st, *a, *g);
+    return mlp_launch<k_mlp_trunk_bwd<KTA, true>, trunk_bwd_waves(KTA)>(TrunkLds<KTA>::bwd_floats, a->num_points, st, *a, *g);
 }
 
 extern "C" int emd_mlp_trunk_backward(const EmdMlpTrunk* a, const EmdMlpTrunkGrads* g, void* hip_stream) {
@@ -1416,16 +1343,16 @@ extern "C" int emd_mlp_trunk_backward(const EmdMlpTrunk* a, const EmdMlpTrunkGra
     hipStream_t st = (hipStream_t)hip_stream;
     switch ((a->ka + 31) / 32) {
         case 0:
-            if (MLP_EMBED_BWD_VALU && a->kb == 4 && !((uintptr_t)a->xb & 15) && !((uintptr_t)g->d_xb & 15)) {     // (the reference's embedding width; static LDS)
-                if (g->num_gh == 1) hipLaunchKernelGGL((k_mlp_embed_bwd<4, false>), dim3(mlp_grid(a->num_points, 1)), dim3(MLP_THREADS), 0, st, *a, *g);
-                else hipLaunchKernelGGL((k_mlp_embed_bwd<4, true>), dim3(mlp_grid(a->num_points, 1)), dim3(MLP_THREADS), 0, st, *a, *g);
+            if (a->kb == 4 && !((uintptr_t)a->xb & 15) && !((uintptr_t)g->d_xb & 15)) {     // (the reference's embedding width; static LDS)
+                if (g->num_gh == 1) hipLaunchKernelGGL((k_mlp_embed_bwd<4, false>), dim3(mlp_grid(a->num_points, embed_bwd_waves)), dim3(MLP_THREADS), 0, st, *a, *g);
+                else hipLaunchKernelGGL((k_mlp_embed_bwd<4, true>), dim3(mlp_grid(a->num_points, embed_bwd_waves)), dim3(MLP_THREADS), 0, st, *a, *g);
                 EMD_LAUNCH_CHECK();
                 return EMD_OK;
             }
-            return launch_trunk_bwd<0, MLP_W_TB0>(a, g, st);
-        case 1: return launch_trunk_bwd<1, MLP_BWD_WAVES>(a, g, st);
-        case 2: return launch_trunk_bwd<2, MLP_BWD_WAVES>(a, g, st);
-        case 3: return launch_trunk_bwd<3, MLP_BWD_WAVES>(a, g, st);
-        default: return launch_trunk_bwd<4, MLP_BWD_WAVES>(a, g, st);
+            return launch_trunk_bwd<0>(a, g, st);
+        case 1: return launch_trunk_bwd<1>(a, g, st);
+        case 2: return launch_trunk_bwd<2>(a, g, st);
+        case 3: return launch_trunk_bwd<3>(a, g, st);
+        default: return launch_trunk_bwd<4>(a, g, st);
     }
 }

@@ -1,29 +1,31 @@
 #!/usr/bin/env python3
-"""Machine-code identity of the projection unit across its split into preprocess.hip + standalone_ops.hip.
+"""Machine-code identity of compilation units between two trees: a refactor that must not change a kernel proves it here.
 
     python profiles/compare_kernel_isa.py OLD_TREE NEW_TREE > profiles/preprocess_split_isa.txt      # CPU only: hipcc -S cross-compiles gfx950
+    python profiles/compare_kernel_isa.py OLD_TREE NEW_TREE mlp hexplane binning > profiles/switches_retired_isa.txt
 
-OLD_TREE is a checkout of the commit before the split (`git worktree add` / `git archive`), NEW_TREE a checkout at or after it.  OLD_TREE's
-emd_amd/csrc/preprocess.hip and NEW_TREE's preprocess.hip + standalone_ops.hip are compiled to assembly the way profiles/make_isa_mix.py does
-(hipcc -S --cuda-device-only), with the flags NEW_TREE's Makefile gives for the unit (`make print-flags-<unit>`; both units carry
--ffp-contract=off -fno-slp-vectorize, as preprocess.hip did before).  For every `.amdhsa_kernel` symbol the instruction text of the function and
-its `.amdhsa_*` descriptor block are compared after exactly these normalisations:
+OLD_TREE is a checkout of the commit before the change (`git worktree add` / `git archive`), NEW_TREE a checkout at or after it.  Every further
+argument names a unit of emd_amd/csrc (`mlp`: the old mlp.hip against the new one) or a split `OLD=NEW1+NEW2`; with none it is
+`preprocess=preprocess+standalone_ops`, the split of the projection unit.  The units are compiled to assembly the way profiles/make_isa_mix.py
+does (hipcc -S --cuda-device-only), both sides with the flags NEW_TREE's Makefile gives for the new unit (`make print-flags-<unit>`; the two
+halves of the preprocess split both carry -ffp-contract=off -fno-slp-vectorize, as preprocess.hip did before).  For every `.amdhsa_kernel`
+symbol the instruction text of the function and its `.amdhsa_*` descriptor block are compared after exactly these normalisations:
 
     * the function index inside local labels (.LBB<n>_<m> -> .LBB_<m>, .Lfunc_begin<n> / .Lfunc_end<n> likewise): a kernel's position in its unit;
     * the __hip_cuid_* symbol (a hash of the compilation);
     * .file / .loc / .ident lines, comments and blank lines.
 
-Passes (exit status 0) when the kernel symbols of the two new units together are exactly those of the old unit, no symbol is in both, and
-every kernel is identical.  One line per kernel: name, VGPRs, SGPRs, LDS bytes, scratch bytes, verdict."""
+Passes (exit status 0) when, for every argument, the kernel symbols of the new units together are exactly those of the old unit, no symbol is in
+two of them (nor, unless it has internal linkage, in the units of two arguments), and every kernel is identical.  One line per kernel: name, VGPRs, SGPRs, LDS bytes, scratch bytes, verdict."""
 import difflib
 import os
 import re
 import subprocess
 import sys
 import tempfile
+import textwrap
 
-OLD_UNITS = ("preprocess",)
-NEW_UNITS = ("preprocess", "standalone_ops")
+DEFAULT_UNITS = ("preprocess=preprocess+standalone_ops",)
 
 
 def unit_flags(tree, unit):
@@ -87,43 +89,54 @@ def demangle(syms):
 
 
 def main():
-    if len(sys.argv) != 3:
+    if len(sys.argv) < 3:
         sys.exit(__doc__)
     old_tree, new_tree = (os.path.abspath(p) for p in sys.argv[1:3])
-    flags = {u: unit_flags(new_tree, u) for u in NEW_UNITS}
-    old, new, where = {}, {}, {}
-    for u in OLD_UNITS:
-        old.update(kernels_of(assemble(old_tree, u, flags[u])))
-    ok = True
-    for u in NEW_UNITS:
-        ks = kernels_of(assemble(new_tree, u, flags[u]))
-        for s in ks:
-            if s in new:
-                print(f"# FAIL: {s} is in {where[s]}.hip and in {u}.hip")
-                ok = False
-            where[s] = u
-        new.update(ks)
-    names = demangle(sorted(set(old) | set(new)))
-    print("# profiles/compare_kernel_isa.py: every kernel of the old emd_amd/csrc/preprocess.hip against the same kernel of the new preprocess.hip /")
-    print("# standalone_ops.hip; `hipcc -S --cuda-device-only`, gfx950, flags: " + " ".join(flags["preprocess"]))
+    # [(old unit, new units)]
+    groups = [(a.split("=")[0], tuple(a.split("=")[-1].split("+"))) for a in (sys.argv[3:] or DEFAULT_UNITS)]
+    new_units = [u for _, us in groups for u in us]
+    flags = {u: unit_flags(new_tree, u) for u in new_units}
+    hips = lambda units: " / ".join(u + ".hip" for u in units)
+    flag_sets = sorted({" ".join(f) for f in flags.values()})
+    flag_text = flag_sets[0] if len(flag_sets) == 1 else "; ".join(f"{u}.hip: {' '.join(flags[u])}" for u in new_units)
+    print(textwrap.fill(f"profiles/compare_kernel_isa.py: every kernel of the old emd_amd/csrc/{hips(o for o, _ in groups)} against the same kernel of the new "
+                        f"{hips(new_units)}; `hipcc -S --cuda-device-only`, gfx950, flags:", 150, initial_indent="# ", subsequent_indent="# ") + " " + flag_text)
     print("# compared: the instruction text of the function and its .amdhsa_* descriptor, modulo local-label function indices, __hip_cuid_*, comments")
     print(f"# {'kernel':28s} {'unit':15s} {'VGPRs':>5s} {'SGPRs':>5s} {'LDS B':>6s} {'scratch B':>9s}  verdict")
-    for s in sorted(set(old) | set(new), key=lambda s: (where.get(s, "~"), names[s], s)):
-        if s not in new or s not in old:
-            print(f"{names[s]:30s} {where.get(s, '-'):15s} {'':>5s} {'':>5s} {'':>6s} {'':>9s}  {'MISSING in the new units' if s not in new else 'NOT in the old unit'}  ({s})")
-            ok = False
-            continue
-        o, n = old[s], new[s]
-        same = o["body"] == n["body"] and o["desc"] == n["desc"]
-        ok &= same
-        anon = "_GLOBAL__N_" in s
-        print(f"{names[s]:30s} {where[s]:15s} {n['vgpr']:5d} {n['sgpr']:5d} {n['lds']:6d} {n['scratch']:9d}  {'identical' if same else 'DIFFERENT'}"
-              f"{'' if anon else '  (outside the anonymous namespace)'}")
-        if not same:
-            for what in ("desc", "body"):
-                for d in list(difflib.unified_diff(o[what], n[what], "old", "new", lineterm="", n=1))[:40]:
-                    print("#     " + d)
-    print(f"# {len(old)} kernels in the old unit, {len(new)} in the new units ({', '.join(f'{u}.hip {sum(1 for s in new if where[s] == u)}' for u in NEW_UNITS)}): "
+    ok = True
+    n_old, n_new, seen = {}, {}, {}          # seen: symbol -> new unit over ALL arguments (anonymous-namespace symbols are per unit: kept per argument only)
+    for old_unit, units in groups:
+        old, new, where = kernels_of(assemble(old_tree, old_unit, flags[units[0]])), {}, {}
+        for u in units:
+            ks = kernels_of(assemble(new_tree, u, flags[u]))
+            for s in ks:
+                if s in where or s in seen:
+                    print(f"# FAIL: {s} is in {where.get(s) or seen[s]}.hip and in {u}.hip")
+                    ok = False
+                where[s] = u
+                if "_GLOBAL__N_" not in s:
+                    seen[s] = u
+            new.update(ks)
+            n_new[u] = len(ks)
+        n_old[old_unit] = len(old)
+        names = demangle(sorted(set(old) | set(new)))
+        for s in sorted(set(old) | set(new), key=lambda s: (where.get(s, "~"), names[s], s)):
+            if s not in new or s not in old:
+                print(f"{names[s]:30s} {where.get(s, '-'):15s} {'':>5s} {'':>5s} {'':>6s} {'':>9s}  {'MISSING in the new units' if s not in new else 'NOT in the old unit'}  ({s})")
+                ok = False
+                continue
+            o, n = old[s], new[s]
+            same = o["body"] == n["body"] and o["desc"] == n["desc"]
+            ok &= same
+            anon = "_GLOBAL__N_" in s
+            print(f"{names[s]:30s} {where[s]:15s} {n['vgpr']:5d} {n['sgpr']:5d} {n['lds']:6d} {n['scratch']:9d}  {'identical' if same else 'DIFFERENT'}"
+                  f"{'' if anon else '  (outside the anonymous namespace)'}")
+            if not same:
+                for what in ("desc", "body"):
+                    for d in list(difflib.unified_diff(o[what], n[what], "old", "new", lineterm="", n=1))[:40]:
+                        print("#     " + d)
+    per = lambda counts: ", ".join(f"{u}.hip {k}" for u, k in counts.items())
+    print(f"# {sum(n_old.values())} kernels in the old unit{'s (' + per(n_old) + ')' if len(n_old) > 1 else ''}, {sum(n_new.values())} in the new units ({per(n_new)}): "
           + ("ALL IDENTICAL" if ok else "FAILED"))
     sys.exit(0 if ok else 1)
 
