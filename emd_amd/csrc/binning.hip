@@ -19,10 +19,11 @@
 // (tile id, depth bits of the Gaussian) for the parity tests.  Bytes through the radix passes on the bench scene
 // (N = 2 M, V = 1.06 M, D = 4.6 M): 6 x 24 B x 4.6 M = 670 MB upstream, 4 N + 8 V + 2 x 16 V + 2 x 16 D = 200 MB here.
 //
-// Launches of the stage (19): per depth pass histogram -> digit scan -> scatter (9); the binning records gathered into depth order with
+// The sort itself -- the per-pass kernels and the pass loop -- is radix_sort.hip; this unit holds the stage's own six kernels.
+// Launches of the stage (19): per depth pass histogram -> digit scan -> scatter (9, radix_sort.hip); the binning records gathered into depth order with
 // the pairs every 256 of them emit (1); the duplicate kernel, which scans those block sums itself (every workgroup, 31 KB from L2) and
 // publishes D / overflow / V -- the single-workgroup scan kernel of rounds 1-3 is gone (1); two tile passes, the first one's histogram
-// built by the duplicate kernel (5); tile ranges; the dispatch order of the render kernels.
+// built by the duplicate kernel (5, radix_sort.hip); tile ranges; the dispatch order of the render kernels.
 //
 // Design for gfx950:
 //   - the duplicate count D stays on the device (EmdStatus.num_rendered); every kernel here is launched on the
@@ -30,35 +31,14 @@
 //   - duplication is balanced over output slots, not Gaussians: a 256-thread block scans the tile counts of its
 //     256 Gaussians (DPP wave scan + LDS), then lane e writes slot e, reading its Gaussian from a max-scan of head
 //     marks in LDS -- consecutive lanes write consecutive pairs (coalesced 4 B + 4 B stores) regardless of footprint size.
-//   - ranking inside a radix block is wave-ballot based (8 ballots per key give the set of lanes with the same digit;
-//     no LDS atomics in the ranking loop), which keeps every pass stable.
 #include <string.h>
 
 #include "common.h"
 #include "device_utils.h"
+#include "radix_sort.h"
 #include "footprint.h"       // (EMD_ID_BITS: the quadrant mask rides above the 28-bit Gaussian id of a list word)
 
-// EMD_BIN_CARRY (round 5, measured and NOT kept; the code stays as the record of the experiment): the 8-byte binning records travel through the
-// depth passes as a second value instead of being gathered in depth order afterwards.  The gather kernel shrinks from 22 to 6 us, every one
-// of the three depth scatters grows by 7 us (16 KB more LDS per block, 8 more bytes per element each way): 798 against 803 it/s on one box.
-#ifndef EMD_BIN_CARRY
-#define EMD_BIN_CARRY 0
-#endif
-
 namespace {
-
-// number of elements of a radix pass: a launch-time constant (first pass of the Gaussian depth sort), or a device-side count
-// (visible Gaussians after that pass; the duplicate count of the tile passes) that reads as 0 while the overflow word is set
-struct SortN { const uint32_t* count; const uint32_t* overflow; uint32_t fixed; };
-__device__ __forceinline__ uint32_t sort_n(const SortN& c) {
-    return c.count ? ((c.overflow && *c.overflow) ? 0u : *c.count) : c.fixed;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// scan geometry of the single-workgroup scans below: 1024 elements per trip
-// ---------------------------------------------------------------------------------------------------
-#define SCAN_ITEMS 4
-#define SCAN_TILE (EMD_BLOCK * SCAN_ITEMS)
 
 #define DUP_SLOTS EMD_SORT_TILE
 
@@ -68,10 +48,9 @@ __device__ __forceinline__ uint32_t sort_n(const SortN& c) {
 // (Round 4, measured and dropped: this gather inside the last depth pass's scatter kernel, with the block sums as one float... integer
 //  atomic per (wave, output block) -- 117 k single-lane atomic instructions at ~117 clocks each on the CU's memory path made that pass
 //  78 us instead of 18; as its own launch with 4900 independent workgroups the gather takes 20.)
-// CARRIED (round 5): the records arrive in depth order already -- the depth passes carry them as a second value (the first pass reads them in
-// index order, coalesced) -- so the gather (150 MB of fabric traffic for 8.5 MB of records, 22 us) is gone and this kernel only adds up the
-// pairs of every block of 256 and clears the tile ranges.
-template <bool CARRIED>
+// (Round 5, measured and dropped: the records carried through the depth passes as a second value, so that they arrive here in depth order.
+//  This gather (150 MB of fabric traffic for 8.5 MB of records) shrank from 22 to 6 us, every one of the three depth scatters grew by 7 us
+//  (16 KB more LDS per block, 8 more bytes per element each way): 798 against 803 it/s.  docs/history/DESIGN_rounds_1-5.md has the record.)
 __global__ void __launch_bounds__(EMD_BLOCK) k_sorted_counts(int N, const uint32_t* __restrict__ num_sorted,
                                                              const uint32_t* __restrict__ perm,
                                                              const uint2* __restrict__ binrec,
@@ -81,8 +60,8 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_sorted_counts(int N, const uint32
     __shared__ uint32_t s_scan[4];
     const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
     uint2 br = make_uint2(0u, 0u);
-    if (i < N && (uint32_t)i < *num_sorted) br = CARRIED ? bin_s[i] : binrec[perm[i]];         // the depth sort kept the V visible Gaussians only
-    if (!CARRIED && i < N) bin_s[i] = br;
+    if (i < N && (uint32_t)i < *num_sorted) br = binrec[perm[i]];         // the depth sort kept the V visible Gaussians only
+    if (i < N) bin_s[i] = br;
     // empty tiles keep the range (0, 0): cleared here instead of by a separate memset launch
     for (uint32_t r = (uint32_t)i; r < n_ranges; r += gridDim.x * EMD_BLOCK) ranges[r] = 0u;
     uint32_t total;
@@ -255,219 +234,6 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_duplicate(int N, int gx, const ui
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K4 radix pass on 32-bit keys with 32-bit values: (a) block histograms, (b) scan over [bin][block], (c) stable scatter.
-// BITS = 8 (256 digits: the tile passes, the wide depth sort) or 9 (512 digits: the usual three-pass depth sort).
-// `offset` is subtracted from every key before the digit is taken (depth bits relative to the near plane's).
-// FIRST (first pass of the depth sort): the value of element idx is idx itself, culled Gaussians (key 0xFFFFFFFF) are skipped --
-// they take part in neither the counts nor the scatter, so this stable pass also compacts the N Gaussians to the V visible
-// ones in index order, and block 0 publishes V for the later passes; keys that do not fit `range_bits` raise bit 1 of the
-// overflow word (the host then switches that camera to the wide sort, like a capacity overflow).
-// ---------------------------------------------------------------------------------------------------
-template <int BITS, bool FIRST>
-__global__ void __launch_bounds__(EMD_BLOCK) k_radix_hist(const uint32_t* __restrict__ keys, SortN cnt, int shift, uint32_t mask, uint32_t offset,
-                                                          uint32_t nblocks_cap, uint32_t* __restrict__ hist, int range_bits,
-                                                          uint32_t* __restrict__ overflow_word) {
-    constexpr int BINS = 1 << BITS, PER = BINS / EMD_BLOCK;
-    __shared__ uint32_t s_h[BINS];
-    const uint32_t D = sort_n(cnt);
-    const uint32_t nblocks = (D + EMD_SORT_TILE - 1) / EMD_SORT_TILE;
-#pragma unroll
-    for (int k = 0; k < PER; k++) s_h[threadIdx.x + k * EMD_BLOCK] = 0;
-    __syncthreads();
-    if (blockIdx.x < nblocks) {
-        const size_t base = (size_t)blockIdx.x * EMD_SORT_TILE;
-        bool wide = false;
-        // all of the thread's keys first, unconditionally (an index past the end reads the last key and is not counted): with the load inside the
-        // guard the compiler waited for every key before asking for the next -- eight trips to memory one after the other per workgroup
-        uint32_t kv[EMD_SORT_ITEMS];
-#pragma unroll
-        for (int k = 0; k < EMD_SORT_ITEMS; k++) {
-            const size_t idx = base + (size_t)k * EMD_BLOCK + threadIdx.x;
-            kv[k] = keys[idx < D ? idx : (size_t)D - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < EMD_SORT_ITEMS; k++) {
-            size_t idx = base + (size_t)k * EMD_BLOCK + threadIdx.x;
-            if (idx < D) {
-                const uint32_t key = kv[k];
-                if (FIRST && key == 0xFFFFFFFFu) continue;
-                const uint32_t rel = key - offset;
-                if (FIRST && range_bits < 32 && (rel >> range_bits)) wide = true;
-                atomicAdd(&s_h[(rel >> shift) & mask], 1u);
-            }
-        }
-        if (FIRST && wide) atomicOr(overflow_word, 2u);
-    }
-    __syncthreads();
-    // bin-major layout over the *capacity* block count so the scan length is launch-time constant
-#pragma unroll
-    for (int k = 0; k < PER; k++) hist[(size_t)(threadIdx.x + k * EMD_BLOCK) * nblocks_cap + blockIdx.x] = s_h[threadIdx.x + k * EMD_BLOCK];
-}
-
-// One workgroup per digit: inclusive scan of that digit's per-block counts (row `bin` of the bin-major table) in place.
-// Replaces three launch-bound generic scan launches per pass; the cross-digit offsets are formed in the scatter kernel.
-__global__ void __launch_bounds__(EMD_BLOCK) k_radix_scan_bins(uint32_t* __restrict__ hist, uint32_t nblocks_cap) {
-    __shared__ uint32_t s[4];
-    uint32_t* row = hist + (size_t)blockIdx.x * nblocks_cap;
-    uint32_t carry = 0;
-    // the counts of the NEXT tile travel while this one is scanned (two barriers and the stores): unconditional loads from clamped positions, masked
-    // where they are used -- a row of a few thousand counts was load -> scan -> store, one round trip per 1024 counts in a 5 us kernel
-    uint32_t nv[SCAN_ITEMS];
-    const uint32_t last = nblocks_cap ? nblocks_cap - 1 : 0u;
-    auto request = [&](uint32_t base) {
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; k++) nv[k] = row[min(base + threadIdx.x * SCAN_ITEMS + k, last)];
-    };
-    request(0);
-    for (uint32_t base = 0; base < nblocks_cap; base += SCAN_TILE) {
-        const uint32_t i0 = base + threadIdx.x * SCAN_ITEMS;
-        uint32_t v[SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; k++) { v[k] = (i0 + k < nblocks_cap) ? nv[k] : 0u; sum += v[k]; }
-        request(base + SCAN_TILE);                    // (past the end: the row's last count again, unused)
-        uint32_t total;
-        const uint32_t inc = block_scan_add_u32(sum, s, &total);
-        uint32_t run = carry + inc - sum;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; k++) { run += v[k]; if (i0 + k < nblocks_cap) row[i0 + k] = run; }
-        carry += total;
-    }
-}
-
-// CARRY: a second, 8-byte value travels with every pair (the binning record of the Gaussian; FIRST: read at the element's own index).
-template <int BITS, bool FIRST, bool CARRY = false>
-__global__ void __launch_bounds__(EMD_BLOCK) k_radix_scatter(const uint32_t* __restrict__ keys_in,
-                                                             const uint32_t* __restrict__ vals_in,
-                                                             uint32_t* __restrict__ keys_out,
-                                                             uint32_t* __restrict__ vals_out, SortN cnt, int shift,
-                                                             uint32_t mask, uint32_t offset, uint32_t nblocks_cap,
-                                                             const uint32_t* __restrict__ hist_inc, uint32_t* __restrict__ count_out,
-                                                             const uint2* __restrict__ carry_in, uint2* __restrict__ carry_out) {
-    // wave w of the block owns the contiguous slice [w*512, (w+1)*512) of the block's 2048 keys and walks it in
-    // 8 rounds of 64 consecutive keys: order inside the block = (wave, round, lane) = memory order => stable.
-    constexpr int BINS = 1 << BITS, PER = BINS / EMD_BLOCK;
-    __shared__ uint32_t s_cnt[4][BINS];   // running per-wave digit counts, then per-wave bases
-    __shared__ uint32_t s_gbase[BINS];
-    __shared__ uint32_t s_keys[EMD_SORT_TILE];
-    __shared__ uint32_t s_vals[EMD_SORT_TILE];
-    __shared__ uint2 s_carry[CARRY ? EMD_SORT_TILE : 1];
-    __shared__ uint32_t s_scan[4];
-    const uint32_t D = sort_n(cnt);
-    const uint32_t nblocks = (D + EMD_SORT_TILE - 1) / EMD_SORT_TILE;
-    if (blockIdx.x >= nblocks) return;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int j = 0; j < PER; j++) s_cnt[k][threadIdx.x + j * EMD_BLOCK] = 0;
-    __syncthreads();
-    const size_t wbase = (size_t)blockIdx.x * EMD_SORT_TILE + (size_t)wave * (EMD_SORT_TILE / 4);
-    uint32_t key[EMD_SORT_ITEMS];
-    uint32_t val[EMD_SORT_ITEMS];
-    uint32_t rank[EMD_SORT_ITEMS];
-    uint2 car[CARRY ? EMD_SORT_ITEMS : 1];
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    // all loads of the block first (keys, values, the digit rows of the scanned histogram further down): one round trip, not three
-#pragma unroll
-    for (int k = 0; k < EMD_SORT_ITEMS; k++) {
-        const size_t idx = wbase + (size_t)k * 64 + lane;
-        key[k] = idx < D ? keys_in[idx] : 0xFFFFFFFFu;
-        val[k] = FIRST ? (uint32_t)idx : (idx < D ? vals_in[idx] : 0u);
-        if (CARRY) car[k] = idx < D ? carry_in[idx] : make_uint2(0u, 0u);
-    }
-    uint32_t h_before[PER], h_tot[PER];
-#pragma unroll
-    for (int j = 0; j < PER; j++) {
-        const uint32_t* row = hist_inc + (size_t)(threadIdx.x * PER + j) * nblocks_cap;       // a thread owns PER consecutive digits
-        h_before[j] = blockIdx.x ? row[blockIdx.x - 1] : 0u;
-        h_tot[j] = row[nblocks_cap - 1];
-    }
-#pragma unroll
-    for (int k = 0; k < EMD_SORT_ITEMS; k++) {
-        const size_t idx = wbase + (size_t)k * 64 + lane;
-        bool valid = idx < D;
-        if (FIRST) valid = valid && key[k] != 0xFFFFFFFFu;          // culled Gaussian: dropped here
-        const uint32_t digit = ((key[k] - offset) >> shift) & mask;
-        // lanes with the same digit (invalid lanes form their own class and are ignored)
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < BITS; b++) {
-            const unsigned long long bal = __ballot((digit >> b) & 1u);
-            same &= ((digit >> b) & 1u) ? bal : ~bal;
-        }
-        const uint32_t before = (uint32_t)__popcll(same & lt_mask);
-        const uint32_t prev = s_cnt[wave][digit];          // count from earlier rounds of this wave
-        rank[k] = valid ? prev + before : 0xFFFFFFFFu;
-        // the highest lane of each class publishes the new count (wave-private row: no atomics, no race)
-        const bool leader = valid && ((same >> lane) >> 1) == 0ull;
-        __builtin_amdgcn_wave_barrier();
-        if (leader) s_cnt[wave][digit] = prev + (uint32_t)__popcll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    // per-wave bases in the block's digit-sorted order + the block's global base for every digit
-    {
-        uint32_t c[PER][4], csum[PER], dtot[PER], before[PER];
-        uint32_t csum_t = 0, dtot_t = 0;
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const uint32_t d = threadIdx.x * PER + j;       // a thread owns PER consecutive digits
-#pragma unroll
-            for (int w = 0; w < 4; w++) c[j][w] = s_cnt[w][d];
-            csum[j] = c[j][0] + c[j][1] + c[j][2] + c[j][3];
-            // keys of digit d in earlier blocks (row-wise inclusive scan) + all keys of smaller digits (row totals)
-            before[j] = h_before[j];
-            dtot[j] = h_tot[j];
-            csum_t += csum[j]; dtot_t += dtot[j];
-        }
-        uint32_t total;
-        uint32_t g = block_scan_add_u32(dtot_t, s_scan, &total) - dtot_t;
-        if (FIRST && count_out && blockIdx.x == 0 && threadIdx.x == 0) *count_out = total;      // V: elements of the later passes
-        uint32_t bpre = block_scan_add_u32(csum_t, s_scan, &total) - csum_t;
-        __syncthreads();                                    // every thread has read its s_cnt columns
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const uint32_t d = threadIdx.x * PER + j;
-            s_gbase[d] = g + before[j] - bpre;              // global slot = s_gbase[digit] + position in block order
-            s_cnt[0][d] = bpre;
-            s_cnt[1][d] = bpre + c[j][0];
-            s_cnt[2][d] = bpre + c[j][0] + c[j][1];
-            s_cnt[3][d] = bpre + c[j][0] + c[j][1] + c[j][2];
-            g += dtot[j]; bpre += csum[j];
-        }
-    }
-    __syncthreads();
-    // Reorder inside LDS first, then write: consecutive lanes hold consecutive output slots, so every digit run
-    // leaves the block as one contiguous segment.  Scattering straight from registers wrote 4-byte fragments
-    // of 256 different runs: 2.2x write amplification at the memory side (profiles/r01_pmc_hbm_traffic.csv).
-    uint32_t nvalid_w = 0;
-#pragma unroll
-    for (int k = 0; k < EMD_SORT_ITEMS; k++) {
-        if (rank[k] != 0xFFFFFFFFu) {
-            const uint32_t digit = ((key[k] - offset) >> shift) & mask;
-            const uint32_t pos = s_cnt[wave][digit] + rank[k];
-            s_keys[pos] = key[k];
-            s_vals[pos] = val[k];
-            if (CARRY) s_carry[pos] = car[k];
-            nvalid_w++;
-        }
-    }
-    uint32_t nvalid;
-    block_scan_add_u32(nvalid_w, s_scan, &nvalid);         // (ends with a barrier: the reordered tile is complete)
-#pragma unroll
-    for (int k = 0; k < EMD_SORT_ITEMS; k++) {
-        const uint32_t pos = threadIdx.x + (uint32_t)k * EMD_BLOCK;
-        if (pos < nvalid) {
-            const uint32_t kk = s_keys[pos];
-            const size_t dst = (size_t)s_gbase[((kk - offset) >> shift) & mask] + pos;
-            keys_out[dst] = kk;
-            vals_out[dst] = s_vals[pos];
-            if (CARRY) carry_out[dst] = s_carry[pos];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // K5 tile ranges
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(EMD_BLOCK) k_tile_ranges(const uint32_t* __restrict__ tkeys,
@@ -557,28 +323,6 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_export_keys(size_t D, const uint3
     if (quad_masks) quad_masks[i] = w >> EMD_ID_BITS;
 }
 
-// one stable LSD pass over `n_cap` (launch bound) / sort_n(cnt) (actual) pairs; `skip_hist`: the histogram was built by the producer
-template <int BITS, bool FIRST>
-int radix_pass(const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, SortN cnt, size_t n_cap, int shift,
-               int bits, uint32_t offset, uint32_t* hist, bool skip_hist, int range_bits, uint32_t* overflow_word, uint32_t* count_out,
-               hipStream_t st, const uint2* carry_in = nullptr, uint2* carry_out = nullptr) {
-    const uint32_t nsb = (uint32_t)((n_cap + EMD_SORT_TILE - 1) / EMD_SORT_TILE);
-    const uint32_t mask = (1u << bits) - 1u;
-    if (!skip_hist) {
-        hipLaunchKernelGGL((k_radix_hist<BITS, FIRST>), dim3(nsb), dim3(EMD_BLOCK), 0, st, kin, cnt, shift, mask, offset, nsb, hist, range_bits,
-                           overflow_word);
-        EMD_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_radix_scan_bins, dim3(1u << BITS), dim3(EMD_BLOCK), 0, st, hist, nsb);
-    EMD_LAUNCH_CHECK();
-    if (carry_in) hipLaunchKernelGGL((k_radix_scatter<BITS, FIRST, true>), dim3(nsb), dim3(EMD_BLOCK), 0, st, kin, vin, kout, vout, cnt, shift, mask, offset, nsb,
-                                     hist, count_out, carry_in, carry_out);
-    else hipLaunchKernelGGL((k_radix_scatter<BITS, FIRST, false>), dim3(nsb), dim3(EMD_BLOCK), 0, st, kin, vin, kout, vout, cnt, shift, mask, offset, nsb, hist,
-                            count_out, carry_in, carry_out);
-    EMD_LAUNCH_CHECK();
-    return EMD_OK;
-}
-
 }  // namespace
 
 int emd_launch_binning(const EmdSettings& s, int flags, int N, const GeomWs& g, const BinWs& b, int64_t capacity, EmdStatus* status,
@@ -587,7 +331,6 @@ int emd_launch_binning(const EmdSettings& s, int flags, int N, const GeomWs& g, 
     const int T = gx * gy;
     if (gx >= 1024 || gy >= 1024) { emd_set_error("image too large: %d x %d tiles (max 1023)", gx, gy); return EMD_ERR_INVALID; }
     const int nb = (N + EMD_BLOCK - 1) / EMD_BLOCK;
-    int rc;
     emd_prof_switch(PROF_PREPROCESS, PROF_SORT, st);
     if (N <= 0) {           // nothing to sort: empty ranges, identity order (the status block was not cleared by a projection kernel)
         { int zrc = emd_zero_async(status, sizeof(EmdStatus), st); if (zrc) return zrc; }
@@ -597,44 +340,29 @@ int emd_launch_binning(const EmdSettings& s, int flags, int N, const GeomWs& g, 
         emd_prof_switch(PROF_SORT, PROF_RANGES, st);
         return EMD_OK;
     }
-    // 1. visible Gaussians in depth order.  (The status word was cleared by K1: the depth passes may raise its overflow bit 1.)
-    uint32_t* const sort_count = &status->reserved;          // V after the first (compacting) depth pass lives in the status block
+    // 1. visible Gaussians in depth order: one compacting sort of the N depth keys, three passes of nine bits over (bits - bits(near plane)) or,
+    //    wide, four of eight over the raw bits.  (The status word was cleared by K1: pass 0 may raise its overflow bit 1.)
+    uint32_t* const sort_count = &status->reserved;          // V, published by pass 0, lives in the status block
     const bool wide = (flags & EMD_FLAG_WIDE_DEPTH_SORT) != 0;
-    const int depth_passes = wide ? EMD_DEPTH_PASSES_WIDE : EMD_DEPTH_PASSES_NARROW;
-    {
-        const SortN c0 = {nullptr, nullptr, (uint32_t)N}, cv = {sort_count, nullptr, 0u};
-        uint32_t near_bits = 0;
-        if (!wide) { const float np = s.near_plane > 0.f ? s.near_plane : 0.f; memcpy(&near_bits, &np, 4); }
-        uint32_t* ovf = &status->overflow;
-        // the binning records travel with the pairs (EMD_BIN_CARRY): pass p writes them to cb[p & 1], chosen so that the last pass lands in bin_s
-        uint2* const cb[2] = {(depth_passes & 1) ? g.bin_s : g.bin_t, (depth_passes & 1) ? g.bin_t : g.bin_s};
-        const bool carry = EMD_BIN_CARRY != 0;
-        if (wide) {
-            rc = radix_pass<8, true>(g.depth_key, nullptr, g.gkeys[0], g.gvals[0], c0, (size_t)N, 0, 8, 0u, g.ghist, false, 32, ovf, sort_count, st,
-                                     carry ? g.binrec : nullptr, cb[0]);
-            for (int p = 1; p < depth_passes && !rc; p++)
-                rc = radix_pass<8, false>(g.gkeys[(p - 1) & 1], g.gvals[(p - 1) & 1], g.gkeys[p & 1], g.gvals[p & 1], cv, (size_t)N, 8 * p, 8, 0u,
-                                          g.ghist, false, 32, ovf, nullptr, st, carry ? cb[(p - 1) & 1] : nullptr, cb[p & 1]);
-        } else {
-            const int B = EMD_DEPTH_BITS_NARROW;
-            rc = radix_pass<EMD_DEPTH_BITS_NARROW, true>(g.depth_key, nullptr, g.gkeys[0], g.gvals[0], c0, (size_t)N, 0, B, near_bits, g.ghist, false,
-                                                         EMD_DEPTH_RANGE_NARROW, ovf, sort_count, st, carry ? g.binrec : nullptr, cb[0]);
-            for (int p = 1; p < depth_passes && !rc; p++)
-                rc = radix_pass<EMD_DEPTH_BITS_NARROW, false>(g.gkeys[(p - 1) & 1], g.gvals[(p - 1) & 1], g.gkeys[p & 1], g.gvals[p & 1], cv, (size_t)N,
-                                                              B * p, B, near_bits, g.ghist, false, 32, ovf, nullptr, st,
-                                                              carry ? cb[(p - 1) & 1] : nullptr, cb[p & 1]);
-        }
-        if (rc) return rc;
-    }
-    const uint32_t* perm = g.gvals[(depth_passes - 1) & 1];
+    RadixSortArgs ds;
+    ds.keys_in = g.depth_key;
+    for (int i = 0; i < 2; i++) { ds.keys[i] = g.gkeys[i]; ds.vals[i] = g.gvals[i]; }
+    ds.hist = g.ghist;
+    ds.n_cap = (size_t)N;
+    ds.passes = wide ? EMD_DEPTH_PASSES_WIDE : EMD_DEPTH_PASSES_NARROW;
+    ds.bits = wide ? EMD_RADIX_BITS : EMD_DEPTH_BITS_NARROW;
+    ds.range_bits = wide ? 32 : EMD_DEPTH_RANGE_NARROW;
+    if (!wide) { const float np = s.near_plane > 0.f ? s.near_plane : 0.f; memcpy(&ds.offset, &np, 4); }
+    ds.overflow_word = &status->overflow;
+    ds.count_out = sort_count;
+    const int dbuf = emd_launch_radix_sort(ds, st);
+    if (dbuf < 0) return dbuf;
+    const uint32_t* perm = g.gvals[dbuf];
     // 2. the binning records in depth order + block sums; duplicate: every workgroup scans the block sums, finds its 2048 output slots and
     //    writes their (tile, Gaussian | quadrant mask) pairs; workgroup 0 publishes D / overflow / V
     emd_prof_switch(PROF_SORT, PROF_DUPLICATE, st);
     const int passes = emd_tile_passes(T), bits = emd_tile_pass_bits(T);
-    if (EMD_BIN_CARRY) hipLaunchKernelGGL((k_sorted_counts<true>), dim3(nb), dim3(EMD_BLOCK), 0, st, N, sort_count, perm, g.binrec, g.bin_s, g.block_sums, b.ranges,
-                                          (uint32_t)(2 * T));
-    else hipLaunchKernelGGL((k_sorted_counts<false>), dim3(nb), dim3(EMD_BLOCK), 0, st, N, sort_count, perm, g.binrec, g.bin_s, g.block_sums, b.ranges,
-                            (uint32_t)(2 * T));
+    hipLaunchKernelGGL(k_sorted_counts, dim3(nb), dim3(EMD_BLOCK), 0, st, N, sort_count, perm, g.binrec, g.bin_s, g.block_sums, b.ranges, (uint32_t)(2 * T));
     EMD_LAUNCH_CHECK();
     if (capacity <= 0) {    // D and V are still reported (capacity 0 is how callers size the workspace)
         hipLaunchKernelGGL(k_duplicate, dim3(1), dim3(EMD_BLOCK), 0, st, N, gx, g.bin_s, perm, g.block_sums, (uint64_t)0, status, b.tkeys[0], b.vals[0],
@@ -652,14 +380,17 @@ int emd_launch_binning(const EmdSettings& s, int flags, int N, const GeomWs& g, 
     EMD_LAUNCH_CHECK();
     // 3. stable partition by tile id
     emd_prof_switch(PROF_DUPLICATE, PROF_SORT, st);
-    const SortN cd = {&status->num_rendered, &status->overflow, 0u};
-    int cur = 0;
-    for (int p = 0; p < passes; p++) {
-        rc = radix_pass<8, false>(b.tkeys[cur], b.vals[cur], b.tkeys[cur ^ 1], b.vals[cur ^ 1], cd, (size_t)capacity, p * bits, bits, 0u, b.hist,
-                                  p == 0, 32, nullptr, nullptr, st);
-        if (rc) return rc;
-        cur ^= 1;
-    }
+    RadixSortArgs ts;
+    for (int i = 0; i < 2; i++) { ts.keys[i] = b.tkeys[i]; ts.vals[i] = b.vals[i]; }
+    ts.hist = b.hist;
+    ts.n_dev = &status->num_rendered;
+    ts.n_dev_overflow = &status->overflow;
+    ts.n_cap = (size_t)capacity;
+    ts.passes = passes;
+    ts.bits = bits;
+    ts.hist0_ready = true;
+    const int cur = emd_launch_radix_sort(ts, st);          // (== b.sorted_buf, which the render kernels and the export read)
+    if (cur < 0) return cur;
     emd_prof_switch(PROF_SORT, PROF_RANGES, st);
     const unsigned rb = (unsigned)(((size_t)capacity + EMD_BLOCK - 1) / EMD_BLOCK);
     hipLaunchKernelGGL(k_tile_ranges, dim3(rb < 4096u ? rb : 4096u), dim3(EMD_BLOCK), 0, st, b.tkeys[cur], status, b.ranges);
@@ -676,18 +407,4 @@ int emd_launch_export_keys(int64_t D, const GeomWs& g, const BinWs& b, uint64_t*
                        b.tkeys[b.sorted_buf], b.vals[b.sorted_buf], g.depth_key, keys, ids, quad_masks);
     EMD_LAUNCH_CHECK();
     return EMD_OK;
-}
-
-// The radix passes above for callers outside the rasterizer (knn.hip): stable LSD sort of (key, element index) pairs by the low 8 * passes bits
-// of n 32-bit keys.  The first pass drops the keys equal to 0xFFFFFFFF and publishes the number kept in *count (device); the sorted pairs end
-// in keys[(passes - 1) & 1] / vals[(passes - 1) & 1].  hist: 256 * ceil(n / EMD_SORT_TILE) words.
-int emd_launch_sort_pairs(const uint32_t* keys_in, uint32_t n, int passes, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t* hist,
-                          uint32_t* count, hipStream_t st) {
-    if (n == 0 || passes < 1) return EMD_OK;
-    const SortN c0 = {nullptr, nullptr, n}, cv = {count, nullptr, 0u};
-    int rc = radix_pass<8, true>(keys_in, nullptr, keys[0], vals[0], c0, (size_t)n, 0, 8, 0u, hist, false, 32, nullptr, count, st);
-    for (int p = 1; p < passes && !rc; p++)
-        rc = radix_pass<8, false>(keys[(p - 1) & 1], vals[(p - 1) & 1], keys[p & 1], vals[p & 1], cv, (size_t)n, 8 * p, 8, 0u, hist, false, 32, nullptr,
-                                  nullptr, st);
-    return rc;
 }

@@ -31,11 +31,9 @@ struct GeomWs {
                              //   touched << 12.  A skip bit: the outer quadrant column / row of the rectangle's first / last tile lies outside the box
     uint32_t* depth_key;     // [N] by Gaussian id: float bits of the view depth, 0xFFFFFFFF when not visible (K1)
     uint32_t* gkeys[2];      // [N] ping-pong of the Gaussian depth sort
-    uint32_t* gvals[2];      // [N] Gaussian ids in depth order after the sort (gvals[1])
+    uint32_t* gvals[2];      // [N] Gaussian ids in depth order after the sort (in the pair the sort's launcher returns)
     uint2* bin_s;            // [N] the same records in depth order
-    uint2* bin_t;            // [N] ping-pong partner of bin_s: the records travel through the depth passes as a second value (round 5)
     uint32_t* ghist;         // radix histograms of the depth sort [bins][ceil(N / sort tile)]
-    uint32_t* sort_count;    // [1] visible Gaussians V: published by the first depth pass (which compacts), read by the later ones
     uint32_t* block_sums;    // [ceil(N/256)] pairs emitted per block of 256 depth-ordered Gaussians (added up by the last depth pass)
     size_t bytes;
 };
@@ -49,7 +47,7 @@ struct BinWs {
     uint32_t* surv;          // [4 * capacity] per (tile, quadrant): the Gaussian ids of the list entries whose footprint reaches the quadrant, in
                              //   list order, written by the render forward for the render backward (at 4 * range start + quadrant * list length)
     uint32_t* quad_need;     // [4 * T] how many of them lie in front of the quadrant's deepest contributor (what the backward walks)
-    int sorted_buf;          // which ping-pong buffer holds the sorted list after forward (fixed by #passes)
+    int sorted_buf;          // which ping-pong buffer holds the sorted list after forward: emd_radix_result_buf of the tile sort
     size_t bytes;
 };
 
@@ -88,6 +86,10 @@ static inline int emd_tile_pass_bits(int num_tiles) {
     const int p = emd_tile_passes(num_tiles);
     return p ? (emd_tile_bits(num_tiles) + p - 1) / p : 0;
 }
+// Which pair of a sort's ping-pong buffers holds the pairs after `passes` passes (radix_sort.h).  Pass 0 of a compacting sort reads the raw keys
+// and writes pair 0; every other pass writes the pair it did not read, starting from pair 0.  The sort's launcher picks the buffers of every pass
+// with this function and returns its value; BinWs::sorted_buf below is the same function of the tile sort's pass count.
+static inline int emd_radix_result_buf(bool compacting, int passes) { return passes < 1 ? 0 : (passes - (compacting ? 1 : 0)) & 1; }
 
 static inline void emd_carve_geom(void* base, int N, GeomWs* w) {
     char* p = (char*)base;
@@ -100,10 +102,8 @@ static inline void emd_carve_geom(void* base, int N, GeomWs* w) {
     for (int i = 0; i < 2; i++) { w->gkeys[i] = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256); }
     for (int i = 0; i < 2; i++) { w->gvals[i] = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256); }
     w->bin_s = (uint2*)(p + off); off = emd_align_up(off + n * 8, 256);
-    w->bin_t = (uint2*)(p + off); off = emd_align_up(off + n * 8, 256);
     size_t nsb = (n + EMD_SORT_TILE - 1) / EMD_SORT_TILE;
     w->ghist = (uint32_t*)(p + off); off = emd_align_up(off + nsb * EMD_DEPTH_BINS_MAX * 4, 256);
-    w->sort_count = (uint32_t*)(p + off); off = emd_align_up(off + 16, 256);
     size_t nb = (n + EMD_BLOCK - 1) / EMD_BLOCK;
     w->block_sums = (uint32_t*)(p + off); off = emd_align_up(off + (nb + 8) * 4, 256);
     w->bytes = off + 256;
@@ -121,7 +121,7 @@ static inline void emd_carve_bin(void* base, int64_t capacity, int num_tiles, Bi
     w->hist = (uint32_t*)(p + off); off = emd_align_up(off + nsb * EMD_RADIX_BINS * 4, 256);
     w->surv = (uint32_t*)(p + off); off = emd_align_up(off + cap * 16, 256);
     w->quad_need = (uint32_t*)(p + off); off = emd_align_up(off + (size_t)num_tiles * 16, 256);
-    w->sorted_buf = emd_tile_passes(num_tiles) & 1;
+    w->sorted_buf = emd_radix_result_buf(false, emd_tile_passes(num_tiles));
     w->bytes = off + 256;
 }
 
@@ -172,8 +172,6 @@ int emd_launch_preprocess(const PreArgs& a, int part, hipStream_t st);       // 
 int emd_launch_binning(const EmdSettings& s, int flags, int N, const GeomWs& g, const BinWs& b, int64_t capacity, EmdStatus* status,
                        hipStream_t st);                                       // binning.hip
 int emd_launch_export_keys(int64_t D, const GeomWs& g, const BinWs& b, uint64_t* keys, uint32_t* ids, uint32_t* quad_masks, hipStream_t st);  // binning.hip
-int emd_launch_sort_pairs(const uint32_t* keys_in, uint32_t n, int passes, uint32_t* const keys[2], uint32_t* const vals[2], uint32_t* hist,
-                          uint32_t* count, hipStream_t st);   // binning.hip: the radix passes for other callers (knn.hip)
 // extra colour sets composited by the same list walk as the main colours (EmdFwdArgs.colors_extra ...)
 struct EmdExtra {
     int num;

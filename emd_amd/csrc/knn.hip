@@ -10,7 +10,7 @@
 //   k_knn_bounds_*   bounding box of the finite points (two launches, no atomics)
 //   k_knn_keys       30-bit Z-order key per point; a point with a non-finite coordinate gets the key 0xFFFFFFFF, which the first radix pass
 //                    drops, and its output row (-1 / +inf) is written here
-//   (binning.hip)    stable radix sort of (key, index): 4 passes of 8 bits; V = number of finite points stays on the device
+//   (radix_sort.hip) stable radix sort of (key, index): 4 passes of 8 bits; V = number of finite points stays on the device
 //   k_knn_leaves     the points in sorted order as float4 (x, y, z, index bits); every 64 consecutive ones are a LEAF with its min / max corners
 //   k_knn_groups     every 64 consecutive leaves are a GROUP with its corners
 //   k_knn_search<K>  one wave per leaf; lane i owns query i of the leaf and keeps its K best (distance, index) pairs sorted in registers.
@@ -24,6 +24,7 @@
 // The traversal order is fixed, so the result is deterministic, equidistant candidates included (the earlier one in the order stays).
 #include "common.h"
 #include "device_utils.h"
+#include "radix_sort.h"
 
 #include <math.h>
 
@@ -484,9 +485,16 @@ extern "C" int emd_knn(int32_t num_points, int32_t k, const float* pts, int32_t*
     EMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_knn_keys, dim3(nb), dim3(EMD_BLOCK), 0, st, N, k, pts, w.aabb, w.keys, idx, d2, mean_d2);
     EMD_LAUNCH_CHECK();
-    int rc = emd_launch_sort_pairs(w.keys, (uint32_t)N, KNN_SORT_PASSES, w.kbuf, w.vbuf, w.hist, w.count, st);
-    if (rc) return rc;
-    const uint32_t* perm = w.vbuf[(KNN_SORT_PASSES - 1) & 1];
+    RadixSortArgs zs;                                       // compacting: the keys of the non-finite points are all ones
+    zs.keys_in = w.keys;
+    for (int i = 0; i < 2; i++) { zs.keys[i] = w.kbuf[i]; zs.vals[i] = w.vbuf[i]; }
+    zs.hist = w.hist;
+    zs.n_cap = (size_t)N;
+    zs.passes = KNN_SORT_PASSES;
+    zs.count_out = w.count;
+    const int zbuf = emd_launch_radix_sort(zs, st);
+    if (zbuf < 0) return zbuf;
+    const uint32_t* perm = w.vbuf[zbuf];
     const unsigned leaf_blocks = w.num_groups_cap * KNN_GROUP / (EMD_BLOCK / 64);      // one wave per leaf
     hipLaunchKernelGGL(k_knn_leaves, dim3(leaf_blocks), dim3(EMD_BLOCK), 0, st, pts, perm, w.count, w.sp, w.leaf_box);
     EMD_LAUNCH_CHECK();
@@ -524,14 +532,19 @@ extern "C" int emd_knn_reverse(int32_t num_points, int32_t k, const int32_t* idx
     while (((int64_t)1 << bits) < num_points) bits++;
     const int passes = (bits + 7) / 8;
     // the values of the last pass are the answer: lay the ping-pong out so that it writes them into rev_slot
-    uint32_t* vals[2];
-    vals[(passes - 1) & 1] = (uint32_t*)rev_slot;
-    vals[passes & 1] = w.vbuf;
+    const int last = emd_radix_result_buf(true, passes);
     // a stable sort of (target, flat position) by target: positions ascend inside every target, entries < 0 (all ones) are dropped
-    int rc = emd_launch_sort_pairs((const uint32_t*)idx, total, passes, w.kbuf, vals, w.hist, w.count, st);
-    if (rc) return rc;
+    RadixSortArgs rs;
+    rs.keys_in = (const uint32_t*)idx;
+    for (int i = 0; i < 2; i++) { rs.keys[i] = w.kbuf[i]; rs.vals[i] = i == last ? (uint32_t*)rev_slot : w.vbuf; }
+    rs.hist = w.hist;
+    rs.n_cap = (size_t)total;
+    rs.passes = passes;
+    rs.count_out = w.count;
+    const int rbuf = emd_launch_radix_sort(rs, st);          // (== last)
+    if (rbuf < 0) return rbuf;
     hipLaunchKernelGGL(k_knn_rev_start, dim3((unsigned)(((size_t)total + 1 + EMD_BLOCK - 1) / EMD_BLOCK)), dim3(EMD_BLOCK), 0, st, (int)num_points, total,
-                       w.kbuf[(passes - 1) & 1], w.count, rev_start);
+                       w.kbuf[rbuf], w.count, rev_start);
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }

@@ -3,6 +3,8 @@
 
     python profiles/compare_kernel_isa.py OLD_TREE NEW_TREE > profiles/preprocess_split_isa.txt      # CPU only: hipcc -S cross-compiles gfx950
     python profiles/compare_kernel_isa.py OLD_TREE NEW_TREE mlp hexplane binning > profiles/switches_retired_isa.txt
+    python profiles/compare_kernel_isa.py OLD_TREE NEW_TREE binning=binning+radix_sort knn --rename 'k_sorted_counts<false>=k_sorted_counts' \
+        --removed 'k_sorted_counts<true>' ... > profiles/radix_sort_split_isa.txt
 
 OLD_TREE is a checkout of the commit before the change (`git worktree add` / `git archive`), NEW_TREE a checkout at or after it.  Every further
 argument names a unit of emd_amd/csrc (`mlp`: the old mlp.hip against the new one) or a split `OLD=NEW1+NEW2`; with none it is
@@ -15,8 +17,14 @@ symbol the instruction text of the function and its `.amdhsa_*` descriptor block
     * the __hip_cuid_* symbol (a hash of the compilation);
     * .file / .loc / .ident lines, comments and blank lines.
 
-Passes (exit status 0) when, for every argument, the kernel symbols of the new units together are exactly those of the old unit, no symbol is in
-two of them (nor, unless it has internal linkage, in the units of two arguments), and every kernel is identical.  One line per kernel: name, VGPRs, SGPRs, LDS bytes, scratch bytes, verdict."""
+A kernel whose symbol changes (a template parameter dropped) is paired with its successor by `--rename 'OLD=NEW'`, one per kernel, and a kernel
+that is dropped on purpose is named by `--removed 'OLD'`; both take the name as the table prints it or the mangled symbol, every pairing and
+removal is printed, none is guessed, and one that matches nothing fails the run.  A renamed kernel that lost arguments has a smaller argument
+segment: for a renamed kernel, and for no other, a difference in the `.amdhsa_kernarg_size` line alone is printed as it is and does not fail the run.
+
+Passes (exit status 0) when, for every argument, the kernel symbols of the new units together are exactly those of the old unit (after the renames,
+less the removed ones), no symbol is in two of them (nor, unless it has internal linkage, in the units of two arguments), and every kernel is
+identical.  One line per kernel: name, VGPRs, SGPRs, LDS bytes, scratch bytes, verdict."""
 import difflib
 import os
 import re
@@ -92,8 +100,20 @@ def main():
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     old_tree, new_tree = (os.path.abspath(p) for p in sys.argv[1:3])
+    # --rename 'OLD=NEW' / --removed 'OLD': explicit pairings of the symbols that change
+    rest, renames, removed = [], {}, set()
+    it = iter(sys.argv[3:])
+    for a in it:
+        if a == "--rename":
+            o, n = next(it).split("=")
+            renames[o.strip()] = n.strip()
+        elif a == "--removed":
+            removed.add(next(it).strip())
+        else:
+            rest.append(a)
+    unused = set(renames) | removed
     # [(old unit, new units)]
-    groups = [(a.split("=")[0], tuple(a.split("=")[-1].split("+"))) for a in (sys.argv[3:] or DEFAULT_UNITS)]
+    groups = [(a.split("=")[0], tuple(a.split("=")[-1].split("+"))) for a in (rest or DEFAULT_UNITS)]
     new_units = [u for _, us in groups for u in us]
     flags = {u: unit_flags(new_tree, u) for u in new_units}
     hips = lambda units: " / ".join(u + ".hip" for u in units)
@@ -104,6 +124,7 @@ def main():
     print("# compared: the instruction text of the function and its .amdhsa_* descriptor, modulo local-label function indices, __hip_cuid_*, comments")
     print(f"# {'kernel':28s} {'unit':15s} {'VGPRs':>5s} {'SGPRs':>5s} {'LDS B':>6s} {'scratch B':>9s}  verdict")
     ok = True
+    n_removed = [0, 0]                     # kernels removed on purpose, renamed kernels identical but for the kernarg size
     n_old, n_new, seen = {}, {}, {}          # seen: symbol -> new unit over ALL arguments (anonymous-namespace symbols are per unit: kept per argument only)
     for old_unit, units in groups:
         old, new, where = kernels_of(assemble(old_tree, old_unit, flags[units[0]])), {}, {}
@@ -120,6 +141,30 @@ def main():
             n_new[u] = len(ks)
         n_old[old_unit] = len(old)
         names = demangle(sorted(set(old) | set(new)))
+        named = lambda syms, x: [s for s in syms if x in (s, names[s])]
+        note = {}                                # new symbol -> the old name it was paired with
+        for o_name, n_name in renames.items():
+            os_, ns_ = named(old, o_name), named([s for s in new if s not in old], n_name)
+            if not os_:
+                continue                         # (a kernel of another argument's unit)
+            unused.discard(o_name)
+            if len(os_) != 1 or len(ns_) != 1:
+                print(f"# FAIL: --rename {o_name}={n_name}: {len(os_)} old and {len(ns_)} new kernels of these names in {old_unit}.hip -> {hips(units)}")
+                ok = False
+                continue
+            print(f"# --rename: {names[os_[0]]} ({os_[0]}) -> {names[ns_[0]]} ({ns_[0]})")
+            k = old.pop(os_[0])
+            old[ns_[0]] = dict(k, body=[l.replace(os_[0], ns_[0]) for l in k["body"]], desc=[l.replace(os_[0], ns_[0]) for l in k["desc"]])
+            note[ns_[0]] = names[os_[0]]
+        for o_name in sorted(removed):
+            for s in named(old, o_name):
+                if s in new:
+                    continue
+                unused.discard(o_name)
+                k = old.pop(s)
+                n_old[old_unit] -= 1
+                n_removed[0] += 1
+                print(f"{names[s]:30s} {'-':15s} {k['vgpr']:5d} {k['sgpr']:5d} {k['lds']:6d} {k['scratch']:9d}  removed (--removed: in the old unit only)  ({s})")
         for s in sorted(set(old) | set(new), key=lambda s: (where.get(s, "~"), names[s], s)):
             if s not in new or s not in old:
                 print(f"{names[s]:30s} {where.get(s, '-'):15s} {'':>5s} {'':>5s} {'':>6s} {'':>9s}  {'MISSING in the new units' if s not in new else 'NOT in the old unit'}  ({s})")
@@ -127,17 +172,28 @@ def main():
                 continue
             o, n = old[s], new[s]
             same = o["body"] == n["body"] and o["desc"] == n["desc"]
+            verdict = "identical" if same else "DIFFERENT"
+            if not same and s in note:           # a renamed kernel that lost arguments: the size of its argument segment is the one line that may differ
+                ka = lambda k: [l for l in k["body"] + k["desc"] if l.startswith(".amdhsa_kernarg_size")]
+                rest_of = lambda k: [l for l in k["body"] + ["--"] + k["desc"] if not l.startswith(".amdhsa_kernarg_size")]
+                if rest_of(o) == rest_of(n):
+                    same, verdict = True, f"identical but for {ka(o)[0]} -> {ka(n)[0].split()[-1]}"
+                    n_removed[1] += 1
             ok &= same
             anon = "_GLOBAL__N_" in s
-            print(f"{names[s]:30s} {where[s]:15s} {n['vgpr']:5d} {n['sgpr']:5d} {n['lds']:6d} {n['scratch']:9d}  {'identical' if same else 'DIFFERENT'}"
-                  f"{'' if anon else '  (outside the anonymous namespace)'}")
+            print(f"{names[s]:30s} {where[s]:15s} {n['vgpr']:5d} {n['sgpr']:5d} {n['lds']:6d} {n['scratch']:9d}  {verdict}"
+                  f"{'' if anon else '  (outside the anonymous namespace)'}{'  (was ' + note[s] + ')' if s in note else ''}")
             if not same:
                 for what in ("desc", "body"):
                     for d in list(difflib.unified_diff(o[what], n[what], "old", "new", lineterm="", n=1))[:40]:
                         print("#     " + d)
+    for x in sorted(unused):
+        print(f"# FAIL: --rename / --removed {x}: no such kernel in the old units")
+        ok = False
     per = lambda counts: ", ".join(f"{u}.hip {k}" for u, k in counts.items())
-    print(f"# {sum(n_old.values())} kernels in the old unit{'s (' + per(n_old) + ')' if len(n_old) > 1 else ''}, {sum(n_new.values())} in the new units ({per(n_new)}): "
-          + ("ALL IDENTICAL" if ok else "FAILED"))
+    print(f"# {sum(n_old.values())} kernels in the old unit{'s (' + per(n_old) + ')' if len(n_old) > 1 else ''}, {sum(n_new.values())} in the new units ({per(n_new)})"
+          f"{', ' + str(n_removed[0]) + ' more in the old units removed on purpose' if n_removed[0] else ''}: "
+          + ("FAILED" if not ok else "ALL IDENTICAL" + (f" ({n_removed[1]} of them but for the size of the argument segment, as printed)" if n_removed[1] else "")))
     sys.exit(0 if ok else 1)
 
 

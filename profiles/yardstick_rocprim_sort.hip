@@ -1,6 +1,6 @@
 // yardstick_rocprim_sort.hip -- a YARDSTICK ONLY (never linked into the product, nothing under emd_amd/ includes rocPRIM):
 // rocprim::radix_sort_pairs (the library's onesweep / merge-sort dispatch) on the two sorts of the binning stage at the bench's sizes,
-// timed with HIP events, next to what the hand-written passes of csrc/binning.hip take for the same job (profiles/r05_sort_yardstick.txt).
+// timed with HIP events, next to what the hand-written passes of csrc/radix_sort.hip take for the same job (profiles/r05_sort_yardstick.txt).
 //
 //   (a) depth sort: u32 keys of 27 significant bits (depth bits above the near plane), u32 values, V = 1.06 M pairs
 //       (the product additionally compacts the N = 2 M keys to the V visible ones in its first pass; the yardstick is given the V pairs)

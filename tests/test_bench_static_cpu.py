@@ -33,7 +33,7 @@ def test_stage_kernels_exist_in_the_sources():
     """... and the names are kernels of the current sources (a summary of an older round may hold kernels that are gone)."""
     import bench
     import re
-    src = "".join(open(os.path.join(ROOT, "emd_amd", "csrc", f)).read() for f in ("preprocess.hip", "binning.hip", "render.hip"))
+    src = "".join(open(os.path.join(ROOT, "emd_amd", "csrc", f)).read() for f in ("preprocess.hip", "binning.hip", "radix_sort.hip", "render.hip"))
     for stage, kernels in bench.PMC_STAGE_KERNELS.items():
         for k in kernels:
             base = re.sub(r"\[[ND]\]$", "", k)

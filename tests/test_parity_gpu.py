@@ -71,6 +71,27 @@ def test_tile_pass_counts(kw):
         compare_forward(hip, orc, tol=IMAGE_TOL)
 
 
+@pytest.mark.parametrize("kw", [
+    dict(n=12000, H=16, W=16, seed=45),                # one tile: zero tile passes
+    dict(n=12000, H=16, W=40, seed=46),                # three tiles: one tile pass
+    dict(n=12000, H=64, W=96, seed=47),                # 24 tiles: one tile pass of five bits
+    dict(n=12000, H=272, W=272, seed=48),              # 289 tiles: two tile passes
+], ids=lambda k: "-".join(f"{a}{b}" for a, b in k.items()))
+def test_wide_depth_sort_across_tile_pass_counts(kw):
+    """The four-pass (even) wide depth sort in front of a tile sort of 0, 1 and 2 passes, over more than one 2048-element sort block: the
+    sort's launcher derives the buffer pair that holds a result from the pass count, and the three-pass (odd) narrow sort of the other tests
+    leaves its result in the other pair.  More than 4096 visible Gaussians: five sort blocks, at least as many blocks of the duplicate kernel
+    (the oracle gives V = 8831, 8909, 8602, 8567 and D = 8831, 11023, 21563, 62562)."""
+    case = make_case(**kw)
+    orc = run_oracle(case, backward=False)
+    assert int((orc["pre"]["radii"] > 0).sum()) > 4096, "the case does not span several sort blocks"
+    for keep_all in (False, True):
+        hip = run_hip(case, backward=False, wide_depth_sort=True, keep_all_pairs=keep_all)
+        compare_forward(hip, orc, tol=IMAGE_TOL)       # bit-exact on keys, ids and ranges
+        if keep_all:
+            np.testing.assert_array_equal(hip["keys"], orc["bin"]["keys"])
+
+
 def test_equal_depth_ties_keep_gaussian_order():
     """Gaussians at exactly the same view depth: the reference's stable sort leaves them in index order inside a tile.
     The depth-first sort must do the same (stable depth sort of the Gaussians, stable partition by tile)."""
