@@ -90,13 +90,16 @@ def cube_lookup(cube, dirs):
     return out.reshape(dirs.shape[:-1] + (C,))
 
 
-def rays(H, W, K, R, T, jitter=None):
-    """get_rays_torch (S3Gaussian/utils/graphics_utils.py:220-241): unit ray directions [H,W,3]."""
+def rays(H, W, K, R, T, jitter=None, dtype=torch.float32):
+    """get_rays_torch (S3Gaussian/utils/graphics_utils.py:220-241): unit ray directions [H,W,3].  `dtype`: the precision of the whole
+    evaluation (pixel grid, K, R, T and jitter are taken in it); the reference's is float32."""
+    K, R, T = K.to(dtype), R.to(dtype), T.to(dtype)
     rays_o = -torch.matmul(R.T, T).squeeze()
-    i, j = torch.meshgrid(torch.arange(W, dtype=torch.float32), torch.arange(H, dtype=torch.float32), indexing="xy")
+    i, j = torch.meshgrid(torch.arange(W, dtype=dtype), torch.arange(H, dtype=dtype), indexing="xy")
     if jitter is None:
         xy1 = torch.stack([i + 0.5, j + 0.5, torch.ones_like(i)], dim=2)
     else:
+        jitter = jitter.to(dtype)
         xy1 = torch.stack([i + jitter[..., 0], j + jitter[..., 1], torch.ones_like(i)], dim=2)
     pixel_camera = torch.matmul(xy1, torch.inverse(K).T)
     pixel_world = torch.matmul(pixel_camera - T.squeeze(), R)
@@ -110,7 +113,7 @@ def sky_s3g(cube, dirs_hw3, acc=None, fill=0.0, threshold=1e-3):
     if acc is None:
         return cube_lookup(cube, dirs_hw3).permute(2, 0, 1).clamp(0.0, 1.0)
     mask = (1 - acc[0]) > threshold
-    sky = torch.full((H, W, 3), float(fill))
+    sky = torch.full((H, W, 3), float(fill), dtype=cube.dtype)
     sky[mask] = cube_lookup(cube, dirs_hw3[mask])
     return sky.permute(2, 0, 1).clamp(0.0, 1.0)
 

@@ -1,7 +1,8 @@
 """-m gpu: the HIP sky cube-map path (through the C ABI, emd_amd/sky.py) against the CPU oracle and the golden vectors
 captured from the reference's SkyCubeMap / EnvLight.  Floating point: colours within 2e-5 of the oracle (fp32: the bilinear
 weights are fractions of u * res, so their rounding error grows with res -- ~res * 2^-23; the face / tap decisions are
-identical), texture gradients within 1e-4 of the largest entry (float atomics reorder the sums)."""
+identical), texture gradients within 1e-4 of the largest entry (float atomics reorder the sums).  The camera-ray path (rays built in the
+kernel, 2-D backward tiles) is compared element by element with the float64 oracle further down, on the cases and bars of tests/sky_cases.py."""
 import os
 import types
 
@@ -109,3 +110,101 @@ def test_full_size_properties():
     got = m.sky_cube_map.grad.sum(dim=(0, 1, 2)).cpu().numpy()
     np.testing.assert_allclose(got, expect, rtol=2e-4)
     torch.testing.assert_close(render.grad, acc.detach().expand(3, H, W), atol=1e-6, rtol=0)
+
+
+# ---- the camera-ray path (SkyCubeMap / composite_s3g: rays built in the kernel, 16 x 16 backward tiles with the LDS window) element by element
+# ---- against the float64 oracle.  Cases, reference and bars: tests/sky_cases.py; the bars are 4 x what float32 costs the oracle itself, measured
+# ---- by tests/test_sky_cpu.py, never taken from the kernel.
+from tests import sky_cases as sc  # noqa: E402
+
+
+def _camera(c, dev, **extra):
+    return types.SimpleNamespace(image_height=c.H, image_width=c.W, intrinsic=c.K.to(dev), world_view_transform=c.w2c.T.contiguous().to(dev), **extra)
+
+
+def _run(c, cam, through_forward=False):
+    """One forward + backward of case `c` on the HIP path -> dict of sky_cases.QUANTITIES on the CPU.  through_forward: SkyCubeMap.forward and the
+    blend in torch instead of composite_s3g (what composite_s3g itself does for a camera with a sky_mask)."""
+    from emd_amd.sky import SkyCubeMap, composite_s3g
+    dev = torch.device("cuda", 0)
+    cfg = types.SimpleNamespace(sky_resolution=c.res, sky_white_background=c.white, white_background=False)
+    m = SkyCubeMap(cfg, device=dev)
+    m.sky_cube_map.data = c.cube.to(dev)
+    render, weight = c.render.to(dev).requires_grad_(True), c.acc.to(dev).requires_grad_(True)
+    train = c.jitter is not None
+    jitter = c.jitter.to(dev) if train else None
+    if not c.blend:
+        out, sky = None, m(cam, acc=weight)
+    elif through_forward:
+        sky = m(cam, acc=weight, is_train=train, jitter=jitter)
+        out = render * weight + sky * (1 - weight)
+    else:
+        out, sky = composite_s3g(m, cam, render, weight, is_train=train, jitter=jitter)
+    sc.loss(out, sky, c.g_out.to(dev), c.g_sky.to(dev)).backward()
+    r = {"sky": sky.detach().cpu(), "d_cube": m.sky_cube_map.grad.cpu()}
+    if c.blend:
+        r.update(out=out.detach().cpu(), d_render=render.grad.cpu(), d_weight=weight.grad.cpu())
+    return r
+
+
+def _check(got, c, only=None):
+    ref = sc.reference(c.id, c.white)
+    assert set(got) == set(ref)
+    assert torch.equal(got["sky"][:, ~c.sampled], torch.full_like(got["sky"][:, ~c.sampled], c.fill))     # not looked up: the fill, exactly
+    assert torch.isfinite(got["d_cube"]).all()
+    bad = []
+    for q in only or ref:
+        assert got[q].shape == ref[q].shape
+        diff, limit = sc.max_diff(got[q], ref[q], c, q), sc.bar(c.id, q)
+        print(f"{c.id} white={c.white} {q}: max |hip - float64| {diff:.3e}  bar {limit:.3e}  largest reference entry {float(ref[q].abs().max()):.3e}")
+        if not diff <= limit:
+            bad.append((q, diff, limit))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("white", [True, False])
+@pytest.mark.parametrize("case_id", list(sc.CASES))
+def test_camera_rays_forward_backward_vs_oracle(case_id, white):
+    """composite_s3g on every case of sky_cases.CASES: sky, out, dL/dcube at every texel, dL/drender, dL/dweight."""
+    c = sc.build(case_id, white)
+    _check(_run(c, _camera(c, torch.device("cuda", 0))), c)
+
+
+@pytest.mark.parametrize("white", [True, False])
+@pytest.mark.parametrize("through_forward", [False, True])
+def test_jitter_vs_oracle(through_forward, white):
+    """A given sub-pixel draw under is_train, through composite_s3g and through SkyCubeMap.forward, against the reference with the same draw."""
+    c = sc.build("jitter", white)
+    _check(_run(c, _camera(c, torch.device("cuda", 0)), through_forward), c)
+
+
+@pytest.mark.parametrize("white", [True, False])
+def test_sky_mask_route_vs_oracle(white):
+    """is_train with camera.sky_mask: rows < 50 forced on, threshold 0.5, the fill elsewhere, two launches and the blend in torch."""
+    c = sc.build("sky-mask", white)
+    dev = torch.device("cuda", 0)
+    _check(_run(c, _camera(c, dev, sky_mask=c.sky_mask.to(dev))), c)
+
+
+@pytest.mark.parametrize("white", [True, False])
+def test_forward_without_blend_vs_oracle(white):
+    """SkyCubeMap.forward(cam, acc=acc): dL/dcube from the sky colour's gradient alone."""
+    c = sc.build("no-blend", white)
+    _check(_run(c, _camera(c, torch.device("cuda", 0))), c)
+
+
+@pytest.mark.parametrize("white", [True, False])
+def test_device_camera_matches_host_camera(white):
+    """camera.sky_rays (the 21 floats on the device) against the host-camera call: the same arithmetic, so everything but dL/dcube is
+    bit-identical; dL/dcube (float atomics reorder) is held to the oracle's bar."""
+    from emd_amd.sky import sky_ray_constants
+    c = sc.build("corner-64", white)
+    dev = torch.device("cuda", 0)
+    host_cam = _camera(c, dev)
+    host = _run(c, host_cam)
+    rays = sky_ray_constants(host_cam.intrinsic, host_cam.world_view_transform).to(dev)
+    assert rays.shape == (21,)
+    got = _run(c, types.SimpleNamespace(image_height=c.H, image_width=c.W, sky_rays=rays))
+    for q in ("sky", "out", "d_render", "d_weight"):
+        assert torch.equal(got[q], host[q]), q
+    _check(got, c, only=["d_cube"])
