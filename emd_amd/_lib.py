@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libemd_raster.so")
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 MAX_EXTRA = 2
 SETTINGS_DEV_FLOATS = 38
 TILE = 16
@@ -210,6 +210,12 @@ class EmdAdamArgs(C.Structure):
     _fields_ = [("num_tensors", C.c_int32), ("reserved", C.c_int32), ("tensors", EmdAdamTensor * ADAM_MAX_TENSORS)]
 
 
+class EmdRadixSortArgs(C.Structure):
+    _fields_ = [("keys_in", _f), ("keys", _f * 2), ("vals", _f * 2), ("hist", _f), ("n_cap", C.c_int64), ("n_dev", _f), ("n_dev_overflow", _f),
+                ("passes", C.c_int32), ("bits", C.c_int32), ("offset", C.c_uint32), ("range_bits", C.c_int32), ("overflow_word", _f),
+                ("count_out", _f)]
+
+
 # every symbol include/emd_raster.h declares
 EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_size", "emd_raster_forward",
                     "emd_raster_backward", "emd_raster_export_binning", "emd_raster_export_geometry",
@@ -223,7 +229,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_mlp_trunk_forward", "emd_mlp_trunk_backward", "emd_mlp_branch_forward", "emd_mlp_branch_backward",
                     "emd_abs_mean_backward", "emd_residual_l1_backward", "emd_tracked_pose_forward", "emd_tracked_pose_backward",
                     "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
-                    "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward")
+                    "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward",
+                    "emd_radix_sort")
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
 PROF_STAGES = 8
@@ -319,6 +326,7 @@ def load():
     lib.emd_knn_reverse.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_embed_reg_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     lib.emd_embed_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]
+    lib.emd_radix_sort.argtypes = [C.POINTER(EmdRadixSortArgs), C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p

@@ -117,7 +117,11 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_radix_scatter(const uint32_t* __r
     __shared__ uint32_t s_scan[4];
     const uint32_t D = sort_n(cnt);
     const uint32_t nblocks = (D + EMD_SORT_TILE - 1) / EMD_SORT_TILE;
-    if (blockIdx.x >= nblocks) return;
+    if (blockIdx.x >= nblocks) {
+        // an empty input (a device-side count of 0, or one voided by its overflow word) still publishes its count: the later passes read it
+        if (FIRST && count_out && blockIdx.x == 0 && threadIdx.x == 0) *count_out = 0u;
+        return;
+    }
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -258,4 +262,33 @@ int emd_launch_radix_sort(const RadixSortArgs& a, hipStream_t st) {
         if (rc) return rc;
     }
     return emd_radix_result_buf(compacting, a.passes);
+}
+
+// The sort on its own (include/emd_raster.h): marshals the C struct into RadixSortArgs after validating it; nothing is launched for a bad argument.
+extern "C" int emd_radix_sort(const EmdRadixSortArgs* a, void* hip_stream) {
+    if (!a) { emd_set_error("radix_sort: null args"); return EMD_ERR_INVALID; }
+    if (!a->keys[0] || !a->keys[1] || !a->vals[0] || !a->vals[1] || !a->hist) { emd_set_error("radix_sort: null keys / vals / hist pointer"); return EMD_ERR_INVALID; }
+    if (a->bits < 1 || a->bits > 9) { emd_set_error("radix_sort: bits %d outside 1..9", a->bits); return EMD_ERR_INVALID; }
+    if (a->passes < 0 || (int64_t)a->passes * a->bits > 32) { emd_set_error("radix_sort: passes %d: need passes >= 0 and passes * bits <= 32", a->passes); return EMD_ERR_INVALID; }
+    const bool compacting = a->keys_in != nullptr;
+    if (compacting && (a->passes < 1 || !a->count_out)) { emd_set_error("radix_sort: a compacting sort needs passes >= 1 and count_out"); return EMD_ERR_INVALID; }
+    if (a->range_bits < 0 || a->range_bits > 32) { emd_set_error("radix_sort: range_bits %d outside 0..32", a->range_bits); return EMD_ERR_INVALID; }
+    if (a->range_bits < 32 && !a->overflow_word) { emd_set_error("radix_sort: range_bits < 32 needs overflow_word"); return EMD_ERR_INVALID; }
+    if (a->n_dev_overflow && !a->n_dev) { emd_set_error("radix_sort: n_dev_overflow without n_dev"); return EMD_ERR_INVALID; }
+    // positions and counts are 32-bit on the device, rounded up to whole blocks of EMD_SORT_TILE keys
+    if (a->n_cap < 0 || a->n_cap > (int64_t)0xFFFFFFFFu - EMD_SORT_TILE) { emd_set_error("radix_sort: n_cap %lld is negative or too large for 32-bit positions", (long long)a->n_cap); return EMD_ERR_INVALID; }
+    RadixSortArgs r;
+    r.keys_in = a->keys_in;
+    for (int i = 0; i < 2; i++) { r.keys[i] = a->keys[i]; r.vals[i] = a->vals[i]; }
+    r.hist = a->hist;
+    r.n_cap = (size_t)a->n_cap;
+    r.n_dev = a->n_dev;
+    r.n_dev_overflow = a->n_dev_overflow;
+    r.passes = a->passes;
+    r.bits = a->bits;
+    r.offset = a->offset;
+    r.range_bits = a->range_bits;
+    r.overflow_word = a->overflow_word;
+    r.count_out = a->count_out;
+    return emd_launch_radix_sort(r, (hipStream_t)hip_stream);          // (n_cap == 0: no launch, the result index alone)
 }

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EMD_ABI_VERSION 28
+#define EMD_ABI_VERSION 29
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
 #define EMD_TILE_X 16
@@ -911,6 +911,38 @@ int emd_embed_reg_forward(int32_t num_points, int32_t k, int32_t embed_dim, cons
 int emd_embed_reg_backward(int32_t num_points, int32_t k, int32_t embed_dim, const float* e, const int32_t* idx, const float* w, const float* c,
                            const int32_t* rev_start, const int32_t* rev_slot, const float* g, const float* inv_pairs, float* grad_e,
                            int32_t accumulate, void* hip_stream);
+
+/* ---- ABI 29: the radix sort of the binning and k-NN stages on its own ------------------------------------------------------------
+ * A stable LSD radix sort of (32-bit key, 32-bit value) pairs: `passes` passes of `bits` bits each, from the lowest bit of
+ * rel = key - offset (mod 2^32) upwards.  The pairs end ordered by the low passes * bits bits of rel; pairs equal in those bits keep their
+ * input order, and the full keys travel with the values.  This is the sort behind the depth sort, the tile sort and the k-NN lists
+ * (csrc/radix_sort.h), exported so that it can be tested directly; a caller with pairs to sort may use it as well.
+ *   - keys_in == NULL: the pairs start in keys[0] / vals[0].  keys_in != NULL: a COMPACTING sort of keys_in [n]: the value of element i is
+ *     i, elements whose key is 0xFFFFFFFF are dropped, and the number kept is written to *count_out (passes >= 1 and count_out required).
+ *     A kept element with rel >> range_bits != 0 raises bit 1 (value 2) of *overflow_word (range_bits < 32 requires overflow_word;
+ *     the word is only ever OR-ed into, never cleared).
+ *   - the element count n is n_cap, or *n_dev when n_dev != NULL (it must not exceed n_cap), read as 0 while *n_dev_overflow != 0
+ *     (n_dev_overflow may be NULL).  No host synchronisation.
+ *   - keys[0], keys[1], vals[0], vals[1]: n_cap words each, all four distinct; hist: (bits == 9 ? 512 : 256) * ceil(n_cap / 2048) words
+ *     of scratch.  Only the first n (compacting: *count_out) positions of a pair are written.
+ *   - returns the index (0 or 1) of the pair that holds the result: 0 when passes < 1, else (passes - (keys_in != NULL)) & 1; or a
+ *     negative EMD_ERR_*.  Every argument is validated before anything is launched; n_cap == 0 launches nothing.
+ *   - 1 <= bits <= 9, passes >= 0, passes * bits <= 32, 0 <= n_cap <= 2^32 - 1 - 2048. */
+typedef struct EmdRadixSortArgs {
+    const uint32_t* keys_in;
+    uint32_t* keys[2];
+    uint32_t* vals[2];
+    uint32_t* hist;
+    int64_t n_cap;
+    const uint32_t* n_dev;
+    const uint32_t* n_dev_overflow;
+    int32_t passes, bits;
+    uint32_t offset;
+    int32_t range_bits;
+    uint32_t* overflow_word;
+    uint32_t* count_out;
+} EmdRadixSortArgs;
+int emd_radix_sort(const EmdRadixSortArgs* args, void* hip_stream);
 
 #ifdef __cplusplus
 }

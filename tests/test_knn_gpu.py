@@ -154,6 +154,42 @@ def test_reverse_table(table_200k):
     assert int(s.rev_start[5]) == 20
 
 
+def _reverse_of(idx):
+    """emd_knn_reverse on a table of the test's own making; -> (rev_start, rev_slot), pre-filled with -7 where the call writes nothing."""
+    from emd_amd import _lib as L
+    lib = L.load()
+    n, k = idx.shape
+    idx = idx.to(torch.int32).to(DEV).contiguous()
+    rev_start = torch.full((n + 1,), -7, dtype=torch.int32, device=DEV)
+    rev_slot = torch.full((n * k,), -7, dtype=torch.int32, device=DEV)
+    ws = torch.empty(lib.emd_knn_reverse_workspace(n, k), dtype=torch.uint8, device=DEV)
+    L.check(lib.emd_knn_reverse(n, k, idx.data_ptr(), rev_start.data_ptr(), rev_slot.data_ptr(), ws.data_ptr(), ws.numel(),
+                                torch.cuda.current_stream().cuda_stream), "emd_knn_reverse")
+    torch.cuda.synchronize()
+    return rev_start.cpu(), rev_slot.cpu()
+
+
+def test_reverse_of_synthetic_tables():
+    """emd_knn_reverse takes any idx: tables no point cloud produces.  One hub that every filled slot targets (one digit holds every key of
+    the sort), no filled slot at all (everything dropped), the last point only, and 257 points (nine target bits: two passes)."""
+    g = torch.Generator().manual_seed(30)
+    n, k = 3000, 20
+    empty = torch.rand(n, k, generator=g) < 0.2
+    tables = {
+        "hub": torch.where(empty, -1, 0),
+        "empty": torch.full((n, k), -1),
+        "last": torch.where(empty, -1, n - 1),
+        "uniform_257": torch.randint(0, 257, (257, k), generator=g),
+    }
+    for name, idx in tables.items():
+        rev_start, rev_slot = _reverse_of(idx)
+        kc.check_reverse(idx, rev_start, rev_slot)
+        m = int((idx >= 0).sum())
+        assert int(rev_start[-1]) == m, name
+        assert (rev_slot[m:] == -7).all(), f"{name}: slots behind the {m} filled ones were written"
+    assert int((tables["uniform_257"] == 256).sum()) > 0             # the ninth bit is in use
+
+
 def _grad_close(got, ref):
     got, ref = got.detach().cpu().double(), ref.double()
     err = torch.abs(got - ref)
