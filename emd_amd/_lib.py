@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libemd_raster.so")
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 MAX_EXTRA = 2
 SETTINGS_DEV_FLOATS = 38
 TILE = 16
@@ -230,7 +230,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_abs_mean_backward", "emd_residual_l1_backward", "emd_tracked_pose_forward", "emd_tracked_pose_backward",
                     "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
                     "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward",
-                    "emd_radix_sort")
+                    "emd_radix_sort", "emd_camera_grad_workspace_size", "emd_raster_backward_camera")
+CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
 PROF_STAGES = 8
@@ -327,6 +328,8 @@ def load():
     lib.emd_embed_reg_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     lib.emd_embed_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]
     lib.emd_radix_sort.argtypes = [C.POINTER(EmdRadixSortArgs), C.c_void_p]
+    lib.emd_camera_grad_workspace_size.argtypes = [C.c_int32, C.POINTER(C.c_size_t)]
+    lib.emd_raster_backward_camera.argtypes = [C.POINTER(EmdBwdArgs), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p
@@ -363,3 +366,9 @@ def workspace_sizes(N, H, W, capacity, flags=0, num_extra=0):
     out = (C.c_size_t * 4)()
     check(load().emd_raster_workspace_size(C.byref(d), out), "emd_raster_workspace_size")
     return tuple(int(x) for x in out)
+
+
+def camera_grad_workspace_size(N):
+    out = C.c_size_t()
+    check(load().emd_camera_grad_workspace_size(int(N), C.byref(out)), "emd_camera_grad_workspace_size")
+    return int(out.value)

@@ -404,6 +404,55 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     return EMD_OK;
 }
 
+int emd_camera_grad_workspace_size(int32_t num_gaussians, size_t* bytes) {
+    if (!bytes || num_gaussians < 0) { emd_set_error("camera_grad_workspace_size: bad argument (N=%d)", num_gaussians); return EMD_ERR_INVALID; }
+    *bytes = emd_camera_grad_bytes(num_gaussians);
+    return EMD_OK;
+}
+
+int emd_raster_backward_camera(const EmdBwdArgs* a, float* dL_dcamera, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!a) { emd_set_error("backward_camera: null args"); return EMD_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int N = a->num_gaussians;
+    int rc = check_common(a->s, N, a->sh_coeffs, a->means3D, a->shs, a->colors_precomp, a->opacities, a->scales,
+                          a->rotations, a->cov3D_precomp, a->flags, a->motion);
+    if (rc) return rc;
+    if (!a->radii || !a->geom_ws || !a->bin_ws || !a->img_ws || !a->bwd_ws || !a->status || !a->out_color || !a->out_depth) {
+        emd_set_error("backward_camera: null state pointer"); return EMD_ERR_INVALID;
+    }
+    if (!dL_dcamera) { emd_set_error("backward_camera: null dL_dcamera"); return EMD_ERR_INVALID; }
+    if (a->dL_dnormal) {
+        // the normal image depends on the view matrix (nv = V nw and its sign flip): that path has no camera gradient yet -- refused, not left out
+        emd_set_error("backward_camera: the camera gradient does not cover the normal image; call without dL_dnormal");
+        return EMD_ERR_INVALID;
+    }
+    if (a->num_extra < 0 || a->num_extra > EMD_MAX_EXTRA) { emd_set_error("backward_camera: num_extra %d not in 0..%d", a->num_extra, EMD_MAX_EXTRA); return EMD_ERR_INVALID; }
+    if ((a->flags & EMD_FLAG_SDEV_TANFOV) && !a->settings_dev) { emd_set_error("backward_camera: EMD_FLAG_SDEV_TANFOV without settings_dev"); return EMD_ERR_INVALID; }
+    GeomWs g;
+    emd_carve_geom((void*)a->geom_ws, N, &g);
+    const size_t need = (size_t)(N > 0 ? N : 1) * emd_bwd_stride(a->num_extra) * sizeof(float);
+    if (g.bytes > a->geom_bytes || need > a->bwd_bytes || !workspace || workspace_bytes < emd_camera_grad_bytes(N)) {
+        emd_set_error("backward_camera: workspace too small (camera %zu/%zu)", workspace_bytes, emd_camera_grad_bytes(N)); return EMD_ERR_WORKSPACE;
+    }
+    if ((uintptr_t)workspace & 15) { emd_set_error("backward_camera: workspace must be 16-byte aligned"); return EMD_ERR_INVALID; }
+    PreBwdArgs pb;
+    memset(&pb, 0, sizeof(pb));                // (no gradient outputs: the kernel writes the workspace and dL_dcamera only)
+    pb.s = a->s; pb.N = N; pb.M = a->sh_coeffs; pb.flags = a->flags;
+    pb.means3D = a->means3D; pb.shs = a->shs; pb.colors_precomp = a->colors_precomp; pb.opacities = a->opacities;
+    pb.scales = a->scales; pb.rotations = a->rotations; pb.cov3D_precomp = a->cov3D_precomp;
+    if (a->flags & EMD_FLAG_MOTION) pb.motion = a->motion;
+    pb.radii = a->radii; pb.g = g; pb.grad_rec = (float*)a->bwd_ws;
+    pb.sdev = a->settings_dev;
+    pb.bwd_stride = emd_bwd_stride(a->num_extra); pb.num_extra = a->num_extra;
+    rc = emd_launch_camera_backward(pb, (float*)workspace, dL_dcamera, st);
+    if (rc) return rc;
+    if (a->s.debug) {
+        hipError_t e_ = hipStreamSynchronize(st);
+        if (e_ != hipSuccess) { emd_set_error("stage camera_backward failed: %s", hipGetErrorString(e_)); return EMD_ERR_HIP; }
+    }
+    return EMD_OK;
+}
+
 int emd_raster_export_binning(const EmdDims* dims, const void* geom_ws, size_t geom_bytes, const void* bin_ws, size_t bin_bytes,
                               int64_t num_rendered, uint64_t* keys, uint32_t* ids, uint32_t* ranges, uint32_t* quad_masks,
                               void* hip_stream) {

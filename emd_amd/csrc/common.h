@@ -218,3 +218,8 @@ __device__ __forceinline__ void emd_settings_from_device(EmdSettings& S, const f
 int emd_launch_preprocess_backward(const PreBwdArgs& a, hipStream_t st);     // preprocess.hip
 // the clamp-masked colour gradient of every Gaussian (the factor of its rank-one dL/dshs) from the render backward's accumulator rows
 int emd_launch_sh_factor(int N, const int32_t* radii, const GeomWs& g, const float* grad_rec, int bwd_stride, float* dL_dsh_color, hipStream_t st);
+// camera_grad.hip: dL/d(viewmatrix, projmatrix, campos) from the accumulator rows K7 left (read, not cleared), between the two halves of the
+// backward.  `partials`: emd_camera_grad_bytes(N) bytes, 16-byte aligned, one 36-float row per workgroup; every one of the 35 outputs is written.
+size_t emd_camera_grad_rows(int N);
+size_t emd_camera_grad_bytes(int N);
+int emd_launch_camera_backward(const PreBwdArgs& a, float* partials, float* dL_dcamera, hipStream_t st);

@@ -24,7 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .rasterizer import GaussianRasterizationSettings, RasterCall, RasterConfig, _Rasterize
+from .rasterizer import GaussianRasterizationSettings, RasterCall, RasterConfig, _Rasterize, camera_inputs
 
 
 class _SphericalHarmonics(torch.autograd.Function):
@@ -125,8 +125,12 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     # options of THESE calls (nothing process-wide is touched): no normal image, gsplat's near plane, absgrad as asked
     opts = RasterConfig.replace(compute_normal=False, absgrad=bool(absgrad), near_plane=float(near_plane))
     flags = (L.FLAG_ABSGRAD if absgrad else 0) | (L.FLAG_NO_SYNC if opts.no_sync else 0)
+    # camera-pose optimisation (OmniRe's CameraOptModule perturbs camtoworlds): with viewmats.requires_grad the camera of every view stays
+    # attached -- _device_camera is plain differentiable torch on 4x4 tensors, the rasterizer returns dL/d(wvt, full, campos), autograd
+    # carries them back to viewmats[c].  Ks stays detached (gsplat gives no gradient for it either).
+    pose_grad = bool(viewmats.requires_grad) and torch.is_grad_enabled()
     for c in range(Cn):
-        vm = viewmats[c].detach().float()
+        vm = viewmats[c].float() if pose_grad else viewmats[c].detach().float()
         K = Ks[c].detach().float()
         if vm.device.type == "cpu" or K.device.type == "cpu":
             vm, K = vm.to(dev), K.to(dev)
@@ -141,7 +145,8 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         rec = RasterCall()
         color, depth, _n, alpha, radii = _Rasterize.apply(means.contiguous().float(), sink, shs, col, opac.contiguous().float(),
                                                           scales.contiguous().float(), quats_n.contiguous(), None, None, None,
-                                                          None, None, rs, flags, opts, rec)[:5]
+                                                          None, None, rs, flags, opts, rec, None, None, None, None,
+                                                          *camera_inputs(rs))[:5]
         if absgrad:
             def _hook(g, c=c, rec=rec):          # runs after this call's backward: its record holds this call's |grad| sums
                 means2d.absgrad[c] = rec.absgrad * scale

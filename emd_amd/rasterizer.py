@@ -101,10 +101,12 @@ class RasterCall:
     (pixel, list entry) pairs it evaluated, the number that contributed, the accumulator rows it sent to memory as float atomics and the
     float atomics issued (EmdBwdArgs.pair_stats).
     `loop_stats` (diagnostic; an int64[6] device tensor set by the caller before the call): the compositing kernel adds the trip counts of its scan /
-    cull / drain loops (EmdFwdArgs.loop_stats; profiles/render_loop_trips.py)."""
+    cull / drain loops (EmdFwdArgs.loop_stats; profiles/render_loop_trips.py).
+    `camera_grad` (after the backward of a call whose camera tensors require grad, else None): the 35 floats dL/d(viewmatrix[16],
+    projmatrix[16], campos[3]) of emd_raster_backward_camera; `camera_partials`: that call's per-workgroup rows (the same allocation)."""
     __slots__ = ("status", "num_rendered", "num_visible", "geom_ws", "bin_ws", "img_ws", "sizes", "capacity", "N", "H", "W",
                  "flags", "settings_dev", "absgrad", "sh_color_grad", "grad_slab", "on_backward", "render_grads", "pair_stats",
-                 "status_buffer", "slab_inputs", "on_sh_factor", "radii", "loop_stats")
+                 "status_buffer", "slab_inputs", "on_sh_factor", "radii", "loop_stats", "camera_grad", "camera_partials")
 
     def __init__(self):
         for k in self.__slots__:
@@ -301,10 +303,21 @@ def _fill_motion(m: L.EmdMotion, actor_ids, actor_pose, residual_dx, residual_dq
     m.residual_dq = L.ptr(residual_dq)
 
 
+def camera_inputs(rs):
+    """(viewmatrix, projmatrix, campos) of the settings as inputs of the autograd node: each one only when it is a device tensor that
+    requires grad, else None -- a call without such a tensor is the call it always was."""
+    pick = lambda t: t if (isinstance(t, torch.Tensor) and t.device.type != "cpu" and t.requires_grad) else None
+    return pick(rs.viewmatrix), pick(rs.projmatrix), pick(rs.campos)
+
+
 class _Rasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, actor_pose,
-                residual_dx, residual_dq, actor_ids, raster_settings, flags, opts, rec, extra0=None, extra1=None, shs_res0=None, shs_res1=None):
+                residual_dx, residual_dq, actor_ids, raster_settings, flags, opts, rec, extra0=None, extra1=None, shs_res0=None, shs_res1=None,
+                cam_view=None, cam_proj=None, cam_pos=None):
+        """`cam_view` / `cam_proj` / `cam_pos`: raster_settings.viewmatrix / projmatrix / campos again, as INPUTS of the node, each only when it
+        is a device tensor that requires grad (else None): the backward then returns dL/d of them (camera-pose optimisation).  Their values
+        are read from raster_settings as always."""
         lib = L.load()
         dev = means3D.device
         if dev.type != "cuda":
@@ -396,6 +409,7 @@ class _Rasterize(torch.autograd.Function):
         ctx.has = (shs is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None,
                    actor_pose is not None, residual_dx is not None, residual_dq is not None)
         ctx.num_extra = len(extras)
+        ctx.cam_shapes = tuple(None if t is None else tuple(t.shape) for t in (cam_view, cam_proj, cam_pos))
         ctx.save_for_backward(means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, actor_pose,
                               residual_dx, residual_dq, actor_ids, radii, geom_ws, bin_ws, img_ws, status, out_color,
                               out_depth, out_normal, sdev, *extras, *out_extra)
@@ -497,14 +511,29 @@ class _Rasterize(torch.autograd.Function):
         for k in range(nx):
             b.colors_extra[k], b.out_extra[k] = extras[k].data_ptr(), out_extra[k].data_ptr()
             b.dL_dextra[k], b.dL_dcolors_extra[k] = L.ptr(g_extra[k]), d_extra[k].data_ptr()
-        if factored and rec.on_sh_factor is not None:
-            # two calls: render backward + the SH factor, the caller's hook (collectives of the factors on the communication stream), then the
-            # projection backward, under which they run
+        want_cam = any(sh is not None for sh in ctx.cam_shapes)
+        d_cam = None
+        if want_cam:
+            # one allocation: the 35 outputs (padded to 36 floats) in front of the per-workgroup rows
+            cam_bytes = L.camera_grad_workspace_size(N)
+            cam_buf = torch.empty(36 + (cam_bytes + 3) // 4, device=dev, dtype=torch.float32)
+            d_cam, cam_rows = cam_buf[:L.CAMERA_GRAD_FLOATS], cam_buf[36:]
+        two_calls = factored and rec.on_sh_factor is not None
+        if two_calls or want_cam:
+            # two calls: render backward (+ the SH factor), then what belongs between the halves -- the camera gradient, which reads the
+            # accumulator rows before the projection backward consumes them, and the caller's hook (collectives of the factors on the
+            # communication stream) -- then the projection backward, under which the collectives run
             b.flags = bflags | L.FLAG_BWD_RENDER_ONLY
             L.check(lib.emd_raster_backward(C.byref(b), _stream()), "emd_raster_backward (render half)")
-            rec.sh_color_grad = d_shc
-            rec.on_sh_factor(rec)
-            b.flags, b.dL_dsh_color = bflags | L.FLAG_BWD_PROJECT_ONLY, None
+            if want_cam:
+                L.check(lib.emd_raster_backward_camera(C.byref(b), d_cam.data_ptr(), cam_rows.data_ptr(), cam_rows.numel() * 4, _stream()),
+                        "emd_raster_backward_camera")
+            if two_calls:
+                rec.sh_color_grad = d_shc
+                rec.on_sh_factor(rec)
+            b.flags = bflags | L.FLAG_BWD_PROJECT_ONLY
+            if d_shc is not None:
+                b.dL_dsh_color = None                  # (extracted behind the render half already)
             L.check(lib.emd_raster_backward(C.byref(b), _stream()), "emd_raster_backward (projection half)")
         else:
             L.check(lib.emd_raster_backward(C.byref(b), _stream()), "emd_raster_backward")
@@ -514,6 +543,7 @@ class _Rasterize(torch.autograd.Function):
             _clean_ws[ws_key] = bwd_ws
         rec.absgrad, rec.sh_color_grad, rec.grad_slab = d_abs, d_shc, slab
         rec.render_grads = bwd_ws.view(max(N, 1), -1) if opts.keep_render_grads else None
+        rec.camera_grad, rec.camera_partials = (d_cam, cam_rows) if want_cam else (None, None)
         if d_abs is not None and ctx.means2D_ref is not None:
             ctx.means2D_ref.absgrad = d_abs          # what gsplat's backward does with `means2d.absgrad`
         if rec.on_backward is not None:
@@ -528,8 +558,9 @@ class _Rasterize(torch.autograd.Function):
             # gradient object then has a single owner and is adopted, not cloned
             alias = torch.empty(0, device=d_shs.device, dtype=d_shs.dtype).set_(d_shs.untyped_storage(), d_shs.storage_offset(), d_shs.shape, d_shs.stride())
             d_r0, d_r1 = (alias if ctx.has_shs_res[0] else None), (alias if ctx.has_shs_res[1] else None)
+        d_cv, d_cp, d_cc = (None if sh is None else d_cam[lo:hi].reshape(sh) for sh, (lo, hi) in zip(ctx.cam_shapes, ((0, 16), (16, 32), (32, 35))))
         return (d_means3D, d_means2D, d_shs, d_col, d_op, d_sc, d_rot, d_cov, d_pose, d_rdx, d_rdq, None, None, None, None, None, d_x[0], d_x[1],
-                d_r0, d_r1)
+                d_r0, d_r1, d_cv, d_cp, d_cc)
 
 
 class GaussianRasterizer(nn.Module):
@@ -632,7 +663,7 @@ class GaussianRasterizer(nn.Module):
         res += [None] * (2 - len(res))
         color, depth, normal, alpha, radii, *x_imgs = _Rasterize.apply(
             means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, actor_pose, residual_dx,
-            residual_dq, actor_ids, rs, flags, opts, rec, extras[0], extras[1], res[0], res[1])
+            residual_dq, actor_ids, rs, flags, opts, rec, extras[0], extras[1], res[0], res[1], *camera_inputs(rs))
         self.last_call = rec
         return color, depth, normal, alpha, radii, (list(x_imgs) if x_imgs else None)
 

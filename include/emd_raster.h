@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EMD_ABI_VERSION 29
+#define EMD_ABI_VERSION 30
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
 #define EMD_TILE_X 16
@@ -325,6 +325,22 @@ int emd_raster_workspace_size(const EmdDims* dims, size_t out[4]);
 
 int emd_raster_forward(EmdFwdArgs* args, void* hip_stream);
 int emd_raster_backward(const EmdBwdArgs* args, void* hip_stream);
+
+/* ---- ABI 30: the gradient of the camera (opt-in; camera-pose optimisation) --------------------------------------------------------
+ * dL/d(viewmatrix[16], projmatrix[16], campos[3]) of one call, 35 floats laid out as the settings block is (viewmatrix as
+ * EmdSettings.viewmatrix: V[4 k + r], translation at 12..14).  Every entry the projection reads is a free variable; the entries it never
+ * reads (V[3], V[7], V[11], V[15], the z column P[4 k + 2]) receive an exact 0.  The chain rule back to a camera pose is the caller's.
+ * The backward is then issued in its two halves with this call in between, all on one stream:
+ *     backward with EMD_FLAG_BWD_RENDER_ONLY  ->  backward_camera  ->  backward with EMD_FLAG_BWD_PROJECT_ONLY
+ * on the same EmdBwdArgs: it reads the accumulator rows the render half left in bwd_ws and changes none of them (the projection half
+ * still consumes them, and hands them back zeroed under EMD_FLAG_BWD_WS_CLEAN).  All 35 outputs are written by every call (no zero fill
+ * by the caller; num_gaussians == 0 gives 35 zeros).  The sum is deterministic: per-workgroup rows in `workspace` (the size the first
+ * function reports, 16-byte aligned; EMD_ERR_WORKSPACE when smaller), added in a fixed order in double precision -- no float atomics.
+ * The normal image's dependence on the view matrix is not covered: a non-NULL dL_dnormal is refused with EMD_ERR_INVALID.
+ * No gradient for tanfov, the intrinsics behind projmatrix, or bg. */
+int emd_camera_grad_workspace_size(int32_t num_gaussians, size_t* bytes);
+int emd_raster_backward_camera(const EmdBwdArgs* args, float* dL_dcamera /*[35], device*/, void* workspace, size_t workspace_bytes,
+                               void* hip_stream);
 
 /* Copy binning state out for parity tests: sorted keys (tile<<32 | depth bits), sorted Gaussian ids, the quadrant mask of every
  * entry (bit q = qy * 2 + qx: the Gaussian's alpha >= 1/255 footprint reaches the 8x8 quadrant q of the tile; ABI 21),
