@@ -15,7 +15,16 @@ MAX_EXTRA = 2
 SETTINGS_DEV_FLOATS = 38
 TILE = 16
 ACTOR_STRIDE = 12
-BWD_STRIDE = 12
+BWD_PAYLOAD = 12
+
+
+def bwd_stride(num_extra=0):
+    """Pitch in floats of an accumulator row of the render backward (emd_bwd_stride of csrc/common.h): the 12 payload floats + 4 per extra
+    colour set, rounded up to whole 64-byte lines."""
+    return (BWD_PAYLOAD + 4 * int(num_extra) + 15) // 16 * 16
+
+
+BWD_STRIDE = bwd_stride(0)
 
 EMD_OK, EMD_ERR_INVALID, EMD_ERR_CAPACITY, EMD_ERR_HIP, EMD_ERR_WORKSPACE, EMD_ERR_DEPTH_RANGE = 0, -1, -2, -3, -4, -5
 FLAG_NORMAL, FLAG_MOTION, FLAG_ABSGRAD, FLAG_NO_SYNC, FLAG_CLAMP_RGB01, FLAG_RAW_PARAMS, FLAG_SDEV_TANFOV = 1, 2, 4, 8, 16, 32, 64

@@ -345,6 +345,7 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     if (g.bytes > a->geom_bytes || b.bytes > a->bin_bytes || im.bytes > a->img_bytes || need > a->bwd_bytes) {
         emd_set_error("backward: workspace too small"); return EMD_ERR_WORKSPACE;
     }
+    if ((uintptr_t)a->bwd_ws & 63) { emd_set_error("backward: bwd_ws must be 64-byte aligned (an accumulator row is one 64-byte line)"); return EMD_ERR_INVALID; }
     if ((a->flags & EMD_FLAG_ABSGRAD) && !a->dL_dmeans2D_abs) { emd_set_error("backward: EMD_FLAG_ABSGRAD without dL_dmeans2D_abs"); return EMD_ERR_INVALID; }
     const bool dbg = a->s.debug != 0;
     // the two halves of the pass may arrive as two calls (EMD_FLAG_BWD_RENDER_ONLY, then EMD_FLAG_BWD_PROJECT_ONLY on the same workspaces)
@@ -435,6 +436,7 @@ int emd_raster_backward_camera(const EmdBwdArgs* a, float* dL_dcamera, void* wor
         emd_set_error("backward_camera: workspace too small (camera %zu/%zu)", workspace_bytes, emd_camera_grad_bytes(N)); return EMD_ERR_WORKSPACE;
     }
     if ((uintptr_t)workspace & 15) { emd_set_error("backward_camera: workspace must be 16-byte aligned"); return EMD_ERR_INVALID; }
+    if ((uintptr_t)a->bwd_ws & 63) { emd_set_error("backward_camera: bwd_ws must be 64-byte aligned (an accumulator row is one 64-byte line)"); return EMD_ERR_INVALID; }
     PreBwdArgs pb;
     memset(&pb, 0, sizeof(pb));                // (no gradient outputs: the kernel writes the workspace and dL_dcamera only)
     pb.s = a->s; pb.N = N; pb.M = a->sh_coeffs; pb.flags = a->flags;

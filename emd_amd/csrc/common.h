@@ -16,11 +16,13 @@
 // r1.w bits: 0..2 = SH colour channel clamped (zero gradient).
 #define EMD_REC_F4 4
 
-// Per-Gaussian gradient accumulator written by the render backward: 12 floats = 48 B (3 x float4)
+// Per-Gaussian gradient accumulator written by the render backward: 12 payload floats = 48 B (3 x float4)
 //   [0..1] d/d mean2D (pixel units)  [2] d/d depth  [3] d/d opacity
 //   [4..6] d/d conic (A,B,C)         [7..9] d/d rgb
 //   [10..11] sum |d/d mean2D| (EMD_FLAG_ABSGRAD)
-#define EMD_BWD_STRIDE 12
+// followed by (r, g, b, -) per extra colour set.  The row PITCH (emd_bwd_stride below) is the payload rounded up to whole 64-byte lines.
+#define EMD_BWD_PAYLOAD 12
+#define EMD_BWD_PITCH_ALIGN 16          // floats: a row starts on a 64-byte line and covers whole lines
 
 struct GeomWs {
     float4* rec;             // [N][4]
@@ -179,8 +181,12 @@ struct EmdExtra {
     float* out[EMD_MAX_EXTRA];             // [3,H,W]
     const float* dL_dout[EMD_MAX_EXTRA];   // [3,H,W] or null (backward)
 };
-// accumulator row of the render backward: EMD_BWD_STRIDE floats + (r, g, b, -) per extra colour set
-static inline int emd_bwd_stride(int num_extra) { return EMD_BWD_STRIDE + 4 * num_extra; }
+// pitch in floats of an accumulator row of the render backward: EMD_BWD_PAYLOAD floats + (r, g, b, -) per extra colour set, rounded up to whole
+// 64-byte lines (16, 16, 32 floats for 0, 1, 2 extra sets).  A device-scope float atomic is performed line by line on the memory side: a row that
+// starts on a line costs one request where a 48-byte pitch cost 1.5 on average.  Nobody writes the pad floats: a clean workspace stays clean.
+__host__ __device__ constexpr int emd_bwd_stride(int num_extra) {
+    return (EMD_BWD_PAYLOAD + 4 * num_extra + EMD_BWD_PITCH_ALIGN - 1) / EMD_BWD_PITCH_ALIGN * EMD_BWD_PITCH_ALIGN;
+}
 int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
                               float* out_color, float* out_depth, float* out_normal, float* out_alpha, const EmdExtra* x,
                               unsigned long long* loop_stats, hipStream_t st);   // render.hip
@@ -196,7 +202,7 @@ struct PreBwdArgs {
     EmdMotion motion;
     const int32_t* radii;
     GeomWs g;
-    float* grad_rec;        // [N][bwd_stride]; read, and cleared row by row under EMD_FLAG_BWD_WS_CLEAN
+    float* grad_rec;        // [N][bwd_stride]; read, and its payload cleared row by row under EMD_FLAG_BWD_WS_CLEAN
     int bwd_stride, num_extra;
     float* dL_dextra[EMD_MAX_EXTRA];   // [N,3] gradient of every extra colour set
     float *dL_dmeans3D, *dL_dmeans2D, *dL_dmeans2D_abs, *dL_dshs, *dL_dcolors, *dL_dopacities, *dL_dscales,

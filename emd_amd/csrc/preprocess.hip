@@ -676,7 +676,7 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
         if (a.dL_dsh_color) { a.dL_dsh_color[3 * i] = sh_gc[0]; a.dL_dsh_color[3 * i + 1] = sh_gc[1]; a.dL_dsh_color[3 * i + 2] = sh_gc[2]; }
         if (a.dL_dcolors) { a.dL_dcolors[3 * i] = gcol[0]; a.dL_dcolors[3 * i + 1] = gcol[1]; a.dL_dcolors[3 * i + 2] = gcol[2]; }
         for (int k = 0; k < a.num_extra; k++) {           // extra colour sets: the accumulated dL/d colour is the gradient of the input itself
-            float4* gxp = (float4*)(a.grad_rec + (size_t)i * a.bwd_stride + EMD_BWD_STRIDE + 4 * k);
+            float4* gxp = (float4*)(a.grad_rec + (size_t)i * a.bwd_stride + EMD_BWD_PAYLOAD + 4 * k);
             const float4 gx = *gxp;
             if (a.flags & EMD_FLAG_BWD_WS_CLEAN) *gxp = make_float4(0.f, 0.f, 0.f, 0.f);
             if (!a.dL_dextra[k]) continue;

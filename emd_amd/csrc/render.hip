@@ -370,7 +370,8 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
     // Round 3: the forward pass leaves, per quadrant, the ids of the entries whose footprint reaches it ("survivors", in list
     // order) and the number of them in front of its deepest contributor.  The backward walks that list back to front, 64 survivors
     // per batch, every lane keeping ITS entry's record in registers: no scan of the tile list, no footprint test, no queue.
-    constexpr int STRIDE = EMD_BWD_STRIDE + 4 * NX;             // accumulator row: 12 floats + (r, g, b, -) per extra set
+    constexpr int STRIDE = EMD_BWD_PAYLOAD + 4 * NX;            // payload of an accumulator row: 12 floats + (r, g, b, -) per extra set (the staging tile's rows)
+    constexpr int PITCH = emd_bwd_stride(NX);                   // its pitch in memory: whole 64-byte lines
     constexpr int PB = NORMAL ? 6 : 4;                          // s_pix planes of the main call; two more per extra set
     __shared__ float4 s_stage4[EMD_WAVE * STRIDE / 4];          // gradient staging tile: 64 rows x STRIDE floats
     __shared__ uint32_t q_id[EMD_WAVE];
@@ -542,7 +543,7 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
         const float m0 = m0_2.x + m0_2.y, gx = gx_2.x + gx_2.y, gy = gy_2.x + gy_2.y, m2xx = m2xx_2.x + m2xx_2.y,
                     m2xy = m2xy_2.x + m2xy_2.y, m2yy = m2yy_2.x + m2yy_2.y, a_dz = dz_2.x + dz_2.y, a_r = r_2.x + r_2.y,
                     a_g = g_2.x + g_2.y, a_b = b_2.x + b_2.y;
-        // rows through LDS so that consecutive lanes add consecutive floats of one 48-byte accumulator row
+        // rows through LDS so that consecutive lanes add consecutive floats of one accumulator row
         q_id[lane] = gid;
         float4* row = reinterpret_cast<float4*>(s_stage + lane * STRIDE);
         row[0] = make_float4(-gx, -gy, a_dz, m0 * __builtin_amdgcn_rcpf(g0.w));
@@ -559,15 +560,21 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
         }
         // (round 6, measured and not kept: walking 10 instead of 12 floats per row without absgrad -- 10 atomic instructions per 64 rows instead of 12 -- changes
         //  nothing: 0.4337 / 0.4362 against 0.4348 / 0.4372 ms, profiles/r06_render_ablations.txt; the lanes of floats 10, 11 were already masked off)
-        for (uint32_t idx = lane; idx < nb * STRIDE; idx += EMD_WAVE) {
-            const uint32_t e = idx / STRIDE, v = idx % STRIDE;
-            const float val = s_stage[idx];
-            if (STATS) st_atoms += (unsigned long long)__popcll(__ballot(val != 0.f));
+        // Lane -> (row, float) = (idx / PITCH, idx % PITCH): a 16-lane group adds into ONE aligned 64-byte line, 64 / PITCH rows per instruction.  The
+        // lanes of the pad floats idle; zero-valued floats are skipped (floats 10, 11 without absgrad, the fourth of an extra set).
+        static_assert(EMD_WAVE % PITCH == 0, "a row is a whole number of 16-lane groups");
+        {
+            const uint32_t v = lane % PITCH;
+            if (v < (uint32_t)STRIDE)
+                for (uint32_t e = lane / PITCH; e < nb; e += EMD_WAVE / PITCH) {
+                    const float val = s_stage[e * STRIDE + v];
+                    if (STATS) st_atoms += (unsigned long long)__popcll(__ballot(val != 0.f));
 #ifndef K7_ABL_NO_FLUSH          /* ablation build (profiles/r06_render_ablations.txt): the rows are staged but never added to HBM */
-            if (val != 0.f) atomicAdd(grad_rec + (size_t)q_id[e] * STRIDE + v, val);
+                    if (val != 0.f) atomicAdd(grad_rec + (size_t)q_id[e] * PITCH + v, val);
 #else
-            if (val == 12345.678f) grad_rec[0] = val;
+                    if (val == 12345.678f) grad_rec[0] = val;
 #endif
+                }
         }
         __syncthreads();
     };

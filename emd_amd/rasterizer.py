@@ -65,7 +65,7 @@ class RasterOptions:
                                     # per-(device, H, W) cache of the last observed count decides alone
     absgrad: bool = False           # also accumulate sum |d/d mean2D| (RasterCall.absgrad and `means2D.absgrad`, as gsplat does)
     clamp_rgb01: bool = False       # OmniRe colour clamp
-    keep_render_grads: bool = False  # tests: keep the per-Gaussian accumulator rows of the render backward (RasterCall.render_grads, [N, 12+])
+    keep_render_grads: bool = False  # tests: keep the per-Gaussian accumulator rows of the render backward (RasterCall.render_grads, [N, row pitch]: L.bwd_stride)
     factored_sh_grad: bool = False  # view-parallel DP: the backward leaves dL/dshs out and publishes the [N,3] factor instead
                                     # (RasterCall.sh_color_grad); emd_amd.dp rebuilds the dense, view-averaged gradient
     aux_stream: bool = False        # run the colour half of the projection kernel on a second stream beside the binning stage (the binding
@@ -156,7 +156,7 @@ def prepare_backward_workspace(device, num_gaussians, num_extra=0, stream=None):
     buffer of their own inside each graph.  emd_amd.StepGraphs calls this for its capture stream."""
     dev = torch.device(device)
     st = torch.cuda.current_stream(dev) if stream is None else stream
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), st.cuda_stream, max(int(num_gaussians), 1) * (L.BWD_STRIDE + 4 * int(num_extra)))
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), st.cuda_stream, max(int(num_gaussians), 1) * L.bwd_stride(num_extra))
     if key not in _clean_ws:
         with torch.cuda.stream(st):
             _clean_ws[key] = torch.zeros(key[2], device=dev, dtype=torch.float32)
@@ -461,14 +461,14 @@ class _Rasterize(torch.autograd.Function):
         d_rdq = z(N, 4) if has_rdq else None
         d_abs = z(N, 2) if flags & L.FLAG_ABSGRAD else None
         # accumulator rows of the render backward.  Kept across calls per (device, stream, size): the projection backward hands every
-        # row it reads back zeroed (EMD_FLAG_BWD_WS_CLEAN), so only the first use pays the 48 N-byte zero fill (20 us per step at 2 M).
+        # row it reads back zeroed (EMD_FLAG_BWD_WS_CLEAN), so only the first use pays the 64 N-byte zero fill (20 us per step at 2 M).
         # keep_render_grads (tests read the rows afterwards) takes a fresh buffer the library clears itself.
         ws_key, bflags = None, flags
         capturing = torch.cuda.is_current_stream_capturing()
         if opts.keep_render_grads:
-            bwd_ws = torch.empty(max(N, 1) * (L.BWD_STRIDE + 4 * nx), device=dev, dtype=torch.float32)
+            bwd_ws = torch.empty(max(N, 1) * L.bwd_stride(nx), device=dev, dtype=torch.float32)
         else:
-            ws_key = (dev.index, torch.cuda.current_stream().cuda_stream, max(N, 1) * (L.BWD_STRIDE + 4 * nx))
+            ws_key = (dev.index, torch.cuda.current_stream().cuda_stream, max(N, 1) * L.bwd_stride(nx))
             bwd_ws = _clean_ws.pop(ws_key, None)          # (popped: a failed backward must not leave a dirty buffer behind)
             if bwd_ws is not None:
                 bflags = flags | L.FLAG_BWD_WS_CLEAN

@@ -89,7 +89,7 @@ enum {
                                       intrinsics, OmniRe/models/trainers/base.py:399-400): they replace the by-value fields */
     EMD_FLAG_BWD_WS_CLEAN = 1 << 8, /* backward only (ABI 18): bwd_ws ARRIVES zero-filled (the caller's promise) and is LEFT zero-filled --
                                       the projection backward clears every accumulator row it reads, so a caller that keeps one
-                                      workspace across steps pays no 48 N-byte zero fill per backward.  Without the flag the library
+                                      workspace across steps pays no 64 N-byte zero fill per backward.  Without the flag the library
                                       clears the workspace itself, as before. */
     EMD_FLAG_BWD_RENDER_ONLY = 1 << 10, /* emd_raster_backward (ABI 21): only the render backward (K7).  With dL_dsh_color set, the clamp-masked
                                       colour gradient of every Gaussian -- the factor of its rank-one dL/dshs -- is extracted from the
@@ -253,7 +253,9 @@ typedef struct EmdBwdArgs {
     const float* dL_ddepth;       /* [1,H,W] */
     const float* dL_dalpha;       /* [1,H,W] */
     const float* dL_dnormal;      /* [3,H,W]  (propagated to the blended normal only) */
-    /* scratch for backward: [N, 12 + 4 num_extra] floats, zeroed by the library */
+    /* scratch for backward, zeroed by the library: one accumulator row per Gaussian, 12 + 4 num_extra floats rounded up to whole 64-byte
+     * lines (16, 16, 32 floats for 0, 1, 2 extra sets; the floats behind the payload are never written).  64-byte aligned:
+     * EMD_ERR_INVALID otherwise.  Its size comes from emd_raster_workspace_size(). */
     void* bwd_ws;  size_t bwd_bytes;
     /* outgoing gradients (NULL = not wanted) */
     float* dL_dmeans3D;           /* [N,3] */
@@ -275,7 +277,7 @@ typedef struct EmdBwdArgs {
                                    * between GPUs instead of 192 */
     const float* settings_dev;    /* as in EmdFwdArgs (same buffer, kept alive by the caller) */
     /* extra colour sets (see EmdFwdArgs): forward inputs / outputs again, incoming and outgoing gradients; bwd_ws then holds
-     * [N, 12 + 4 num_extra] floats (emd_raster_workspace_size with EmdDims.num_extra) */
+     * rows of 12 + 4 num_extra floats at the pitch described there (emd_raster_workspace_size with EmdDims.num_extra) */
     int32_t num_extra;
     const float* colors_extra[EMD_MAX_EXTRA];
     const float* out_extra[EMD_MAX_EXTRA];
