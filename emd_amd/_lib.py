@@ -16,6 +16,7 @@ SETTINGS_DEV_FLOATS = 38
 TILE = 16
 ACTOR_STRIDE = 12
 BWD_PAYLOAD = 12
+SEG_CHUNK = 512          # EMD_SEG_CHUNK: chunk length of the pinned association of the segmented row sum (csrc/segsum.h)
 
 
 def bwd_stride(num_extra=0):
@@ -33,6 +34,7 @@ FLAG_BWD_WS_CLEAN = 256
 FLAG_KEEP_ALL_PAIRS = 512
 FLAG_BWD_RENDER_ONLY = 1024
 FLAG_BWD_PROJECT_ONLY = 2048
+FLAG_DETERMINISTIC = 4096
 
 _f = C.c_void_p  # device pointers are passed as integers
 
@@ -82,7 +84,7 @@ class EmdBwdArgs(C.Structure):
                 ("dL_dcov3D", _f), ("dL_dactor_pose", _f), ("dL_dresidual_dx", _f), ("dL_dresidual_dq", _f),
                 ("dL_dsh_color", _f), ("settings_dev", _f),
                 ("num_extra", C.c_int32), ("colors_extra", _f * 2), ("out_extra", _f * 2), ("dL_dextra", _f * 2), ("dL_dcolors_extra", _f * 2),
-                ("pair_stats", _f)]
+                ("pair_stats", _f), ("det_ws", _f), ("det_bytes", C.c_size_t)]
 
 
 SKY_CLAMP01, SKY_BLEND_S3G, SKY_BLEND_ADD, SKY_INTERLEAVED = 1, 2, 4, 8
@@ -225,6 +227,11 @@ class EmdRadixSortArgs(C.Structure):
                 ("count_out", _f)]
 
 
+class EmdSegSumArgs(C.Structure):
+    _fields_ = [("keys", _f), ("slots", _f), ("n_dev", _f), ("n_cap", C.c_int64), ("rows", _f), ("row_pitch", C.c_int32), ("width", C.c_int32),
+                ("out", _f), ("out_pitch", C.c_int32), ("reserved", C.c_int32), ("partials", _f), ("partial_bytes", C.c_size_t)]
+
+
 # every symbol include/emd_raster.h declares
 EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_size", "emd_raster_forward",
                     "emd_raster_backward", "emd_raster_export_binning", "emd_raster_export_geometry",
@@ -239,7 +246,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_abs_mean_backward", "emd_residual_l1_backward", "emd_tracked_pose_forward", "emd_tracked_pose_backward",
                     "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
                     "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward",
-                    "emd_radix_sort", "emd_camera_grad_workspace_size", "emd_raster_backward_camera")
+                    "emd_radix_sort", "emd_camera_grad_workspace_size", "emd_raster_backward_camera",
+                    "emd_raster_det_workspace_size", "emd_raster_det_layout", "emd_segmented_row_sum_workspace", "emd_segmented_row_sum")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -339,6 +347,11 @@ def load():
     lib.emd_radix_sort.argtypes = [C.POINTER(EmdRadixSortArgs), C.c_void_p]
     lib.emd_camera_grad_workspace_size.argtypes = [C.c_int32, C.POINTER(C.c_size_t)]
     lib.emd_raster_backward_camera.argtypes = [C.POINTER(EmdBwdArgs), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_raster_det_workspace_size.argtypes = [C.POINTER(EmdDims), C.POINTER(C.c_size_t)]
+    lib.emd_raster_det_layout.argtypes = [C.POINTER(EmdDims), C.c_int32, C.POINTER(C.c_size_t)]
+    lib.emd_segmented_row_sum_workspace.argtypes = [C.c_int64, C.c_int32]
+    lib.emd_segmented_row_sum_workspace.restype = C.c_size_t
+    lib.emd_segmented_row_sum.argtypes = [C.POINTER(EmdSegSumArgs), C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p
@@ -381,3 +394,21 @@ def camera_grad_workspace_size(N):
     out = C.c_size_t()
     check(load().emd_camera_grad_workspace_size(int(N), C.byref(out)), "emd_camera_grad_workspace_size")
     return int(out.value)
+
+
+def det_workspace_size(N, capacity, num_extra=0):
+    """Bytes of EmdBwdArgs.det_ws, the workspace of the deterministic backward (emd_raster_det_workspace_size)."""
+    d = EmdDims(int(N), 1, 1, int(capacity), 0, int(num_extra))
+    out = C.c_size_t()
+    check(load().emd_raster_det_workspace_size(C.byref(d), C.byref(out)), "emd_raster_det_workspace_size")
+    return int(out.value)
+
+
+def det_layout(N, capacity, num_extra=0, num_actors=0):
+    """Byte offsets inside det_ws and the result pairs of its two sorts (emd_raster_det_layout): a dict."""
+    d = EmdDims(int(N), 1, 1, int(capacity), 0, int(num_extra))
+    out = (C.c_size_t * 15)()
+    check(load().emd_raster_det_layout(C.byref(d), int(num_actors), out), "emd_raster_det_layout")
+    o = [int(x) for x in out]
+    return dict(rows=o[0], keys=(o[1], o[2]), slots=(o[3], o[4]), counts=o[5], pose_rows=o[6], pose_keys=(o[7], o[8]), pose_points=(o[9], o[10]),
+                sorted_buf=o[11], pose_sorted_buf=o[12], raw_keys=o[13], pose_raw_keys=o[14])

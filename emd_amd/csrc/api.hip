@@ -6,6 +6,8 @@
 #include <string.h>
 
 #include "common.h"
+#include "radix_sort.h"
+#include "segsum.h"
 
 static thread_local char g_err[512] = "";
 
@@ -347,6 +349,21 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     }
     if ((uintptr_t)a->bwd_ws & 63) { emd_set_error("backward: bwd_ws must be 64-byte aligned (an accumulator row is one 64-byte line)"); return EMD_ERR_INVALID; }
     if ((a->flags & EMD_FLAG_ABSGRAD) && !a->dL_dmeans2D_abs) { emd_set_error("backward: EMD_FLAG_ABSGRAD without dL_dmeans2D_abs"); return EMD_ERR_INVALID; }
+    // EMD_FLAG_DETERMINISTIC: no float atomics anywhere in this pass
+    const bool det = (a->flags & EMD_FLAG_DETERMINISTIC) != 0;
+    const size_t det_slots = 4 * (size_t)(a->bin_capacity > 0 ? a->bin_capacity : 1);       // contribution slots: one per quadrant and list entry
+    DetWs dw;
+    memset(&dw, 0, sizeof(dw));
+    if (det) {
+        if (a->pair_stats) { emd_set_error("backward: pair_stats (diagnostic counters of the float atomics) cannot be combined with EMD_FLAG_DETERMINISTIC"); return EMD_ERR_INVALID; }
+        if (det_slots > (size_t)0xFFFFFFFFu - EMD_SORT_TILE) { emd_set_error("backward: EMD_FLAG_DETERMINISTIC: 4 x bin_capacity %lld exceeds 32-bit slot numbers", (long long)a->bin_capacity); return EMD_ERR_INVALID; }
+        emd_carve_det(a->det_ws, N, a->bin_capacity, a->num_extra, &dw);
+        if (!a->det_ws || a->det_bytes < dw.bytes) {
+            emd_set_error("backward: EMD_FLAG_DETERMINISTIC needs det_ws of %zu bytes (emd_raster_det_workspace_size), got %zu", dw.bytes, a->det_ws ? a->det_bytes : (size_t)0);
+            return EMD_ERR_WORKSPACE;
+        }
+        if ((uintptr_t)a->det_ws & 63) { emd_set_error("backward: det_ws must be 64-byte aligned"); return EMD_ERR_INVALID; }
+    }
     const bool dbg = a->s.debug != 0;
     // the two halves of the pass may arrive as two calls (EMD_FLAG_BWD_RENDER_ONLY, then EMD_FLAG_BWD_PROJECT_ONLY on the same workspaces)
     const bool do_render = !(a->flags & EMD_FLAG_BWD_PROJECT_ONLY), do_project = !(a->flags & EMD_FLAG_BWD_RENDER_ONLY);
@@ -374,8 +391,28 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
         }
         rc = emd_launch_render_backward(a->s, a->settings_dev, a->flags, g, b, im, a->out_color, a->out_depth, a->out_normal, a->dL_dcolor,
                                         a->dL_ddepth, a->dL_dalpha, a->dL_dnormal, &ex, (float*)a->bwd_ws, pose_grad, pose_grad_n,
-                                        (unsigned long long*)a->pair_stats, st);
+                                        (unsigned long long*)a->pair_stats, st, det ? dw.part : nullptr);
         if (rc) return rc;
+        if (det) {
+            // every contribution row sits in its survivor's slot: list the slots per Gaussian (a stable sort: ascending slot order inside a Gaussian,
+            // a function of the bit-exact binning alone) and sum each list in the pinned order into the accumulator rows K8 expects
+            rc = emd_launch_det_render_keys(gx * gy, b, a->status, dw.r.keys_in, dw.counts, st);
+            if (rc) return rc;
+            RadixSortArgs rs;
+            rs.keys_in = dw.r.keys_in;
+            for (int i = 0; i < 2; i++) { rs.keys[i] = dw.r.keys[i]; rs.vals[i] = dw.r.vals[i]; }
+            rs.hist = dw.r.hist; rs.n_cap = det_slots; rs.n_dev = dw.counts;
+            rs.passes = emd_det_sort_passes(N); rs.bits = emd_det_sort_bits(N);
+            rs.count_out = dw.counts + 1;
+            const int buf = emd_launch_radix_sort(rs, st);
+            if (buf < 0) return buf;
+            SegSumArgs ss;
+            ss.keys = dw.r.keys[buf]; ss.slots = dw.r.vals[buf]; ss.n_dev = dw.counts + 1; ss.n_cap = det_slots;
+            ss.rows = dw.part; ss.row_pitch = emd_bwd_stride(a->num_extra); ss.width = EMD_BWD_PAYLOAD + 4 * a->num_extra;
+            ss.out = (float*)a->bwd_ws; ss.out_pitch = emd_bwd_stride(a->num_extra); ss.partials = dw.r.partials;
+            rc = emd_launch_segmented_row_sum(ss, st);
+            if (rc) return rc;
+        }
         if (!do_project && a->dL_dsh_color) {      // the SH factor right behind K7: a view-parallel step starts gathering it under K8
             rc = emd_launch_sh_factor(N, a->radii, g, (const float*)a->bwd_ws, emd_bwd_stride(a->num_extra), a->dL_dsh_color, st);
             if (rc) return rc;
@@ -397,11 +434,68 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     pb.sdev = a->settings_dev;
     pb.bwd_stride = emd_bwd_stride(a->num_extra); pb.num_extra = a->num_extra;
     for (int k = 0; k < EMD_MAX_EXTRA; k++) pb.dL_dextra[k] = k < a->num_extra ? a->dL_dcolors_extra[k] : nullptr;
+    const bool det_pose = det && (a->flags & EMD_FLAG_MOTION) && a->dL_dactor_pose && a->motion.num_actors > 0;
+    pb.pose_rows = det_pose ? dw.pose_rows : nullptr;
     if (do_render) emd_prof_switch(PROF_RENDER_BWD, PROF_PREPROCESS_BWD, st); else emd_prof_begin(PROF_PREPROCESS_BWD, st);
     rc = emd_launch_preprocess_backward(pb, st);
+    if (!rc && det_pose && a->motion.actor_id && N > 0) {
+        // K8 stored the pose gradient of every visible actor-bound point: the points by actor (stable: ascending point index), the rows summed in the
+        // pinned order.  Actors without a visible point keep the zeros K7's first workgroup wrote.
+        rc = emd_launch_det_pose_keys(N, a->radii, a->motion.actor_id, dw.p.keys_in, st);
+        if (rc) return rc;
+        RadixSortArgs rs;
+        rs.keys_in = dw.p.keys_in;
+        for (int i = 0; i < 2; i++) { rs.keys[i] = dw.p.keys[i]; rs.vals[i] = dw.p.vals[i]; }
+        rs.hist = dw.p.hist; rs.n_cap = (size_t)N;
+        rs.passes = emd_det_sort_passes(a->motion.num_actors); rs.bits = emd_det_sort_bits(a->motion.num_actors);
+        rs.count_out = dw.counts + 2;
+        const int buf = emd_launch_radix_sort(rs, st);
+        if (buf < 0) return buf;
+        SegSumArgs ss;
+        ss.keys = dw.p.keys[buf]; ss.slots = dw.p.vals[buf]; ss.n_dev = dw.counts + 2; ss.n_cap = (size_t)N;
+        ss.rows = dw.pose_rows; ss.row_pitch = EMD_ACTOR_STRIDE; ss.width = EMD_ACTOR_STRIDE;
+        ss.out = a->dL_dactor_pose; ss.out_pitch = EMD_ACTOR_STRIDE; ss.partials = dw.p.partials;
+        rc = emd_launch_segmented_row_sum(ss, st);
+    }
     emd_prof_end(PROF_PREPROCESS_BWD, st);
     if (rc) return rc;
     STAGE_SYNC("preprocess_backward");
+    return EMD_OK;
+}
+
+static int check_det_dims(const EmdDims* dims, const char* who) {
+    if (!dims) { emd_set_error("%s: null argument", who); return EMD_ERR_INVALID; }
+    if (dims->num_gaussians < 0 || dims->bin_capacity < 0 || dims->num_extra < 0 || dims->num_extra > EMD_MAX_EXTRA) {
+        emd_set_error("%s: bad dims N=%d cap=%lld num_extra=%d", who, dims->num_gaussians, (long long)dims->bin_capacity, dims->num_extra);
+        return EMD_ERR_INVALID;
+    }
+    return EMD_OK;
+}
+
+int emd_raster_det_workspace_size(const EmdDims* dims, size_t* bytes) {
+    int rc = check_det_dims(dims, "det_workspace_size");
+    if (rc) return rc;
+    if (!bytes) { emd_set_error("det_workspace_size: null argument"); return EMD_ERR_INVALID; }
+    DetWs w;
+    emd_carve_det(nullptr, dims->num_gaussians, dims->bin_capacity, dims->num_extra, &w);
+    *bytes = w.bytes;
+    return EMD_OK;
+}
+
+int emd_raster_det_layout(const EmdDims* dims, int32_t num_actors, size_t out[15]) {
+    int rc = check_det_dims(dims, "det_layout");
+    if (rc) return rc;
+    if (!out) { emd_set_error("det_layout: null argument"); return EMD_ERR_INVALID; }
+    DetWs w;
+    emd_carve_det(nullptr, dims->num_gaussians, dims->bin_capacity, dims->num_extra, &w);
+    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
+    out[0] = off(w.part);
+    out[1] = off(w.r.keys[0]); out[2] = off(w.r.keys[1]); out[3] = off(w.r.vals[0]); out[4] = off(w.r.vals[1]);
+    out[5] = off(w.counts); out[6] = off(w.pose_rows);
+    out[7] = off(w.p.keys[0]); out[8] = off(w.p.keys[1]); out[9] = off(w.p.vals[0]); out[10] = off(w.p.vals[1]);
+    out[11] = (size_t)emd_radix_result_buf(true, emd_det_sort_passes(dims->num_gaussians));
+    out[12] = (size_t)emd_radix_result_buf(true, emd_det_sort_passes(num_actors));
+    out[13] = off(w.r.keys_in); out[14] = off(w.p.keys_in);
     return EMD_OK;
 }
 

@@ -135,6 +135,46 @@ static inline void emd_carve_img(void* base, int H, int W, ImgWs* w) {
     w->bytes = off + 256;
 }
 
+// ---- workspace of the deterministic backward (EMD_FLAG_DETERMINISTIC, EmdBwdArgs.det_ws) ------------------------------------------------
+// A sort of n destination ids: ceil(log2 n) key bits in passes of at most nine.
+static inline int emd_det_sort_passes(int64_t n_ids) { const int b = emd_tile_bits((int)(n_ids > 1 ? n_ids : 2)); return (b + 8) / 9; }
+static inline int emd_det_sort_bits(int64_t n_ids) { const int b = emd_tile_bits((int)(n_ids > 1 ? n_ids : 2)), p = emd_det_sort_passes(n_ids); return (b + p - 1) / p; }
+struct DetSortWs {
+    uint32_t* keys_in;       // [n] raw destination ids, 0xFFFFFFFF = no contribution (dropped by the compacting first pass)
+    uint32_t *keys[2], *vals[2];   // [n] ping-pong of the stable sort: destination id, and the slot / point index it came from
+    uint32_t* hist;          // [512][ceil(n / EMD_SORT_TILE)]
+    double* partials;        // chunk sums of the segmented row sum (segsum.h)
+};
+struct DetWs {
+    float* part;             // [4 * capacity][row pitch] contribution rows of the render backward: the survivor's own slot, as BinWs::surv lays them out
+    DetSortWs r;             // n = 4 * capacity slots -> Gaussian ids
+    uint32_t* counts;        // [16] device-side counts: [0] slots in use (4 D)  [1] contributions the render sort kept  [2] points the pose sort kept
+    float* pose_rows;        // [N][EMD_ACTOR_STRIDE] pose gradient of every visible, actor-bound point (K8)
+    DetSortWs p;             // n = N points -> actor ids
+    size_t bytes;
+};
+static inline void emd_carve_det_sort(char* p, size_t& off, size_t n, int width, DetSortWs* w);
+static inline void emd_carve_det(void* base, int N, int64_t capacity, int num_extra, DetWs* w) {
+    char* p = (char*)base;
+    size_t off = 0;
+    const size_t n = (size_t)(N > 0 ? N : 1), R = 4 * (size_t)(capacity > 0 ? capacity : 1);
+    const size_t pitch = (size_t)((EMD_BWD_PAYLOAD + 4 * num_extra + EMD_BWD_PITCH_ALIGN - 1) / EMD_BWD_PITCH_ALIGN * EMD_BWD_PITCH_ALIGN);
+    w->part = (float*)(p + off); off = emd_align_up(off + R * pitch * sizeof(float), 256);
+    emd_carve_det_sort(p, off, R, EMD_BWD_PAYLOAD + 4 * num_extra, &w->r);
+    w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
+    w->pose_rows = (float*)(p + off); off = emd_align_up(off + n * EMD_ACTOR_STRIDE * sizeof(float), 256);
+    emd_carve_det_sort(p, off, n, EMD_ACTOR_STRIDE, &w->p);
+    w->bytes = off + 256;
+}
+static inline void emd_carve_det_sort(char* p, size_t& off, size_t n, int width, DetSortWs* w) {
+    w->keys_in = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);
+    for (int i = 0; i < 2; i++) { w->keys[i] = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256); }
+    for (int i = 0; i < 2; i++) { w->vals[i] = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256); }
+    w->hist = (uint32_t*)(p + off); off = emd_align_up(off + (n + EMD_SORT_TILE - 1) / EMD_SORT_TILE * EMD_DEPTH_BINS_MAX * 4, 256);
+    // (the chunk sums: two per EMD_SEG_CHUNK elements, one lane group of 16 or 32 doubles each -- emd_segsum_partial_bytes of segsum.h)
+    w->partials = (double*)(p + off); off = emd_align_up(off + 2 * ((n + EMD_SEG_CHUNK - 1) / EMD_SEG_CHUNK) * (size_t)(width <= 16 ? 16 : 32) * sizeof(double), 256);
+}
+
 // ---- error plumbing (api.hip) -------------------------------------------------------------------
 void emd_set_error(const char* fmt, ...);
 #define EMD_HIP_CHECK(expr)                                                                          \
@@ -194,7 +234,13 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
                                const float* out_color, const float* out_depth, const float* out_normal,
                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
                                const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
-                               unsigned long long* pair_stats, hipStream_t st);  // render.hip (zero_buf: small table cleared by block 0 for K8)
+                               unsigned long long* pair_stats, hipStream_t st, float* det_part = nullptr);  // render.hip (zero_buf: small table cleared by
+                               // block 0 for K8; det_part: the deterministic variant -- every row STORED to its survivor's slot there, grad_rec untouched)
+// EMD_FLAG_DETERMINISTIC: keys_in[slot] = Gaussian id of the survivor that owns contribution slot `slot` (below 4 D; 0xFFFFFFFF for the survivors
+// the render backward does not walk), *count = 4 D                                                                                     // render.hip
+int emd_launch_det_render_keys(int num_tiles, const BinWs& b, const EmdStatus* status, uint32_t* keys_in, uint32_t* count, hipStream_t st);
+// ... and keys_in[i] = actor id of point i when it is visible and bound to an actor, else 0xFFFFFFFF                                   // preprocess.hip
+int emd_launch_det_pose_keys(int N, const int32_t* radii, const int32_t* actor_id, uint32_t* keys_in, hipStream_t st);
 struct PreBwdArgs {
     EmdSettings s;
     int N, M, flags;
@@ -208,6 +254,8 @@ struct PreBwdArgs {
     float *dL_dmeans3D, *dL_dmeans2D, *dL_dmeans2D_abs, *dL_dshs, *dL_dcolors, *dL_dopacities, *dL_dscales,
         *dL_drotations, *dL_dcov3D, *dL_dactor_pose, *dL_dresidual_dx, *dL_dresidual_dq, *dL_dsh_color;
     const float* sdev;
+    float* pose_rows;       // EMD_FLAG_DETERMINISTIC: [N][EMD_ACTOR_STRIDE], the pose gradient of every visible actor-bound point is STORED here instead of
+                            // being added to dL_dactor_pose with atomics (api.hip sorts the points by actor and sums the rows: segsum.h); else null
 };
 
 // Camera-dependent settings from their device copy (uniform scalar loads), replacing the by-value fields.

@@ -764,7 +764,26 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
         st4(reinterpret_cast<float4*>(a.dL_drotations + 4 * b) + t, s4[O_ROT / 4 + t]);
         if (t < B / 4) st4(reinterpret_cast<float4*>(a.dL_dopacities + b) + t, s4[O_OP / 4 + t]);
     }
-    if ((a.flags & EMD_FLAG_MOTION) && a.dL_dactor_pose) reduce_pose_grad(a_id, pose_g, a.dL_dactor_pose);
+    if ((a.flags & EMD_FLAG_MOTION) && a.dL_dactor_pose) {
+        if (a.pose_rows) {
+            // EMD_FLAG_DETERMINISTIC: the point's own row, summed per actor in a pinned order afterwards (api.hip, segsum.h) -- no atomics
+            if (a_id >= 0) {
+                float4* pr = reinterpret_cast<float4*>(a.pose_rows + (size_t)i * EMD_ACTOR_STRIDE);
+                pr[0] = make_float4(pose_g[0], pose_g[1], pose_g[2], pose_g[3]);
+                pr[1] = make_float4(pose_g[4], pose_g[5], pose_g[6], pose_g[7]);
+                pr[2] = make_float4(pose_g[8], pose_g[9], pose_g[10], pose_g[11]);
+            }
+        } else reduce_pose_grad(a_id, pose_g, a.dL_dactor_pose);
+    }
+}
+
+// EMD_FLAG_DETERMINISTIC: destination of every point's pose row -- its actor when K8 stores one (visible and bound), else dropped by the sort
+__global__ void __launch_bounds__(EMD_BLOCK) k_det_pose_keys(int N, const int32_t* __restrict__ radii, const int32_t* __restrict__ actor_id,
+                                                             uint32_t* __restrict__ keys_in) {
+    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
+    if (i >= N) return;
+    const int a = actor_id[i];
+    keys_in[i] = (radii[i] > 0 && a >= 0) ? (uint32_t)a : 0xFFFFFFFFu;
 }
 
 __global__ void __launch_bounds__(EMD_BLOCK) k_export_geometry(int N, const float4* rec, const uint2* binrec,
@@ -804,6 +823,13 @@ int emd_launch_preprocess_backward(const PreBwdArgs& a, hipStream_t st) {
     if (a.N <= 0) return EMD_OK;
     const int nb = (a.N + K8_BLOCK - 1) / K8_BLOCK;
     hipLaunchKernelGGL(k_preprocess_backward, dim3(nb), dim3(K8_BLOCK), 0, st, a);
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+int emd_launch_det_pose_keys(int N, const int32_t* radii, const int32_t* actor_id, uint32_t* keys_in, hipStream_t st) {
+    if (N <= 0) return EMD_OK;
+    hipLaunchKernelGGL(k_det_pose_keys, dim3((N + EMD_BLOCK - 1) / EMD_BLOCK), dim3(EMD_BLOCK), 0, st, N, radii, actor_id, keys_in);
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }

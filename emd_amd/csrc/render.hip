@@ -347,8 +347,11 @@ __global__ void __launch_bounds__(EMD_WAVE) k_render_forward_q(RenderDims d, con
 // ---------------------------------------------------------------------------------------------------
 #define BQ_QUEUE 128
 
-template <bool NORMAL, bool ABS, int NX, bool STATS = false>
-__global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(NX == 0 ? 4 : NX == 1 ? 3 : 2))) k_render_backward_q(RenderDims d, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ ranges,
+// The body of both K7 kernels.  DET (EMD_FLAG_DETERMINISTIC): everything in front of the flush is the same; the flush STORES each staged row, all
+// STRIDE floats, to the survivor's own slot of `grad_rec` (then the contribution rows DetWs::part, laid out as `surv` is) instead of adding its
+// non-zero floats to the Gaussian's accumulator row: no atomics, every slot the key build of emd_launch_det_render_keys keeps is written exactly once.
+template <bool NORMAL, bool ABS, int NX, bool STATS, bool DET>
+__device__ __forceinline__ void render_backward_body(const RenderDims& d, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ ranges,
                                                                 const uint32_t* __restrict__ surv,
                                                                 const uint32_t* __restrict__ quad_need,
                                                                 const float4* __restrict__ rec,
@@ -544,7 +547,7 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
                     m2xy = m2xy_2.x + m2xy_2.y, m2yy = m2yy_2.x + m2yy_2.y, a_dz = dz_2.x + dz_2.y, a_r = r_2.x + r_2.y,
                     a_g = g_2.x + g_2.y, a_b = b_2.x + b_2.y;
         // rows through LDS so that consecutive lanes add consecutive floats of one accumulator row
-        q_id[lane] = gid;
+        q_id[lane] = DET ? pos : gid;
         float4* row = reinterpret_cast<float4*>(s_stage + lane * STRIDE);
         row[0] = make_float4(-gx, -gy, a_dz, m0 * __builtin_amdgcn_rcpf(g0.w));
         row[1] = make_float4(-0.5f * m2xx, -m2xy, -0.5f * m2yy, a_r);
@@ -570,6 +573,8 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
                     const float val = s_stage[e * STRIDE + v];
                     if (STATS) st_atoms += (unsigned long long)__popcll(__ballot(val != 0.f));
 #ifndef K7_ABL_NO_FLUSH          /* ablation build (profiles/r06_render_ablations.txt): the rows are staged but never added to HBM */
+                    if (DET) grad_rec[(4 * (size_t)start + (size_t)quad * n_tile + q_id[e]) * PITCH + v] = val;        // zeros included: the slot's whole payload
+                    else
                     if (val != 0.f) atomicAdd(grad_rec + (size_t)q_id[e] * PITCH + v, val);
 #else
                     if (val == 12345.678f) grad_rec[0] = val;
@@ -644,6 +649,25 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
     if (STATS && lane == 0) { atomicAdd(pair_stats, st_eval); atomicAdd(pair_stats + 1, st_hit); atomicAdd(pair_stats + 2, st_rows); atomicAdd(pair_stats + 3, st_atoms); }
 }
 
+#define K7_PARAMS                                                                                                                                     \
+    RenderDims d, const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ ranges, const uint32_t *__restrict__ surv,                    \
+        const uint32_t *__restrict__ quad_need, const float4 *__restrict__ rec, const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib, \
+        const float *__restrict__ out_color, const float *__restrict__ out_depth, const float *__restrict__ out_normal, const float *__restrict__ dL_dcolor, \
+        const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, const float *__restrict__ dL_dnormal, float *__restrict__ grad_rec,  \
+        float *__restrict__ zero_buf, int zero_n, unsigned long long *__restrict__ pair_stats
+#define K7_ARGS d, tile_order, ranges, surv, quad_need, rec, final_T, n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, grad_rec, zero_buf, zero_n, pair_stats
+template <bool NORMAL, bool ABS, int NX, bool STATS = false>
+__global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(NX == 0 ? 4 : NX == 1 ? 3 : 2))) k_render_backward_q(K7_PARAMS) {
+    render_backward_body<NORMAL, ABS, NX, STATS, false>(K7_ARGS);
+}
+// the deterministic variant: `grad_rec` is the contribution-row buffer
+template <bool NORMAL, bool ABS, int NX>
+__global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(NX == 0 ? 4 : NX == 1 ? 3 : 2))) k_render_backward_det_q(K7_PARAMS) {
+    render_backward_body<NORMAL, ABS, NX, false, true>(K7_ARGS);
+}
+#undef K7_PARAMS
+#undef K7_ARGS
+
 RenderDims make_dims(const EmdSettings& s, const float* sdev, const EmdExtra* x) {
     RenderDims d;
     d.bg_dev = sdev;
@@ -687,11 +711,15 @@ int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags
     return EMD_OK;
 }
 
+static int launch_render_backward_det(const RenderDims& d, int T, bool nrm, bool ab, int nx, const GeomWs& g, const BinWs& b, const ImgWs& im, const float* out_color,
+                                      const float* out_depth, const float* out_normal, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                                      const float* dL_dnormal, float* det_part, float* zero_buf, int zero_n, hipStream_t st);
+
 int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
                                const float* out_color, const float* out_depth, const float* out_normal,
                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
                                const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
-                               unsigned long long* pair_stats, hipStream_t st) {
+                               unsigned long long* pair_stats, hipStream_t st, float* det_part) {
     const RenderDims d = make_dims(s, sdev, x);
     const int T = d.gx * d.gy;
     if (T <= 0) return EMD_OK;
@@ -706,6 +734,7 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
     else if (nrm) LAUNCH_BWD(true, false, X_);             \
     else if (ab) LAUNCH_BWD(false, true, X_);              \
     else LAUNCH_BWD(false, false, X_)
+    if (det_part) return launch_render_backward_det(d, T, nrm, ab, nx, g, b, im, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, det_part, zero_buf, zero_n, st);
     if (nx == 0 && pair_stats) {          // diagnostic: the same kernel with the pair counters compiled in
         hipLaunchKernelGGL((k_render_backward_q<false, false, 0, true>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv,
                            b.quad_need, g.rec, im.final_T, im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, nullptr, grad_rec,
@@ -716,6 +745,61 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
     else { LAUNCH_BWD_X(2); }
 #undef LAUNCH_BWD_X
 #undef LAUNCH_BWD
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+// EMD_FLAG_DETERMINISTIC: the same walk, every row STORED to its survivor's slot of det_part (api.hip sorts and sums them).  Defined behind the default
+// launcher so that the default kernels are instantiated first: their code objects keep their order (profiles/make_isa_mix.py names loops by it).
+static int launch_render_backward_det(const RenderDims& d, int T, bool nrm, bool ab, int nx, const GeomWs& g, const BinWs& b, const ImgWs& im, const float* out_color,
+                                      const float* out_depth, const float* out_normal, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                                      const float* dL_dnormal, float* det_part, float* zero_buf, int zero_n, hipStream_t st) {
+#define LAUNCH_DET(N_, A_, X_)                                                                                          \
+    hipLaunchKernelGGL((k_render_backward_det_q<N_, A_, X_>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv, b.quad_need, g.rec,   \
+                       im.final_T, im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha,    \
+                       dL_dnormal, det_part, zero_buf, zero_n, nullptr)
+#define LAUNCH_DET_X(X_)                                   \
+    if (nrm && ab) LAUNCH_DET(true, true, X_);             \
+    else if (nrm) LAUNCH_DET(true, false, X_);             \
+    else if (ab) LAUNCH_DET(false, true, X_);              \
+    else LAUNCH_DET(false, false, X_)
+    if (nx == 0) { LAUNCH_DET_X(0); }
+    else if (nx == 1) { LAUNCH_DET_X(1); }
+    else { LAUNCH_DET_X(2); }
+#undef LAUNCH_DET_X
+#undef LAUNCH_DET
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+namespace {
+// EMD_FLAG_DETERMINISTIC: the destination of every contribution slot.  One workgroup per tile: its 4 x n_tile slots start at 4 x the list start; slot
+// quad * n_tile + i belongs to survivor i of the quadrant -- a contribution iff the render backward walks it (i < min(quad_need, n_tile), as K7 reads it).
+// (a template only so that it is emitted behind the kernels above, which keep their positions in the code object)
+template <int UNUSED>
+__global__ void __launch_bounds__(EMD_BLOCK) k_det_render_keys(int T, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ surv,
+                                                               const uint32_t* __restrict__ quad_need, const EmdStatus* __restrict__ status,
+                                                               uint32_t* __restrict__ keys_in, uint32_t* __restrict__ count) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = status->overflow ? 0u : 4u * status->num_rendered;       // (an overflowed call has empty ranges)
+    const uint32_t tile = blockIdx.x;
+    if (tile >= (uint32_t)T) return;
+    const uint32_t start = ranges[2 * tile], n_tile = ranges[2 * tile + 1] - start;
+    if (n_tile == 0) return;
+    const uint32_t need[4] = {min(quad_need[4 * tile], n_tile), min(quad_need[4 * tile + 1], n_tile), min(quad_need[4 * tile + 2], n_tile),
+                              min(quad_need[4 * tile + 3], n_tile)};
+    const size_t base = 4 * (size_t)start;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        for (uint32_t i = threadIdx.x; i < n_tile; i += EMD_BLOCK) {
+            const size_t slot = base + (size_t)q * n_tile + i;
+            keys_in[slot] = i < need[q] ? surv[slot] : 0xFFFFFFFFu;
+        }
+}
+}  // namespace
+
+int emd_launch_det_render_keys(int num_tiles, const BinWs& b, const EmdStatus* status, uint32_t* keys_in, uint32_t* count, hipStream_t st) {
+    hipLaunchKernelGGL(k_det_render_keys<0>, dim3((unsigned)(num_tiles > 0 ? num_tiles : 1)), dim3(EMD_BLOCK), 0, st, num_tiles, b.ranges, b.surv, b.quad_need, status,
+                       keys_in, count);
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }

@@ -79,6 +79,11 @@ class RasterOptions:
                                     # the next call in no_sync mode); a call captured into a hipGraph reads nothing back and keeps the
                                     # flags it was captured with, so scenes with such depths must set this for captured steps (or
                                     # check bit 1 of RasterCall.status after replays: an affected frame renders as background)
+    deterministic: bool = False     # bit-reproducible backward (EMD_FLAG_DETERMINISTIC): every gradient of a call is a fixed function of its inputs --
+                                    # the render backward stores one row per (quadrant, survivor) and a stable sort + a segmented sum with a pinned
+                                    # association replace its float atomics, the actor-pose gradient likewise.  The forward is untouched.  Costs a
+                                    # workspace of 64 B x 4 x capacity and five more launches; emd_amd.nodes' stand-alone motion
+                                    # op, the HexPlane and the sky backward keep their atomics
 
     def replace(self, **kw):
         return dataclasses.replace(self, **{k: v for k, v in kw.items() if v is not None})
@@ -102,11 +107,15 @@ class RasterCall:
     float atomics issued (EmdBwdArgs.pair_stats).
     `loop_stats` (diagnostic; an int64[6] device tensor set by the caller before the call): the compositing kernel adds the trip counts of its scan /
     cull / drain loops (EmdFwdArgs.loop_stats; profiles/render_loop_trips.py).
+    `det_state` (after a deterministic backward with keep_render_grads, else None): views into that call's workspace -- dict(rows=[4 capacity, row pitch]
+    contribution rows of the render backward, keys / slots = the sorted Gaussian ids and contribution slots (int32 views of uint32, full length; the
+    first count[1] are valid), counts = int32[16]: [0] slots in use, [1] contributions kept, [2] actor-bound visible points; pose_rows [N, 12],
+    pose_keys / pose_points = the sorted actor ids and point indices).
     `camera_grad` (after the backward of a call whose camera tensors require grad, else None): the 35 floats dL/d(viewmatrix[16],
     projmatrix[16], campos[3]) of emd_raster_backward_camera; `camera_partials`: that call's per-workgroup rows (the same allocation)."""
     __slots__ = ("status", "num_rendered", "num_visible", "geom_ws", "bin_ws", "img_ws", "sizes", "capacity", "N", "H", "W",
                  "flags", "settings_dev", "absgrad", "sh_color_grad", "grad_slab", "on_backward", "render_grads", "pair_stats",
-                 "status_buffer", "slab_inputs", "on_sh_factor", "radii", "loop_stats", "camera_grad", "camera_partials")
+                 "status_buffer", "slab_inputs", "on_sh_factor", "radii", "loop_stats", "camera_grad", "camera_partials", "det_state")
 
     def __init__(self):
         for k in self.__slots__:
@@ -310,6 +319,17 @@ def camera_inputs(rs):
     return pick(rs.viewmatrix), pick(rs.projmatrix), pick(rs.campos)
 
 
+def _det_views(ws, N, capacity, num_extra, num_actors):
+    """Typed views into the workspace of a deterministic backward (RasterCall.det_state)."""
+    lay = L.det_layout(N, capacity, num_extra, num_actors)
+    R, n, pitch = 4 * max(int(capacity), 1), max(int(N), 1), L.bwd_stride(num_extra)
+    i32 = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32)
+    return dict(rows=ws[lay["rows"]:lay["rows"] + 4 * R * pitch].view(torch.float32).view(R, pitch),
+                keys=i32(lay["keys"][lay["sorted_buf"]], R), slots=i32(lay["slots"][lay["sorted_buf"]], R), counts=i32(lay["counts"], 16),
+                pose_rows=ws[lay["pose_rows"]:lay["pose_rows"] + 4 * n * L.ACTOR_STRIDE].view(torch.float32).view(n, L.ACTOR_STRIDE),
+                pose_keys=i32(lay["pose_keys"][lay["pose_sorted_buf"]], n), pose_points=i32(lay["pose_points"][lay["pose_sorted_buf"]], n))
+
+
 class _Rasterize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, actor_pose,
@@ -484,6 +504,11 @@ class _Rasterize(torch.autograd.Function):
                 bflags = flags | L.FLAG_BWD_WS_CLEAN
         g_extra = [None if g is None else g.contiguous().float() for g in g_extra]
         d_extra = [z(N, 3) for _ in range(nx)]
+        det_ws = None
+        if opts.deterministic:
+            # caller-owned, never cleared: nothing in it is read before the same backward wrote it (a captured step takes it from the graph's pool)
+            bflags |= L.FLAG_DETERMINISTIC
+            det_ws = torch.empty(L.det_workspace_size(N, ctx.capacity, nx), device=dev, dtype=torch.uint8)
 
         b = L.EmdBwdArgs()
         b.s = ctx.cs
@@ -507,6 +532,7 @@ class _Rasterize(torch.autograd.Function):
         b.dL_dactor_pose, b.dL_dresidual_dx, b.dL_dresidual_dq = L.ptr(d_pose), L.ptr(d_rdx), L.ptr(d_rdq)
         b.dL_dsh_color = L.ptr(d_shc)
         b.pair_stats = L.ptr(rec.pair_stats)         # diagnostic: an int64[4] device tensor set on the record before backward(), or None
+        b.det_ws, b.det_bytes = L.ptr(det_ws), (0 if det_ws is None else det_ws.numel())
         b.num_extra = nx
         for k in range(nx):
             b.colors_extra[k], b.out_extra[k] = extras[k].data_ptr(), out_extra[k].data_ptr()
@@ -544,6 +570,8 @@ class _Rasterize(torch.autograd.Function):
         rec.absgrad, rec.sh_color_grad, rec.grad_slab = d_abs, d_shc, slab
         rec.render_grads = bwd_ws.view(max(N, 1), -1) if opts.keep_render_grads else None
         rec.camera_grad, rec.camera_partials = (d_cam, cam_rows) if want_cam else (None, None)
+        rec.det_state = _det_views(det_ws, N, ctx.capacity, nx, 0 if actor_pose is None else int(actor_pose.shape[0])) \
+            if (det_ws is not None and opts.keep_render_grads) else None
         if d_abs is not None and ctx.means2D_ref is not None:
             ctx.means2D_ref.absgrad = d_abs          # what gsplat's backward does with `means2d.absgrad`
         if rec.on_backward is not None:

@@ -57,6 +57,8 @@
 extern "C" {
 #endif
 
+/* (the deterministic backward extends ABI 30 compatibly -- a new flag bit, two fields at the END of EmdBwdArgs that are read only when the flag
+ * is set, new entry points -- so a caller built against the earlier ABI 30 header keeps working and the number stays) */
 #define EMD_ABI_VERSION 30
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
@@ -98,6 +100,11 @@ enum {
     EMD_FLAG_BWD_PROJECT_ONLY = 1 << 11, /* ... and only the projection backward (K8) on the accumulator rows of such a call: the two halves
                                       of one backward as two calls, with whatever the caller enqueues in between (emd_amd.dp: collectives
                                       on the communication stream).  dL_dsh_color is then left alone (pass NULL). */
+    EMD_FLAG_DETERMINISTIC = 1 << 12, /* emd_raster_backward only (ABI 30 extension; the forward ignores it): every output of the backward is a fixed function
+                                      of the call's inputs -- no float atomics.  The render backward stores each (quadrant, survivor) row to its own
+                                      slot of EmdBwdArgs.det_ws, a stable sort lists the slots per Gaussian and a segmented sum with a pinned
+                                      association (EMD_SEG_CHUNK) builds the accumulator rows; the actor-pose gradient goes the same way.  Needs
+                                      det_ws (emd_raster_det_workspace_size) on BOTH halves of a two-call backward; refused together with pair_stats */
     EMD_FLAG_KEEP_ALL_PAIRS = 1 << 9 /* (ABI 21) enumerate every tile of upstream's tile rectangle (the 3-sigma square of the largest
                                       eigenvalue): the sorted keys then ARE upstream's (tile << 32 | depth bits) list, entry for entry.
                                       By default a Gaussian enumerates only the tiles of that rectangle which its alpha >= 1/255 bounding
@@ -288,6 +295,10 @@ typedef struct EmdBwdArgs {
      * to memory as float atomics (one per (quadrant, survivor) with a non-zero entry), [3] float atomics issued.  NULL in production: the counting
      * instantiation of the kernel is only launched when the pointer is set (plain call only: no extra sets / absgrad / dL_dnormal) */
     uint64_t* pair_stats;
+    /* ABI 30 extension, EMD_FLAG_DETERMINISTIC (read ONLY when that flag is set): the workspace of the deterministic backward, emd_raster_det_workspace_size() bytes, 64-byte aligned, caller-owned,
+     * never cleared by anybody (no part of it is read before the same call wrote it).  The same buffer on both halves of a two-call backward.
+     * EMD_ERR_WORKSPACE when the flag is set and it is missing or short, EMD_ERR_INVALID when misaligned. */
+    void* det_ws;  size_t det_bytes;
 } EmdBwdArgs;
 
 /* Per-step inputs of a training step that is replayed from ONE hipGraph (ABI 18).  A captured step reads everything that changes
@@ -327,6 +338,22 @@ int emd_raster_workspace_size(const EmdDims* dims, size_t out[4]);
 
 int emd_raster_forward(EmdFwdArgs* args, void* hip_stream);
 int emd_raster_backward(const EmdBwdArgs* args, void* hip_stream);
+
+/* ---- ABI 30 extension: the deterministic backward (opt-in, EMD_FLAG_DETERMINISTIC) ------------------------------------------------------------
+ * Bytes of EmdBwdArgs.det_ws for dims (num_gaussians N, bin_capacity C, num_extra x).  R = 4 max(C, 1) contribution slots (one per quadrant
+ * and list entry: the worst case; only the slots below 4 D are ever touched), n = max(N, 1), p = the accumulator row pitch in floats
+ * (16, 16, 32 for x = 0, 1, 2), up(b) = b rounded up to 256:
+ *     sort(m, g) = 5 up(4 m) + up(4 * 512 ceil(m / 2048)) + up(8 g * 2 ceil(m / EMD_SEG_CHUNK))
+ *                  raw keys and two ping-pong pairs, the histograms, the fp64 chunk sums of the segmented sum (g doubles each)
+ *     bytes      = up(4 R p) + sort(R, 12 + 4 x <= 16 ? 16 : 32) + up(64) + up(48 n) + sort(n, 16) + 256
+ *                  contribution rows, the render sort, the count words, the [N, 12] pose rows, the pose sort
+ * The layout is emd_carve_det of csrc/common.h.  Nothing in it needs clearing. */
+int emd_raster_det_workspace_size(const EmdDims* dims, size_t* bytes);
+/* Byte offsets inside det_ws, for tests and profiles: [0] contribution rows  [1] / [2] the two key buffers and [3] / [4] the two slot buffers of
+ * the render sort  [5] the count words (uint32: [0] slots in use = 4 D, [1] contributions the sort kept, [2] actor-bound visible points)
+ * [6] the [N, 12] pose rows  [7] / [8] key and [9] / [10] point-index buffers of the pose sort  [13] / [14] the raw keys of the two sorts;
+ * out[11] = which pair (0 / 1) holds the sorted render lists after a backward, out[12] the same for the pose lists with num_actors actors */
+int emd_raster_det_layout(const EmdDims* dims, int32_t num_actors, size_t out[15]);
 
 /* ---- ABI 30: the gradient of the camera (opt-in; camera-pose optimisation) --------------------------------------------------------
  * dL/d(viewmatrix[16], projmatrix[16], campos[3]) of one call, 35 floats laid out as the settings block is (viewmatrix as
@@ -961,6 +988,29 @@ typedef struct EmdRadixSortArgs {
     uint32_t* count_out;
 } EmdRadixSortArgs;
 int emd_radix_sort(const EmdRadixSortArgs* args, void* hip_stream);
+
+/* ---- ABI 30 extension: segmented row sum with a pinned association (csrc/segsum.h), the deterministic stand-in for per-destination float atomics ----
+ * n elements (n = n_cap, or *n_dev <= n_cap when n_dev != NULL) with NON-DECREASING destination ids keys[e] and row indices slots[e].  For every
+ * maximal run of equal keys: out[key * out_pitch + f] = sum over the run of rows[slots[e] * row_pitch + f], f < width.  Destinations without a
+ * run are not written.  The association depends only on the run's length and an element's position in it: consecutive chunks of
+ * EMD_SEG_CHUNK elements, each summed in ascending element order in fp64 from 0.0, the chunk sums added in ascending chunk order in fp64
+ * from 0.0, one rounding to fp32.  `partials`: emd_segmented_row_sum_workspace(n_cap, width) bytes of scratch, 8-byte aligned, needs no clearing.
+ * 1 <= width <= 32, width <= row_pitch, out_pitch; 0 <= n_cap <= 2^32 - 1 - 2048; no host synchronisation, no atomics. */
+#define EMD_SEG_CHUNK 512
+typedef struct EmdSegSumArgs {
+    const uint32_t* keys;
+    const uint32_t* slots;
+    const uint32_t* n_dev;
+    int64_t n_cap;
+    const float* rows;
+    int32_t row_pitch, width;
+    float* out;
+    int32_t out_pitch, reserved;
+    double* partials;
+    size_t partial_bytes;
+} EmdSegSumArgs;
+size_t emd_segmented_row_sum_workspace(int64_t n_cap, int32_t width);
+int emd_segmented_row_sum(const EmdSegSumArgs* args, void* hip_stream);
 
 #ifdef __cplusplus
 }
