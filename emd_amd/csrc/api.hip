@@ -5,9 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.h"
-#include "radix_sort.h"
-#include "segsum.h"
+#include "det_backward.h"
 
 static thread_local char g_err[512] = "";
 
@@ -127,29 +125,64 @@ int emd_zero_async(void* p, size_t bytes, hipStream_t st) {
     return EMD_OK;
 }
 
-int emd_launch_abs_mean_backward(size_t n, const float* x, const float* g, float* out, hipStream_t st);
-int emd_launch_residual_l1_backward(size_t n, const float* up_a, const float* up_b, const float* x_a, const float* x_b, const float* g_a,
-                                    const float* g_b, float* out_a, float* out_b, hipStream_t st);
-int emd_launch_motion_forward(int n, const float* means, const float* quats, const float* opac, const EmdMotion& mo,
-                              float* wm, float* wq, float* wo, hipStream_t st);
-int emd_launch_motion_backward(int n, const float* means, const float* quats, const float* opac, const EmdMotion& mo,
-                               const float* g_wm, const float* g_wq, const float* g_wo, float* d_means, float* d_quats,
-                               float* d_opac, float* d_pose, float* d_rdx, float* d_rdq, hipStream_t st);
-int emd_launch_sh_forward(int n, int deg, int M, const float* dirs, const float* coeffs, float* rgb, hipStream_t st);
-int emd_launch_sh_backward(int n, int deg, int M, const float* dirs, const float* coeffs, const float* g_rgb,
-                           float* d_coeffs, float* d_dirs, hipStream_t st);
-int emd_launch_sh_grad_from_factors(int n, int V, int deg, int M, const float* means, const EmdMotion& mo, int pose_per_view,
-                                    const float* campos, const float* gc, float scale, float* d_shs, hipStream_t st);
-int emd_launch_densification_stats(int n, const int32_t* radii, const float* g2d, float* accum, float* denom, float* max_radii,
-                                   hipStream_t st);
-int emd_launch_actor_pose_forward(int A, const float* q, const float* t, const uint8_t* valid, const float* dt, const float* dq,
-                                  float* pose, const int32_t* frame_dev, hipStream_t st);
-int emd_launch_actor_pose_backward(int A, const float* q, const float* dt, const float* dq, const float* g_pose, float* d_q,
-                                   float* d_t, float* d_dt, float* d_dq, const int32_t* frame_dev, hipStream_t st);
-int emd_launch_l1_loss(size_t n, const float* a, const float* b, float* loss, float* grad, uint32_t* scratch, hipStream_t st);
-int emd_launch_activations(int n, const float* ls, float* sc, const float* rq, float* q, const float* lo, float* o, hipStream_t st);
-int emd_launch_export_geometry(int N, const GeomWs& g, float* means2D, float* depths, float* conic_opacity, float* rgb,
-                               float* normal, uint32_t* tiles_touched, hipStream_t st);
+// debug mode (EmdSettings.debug): a stage's faults are reported under its name
+static int stage_sync(bool dbg, hipStream_t st, const char* name) {
+    if (!dbg) return EMD_OK;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { emd_set_error("stage %s failed: %s", name, hipGetErrorString(e)); return EMD_ERR_HIP; }
+    return EMD_OK;
+}
+
+// The inputs PreArgs (K1) and PreBwdArgs (K8, the camera gradient) share, from the public arguments; the motion block only under EMD_FLAG_MOTION.
+template <class P, class A> static void fill_inputs(P& p, const A& a, const GeomWs& g) {
+    p.s = a.s; p.N = a.num_gaussians; p.M = a.sh_coeffs; p.flags = a.flags;
+    p.means3D = a.means3D; p.shs = a.shs; p.colors_precomp = a.colors_precomp; p.opacities = a.opacities;
+    p.scales = a.scales; p.rotations = a.rotations; p.cov3D_precomp = a.cov3D_precomp;
+    if (a.flags & EMD_FLAG_MOTION) p.motion = a.motion; else memset(&p.motion, 0, sizeof(p.motion));
+    p.radii = a.radii; p.g = g; p.sdev = a.settings_dev;
+}
+static void fill_bwd_inputs(PreBwdArgs& p, const EmdBwdArgs& a, const GeomWs& g) {
+    fill_inputs(p, a, g);
+    p.grad_rec = (float*)a.bwd_ws; p.bwd_stride = emd_bwd_stride(a.num_extra); p.num_extra = a.num_extra;
+}
+
+// What both backward entries need of the forward's state, behind check_common: the pointers, num_extra, the device settings, the sizes of geom_ws and bwd_ws
+// (`rest_fits`: the entry's other workspaces are large enough -- one EMD_ERR_WORKSPACE for all of them), the alignment of the accumulator rows.  Carves g.
+static int check_bwd_state(const EmdBwdArgs* a, const char* who, GeomWs* g, bool rest_fits) {
+    if (!a->radii || !a->geom_ws || !a->bin_ws || !a->img_ws || !a->bwd_ws || !a->status || !a->out_color || !a->out_depth) {
+        emd_set_error("%s: null state pointer", who); return EMD_ERR_INVALID;
+    }
+    if (a->num_extra < 0 || a->num_extra > EMD_MAX_EXTRA) { emd_set_error("%s: num_extra %d not in 0..%d", who, a->num_extra, EMD_MAX_EXTRA); return EMD_ERR_INVALID; }
+    if ((a->flags & EMD_FLAG_SDEV_TANFOV) && !a->settings_dev) { emd_set_error("%s: EMD_FLAG_SDEV_TANFOV without settings_dev", who); return EMD_ERR_INVALID; }
+    emd_carve_geom((void*)a->geom_ws, a->num_gaussians, g);
+    const size_t need = emd_bwd_bytes(a->num_gaussians, a->num_extra);
+    if (g->bytes > a->geom_bytes || need > a->bwd_bytes || !rest_fits) {
+        emd_set_error("%s: workspace too small (geom %zu/%zu bwd %zu/%zu%s)", who, a->geom_bytes, g->bytes, a->bwd_bytes, need, rest_fits ? "" : "; another workspace of the call is short");
+        return EMD_ERR_WORKSPACE;
+    }
+    if ((uintptr_t)a->bwd_ws & 63) { emd_set_error("%s: bwd_ws must be 64-byte aligned (an accumulator row is one 64-byte line)", who); return EMD_ERR_INVALID; }
+    return EMD_OK;
+}
+
+// One reduction of the deterministic backward.  The caller's key-build launch left every row's destination id in w.keys_in (0xFFFFFFFF: no contribution): a
+// stable compacting sort lists the rows per destination -- in ascending row order inside a destination, a function of the bit-exact forward alone -- and
+// every list is summed in the pinned order (segsum.h) into out[destination].  *count_out: the rows the sort kept, on the device.
+static int det_sort_and_sum(const DetSortWs& w, size_t n_cap, int64_t n_ids, const uint32_t* n_dev_in, uint32_t* count_out, const float* rows, int row_pitch,
+                            int width, float* out, int out_pitch, hipStream_t st) {
+    RadixSortArgs rs;
+    rs.keys_in = w.keys_in;
+    for (int i = 0; i < 2; i++) { rs.keys[i] = w.keys[i]; rs.vals[i] = w.vals[i]; }
+    rs.hist = w.hist; rs.n_cap = n_cap; rs.n_dev = n_dev_in;
+    rs.passes = emd_det_sort_passes(n_ids); rs.bits = emd_det_sort_bits(n_ids);
+    rs.count_out = count_out;
+    const int buf = emd_launch_radix_sort(rs, st);
+    if (buf < 0) return buf;
+    SegSumArgs ss;
+    ss.keys = w.keys[buf]; ss.slots = w.vals[buf]; ss.n_dev = count_out; ss.n_cap = n_cap;
+    ss.rows = rows; ss.row_pitch = row_pitch; ss.width = width;
+    ss.out = out; ss.out_pitch = out_pitch; ss.partials = w.partials;
+    return emd_launch_segmented_row_sum(ss, st);
+}
 
 extern "C" {
 
@@ -194,7 +227,7 @@ int emd_raster_workspace_size(const EmdDims* dims, size_t out[4]) {
     emd_carve_img(nullptr, dims->image_height, dims->image_width, &im);
     out[0] = g.bytes; out[1] = b.bytes; out[2] = im.bytes;
     if (dims->num_extra < 0 || dims->num_extra > EMD_MAX_EXTRA) { emd_set_error("workspace_size: num_extra %d not in 0..%d", dims->num_extra, EMD_MAX_EXTRA); return EMD_ERR_INVALID; }
-    out[3] = (size_t)(dims->num_gaussians > 0 ? dims->num_gaussians : 1) * emd_bwd_stride(dims->num_extra) * sizeof(float);
+    out[3] = emd_bwd_bytes(dims->num_gaussians, dims->num_extra);
     return EMD_OK;
 }
 
@@ -247,20 +280,12 @@ int emd_raster_forward(EmdFwdArgs* a, void* hip_stream) {
         return EMD_ERR_WORKSPACE;
     }
     const bool dbg = a->s.debug != 0;
-#define STAGE_SYNC(name)                                                                                     \
-    if (dbg) {                                                                                               \
-        hipError_t e_ = hipStreamSynchronize(st);                                                            \
-        if (e_ != hipSuccess) { emd_set_error("stage %s failed: %s", name, hipGetErrorString(e_)); return EMD_ERR_HIP; } \
-    }
     PreArgs pa;   // (the status word is written by the binning stage)
-    pa.s = a->s; pa.N = N; pa.M = a->sh_coeffs; pa.flags = a->flags;
-    pa.means3D = a->means3D; pa.shs = a->shs; pa.colors_precomp = a->colors_precomp; pa.opacities = a->opacities;
-    pa.scales = a->scales; pa.rotations = a->rotations; pa.cov3D_precomp = a->cov3D_precomp;
-    pa.motion = a->motion; pa.radii = a->radii; pa.g = g; pa.status = a->status; pa.sdev = a->settings_dev;
+    fill_inputs(pa, *a, g);
+    pa.status = a->status;
     pa.shs_res0 = a->shs_residual[0]; pa.shs_res1 = a->shs_residual[1];
     if ((pa.shs_res0 || pa.shs_res1) && !a->shs) { emd_set_error("raster_forward: shs_residual needs shs"); return EMD_ERR_INVALID; }
     if (pa.shs_res1 && !pa.shs_res0) { pa.shs_res0 = pa.shs_res1; pa.shs_res1 = nullptr; }
-    if (!(a->flags & EMD_FLAG_MOTION)) memset(&pa.motion, 0, sizeof(pa.motion));
     emd_prof_begin(PROF_PREPROCESS, st);
     // With an auxiliary stream the colour half of K1 (SH colour, clamp bits, colour Jacobian: needed by K6 only) runs BESIDE the binning
     // stage: fork after the geometry half, join in front of K6.  (Measured in round 3 and OFF by default in the binding: the halves cost
@@ -289,10 +314,10 @@ int emd_raster_forward(EmdFwdArgs* a, void* hip_stream) {
         hipError_t e2 = hipEventRecord(ev_join, aux);
         if (rc || e2 != hipSuccess) { (void)join(); if (!rc) { emd_set_error("forward: hipEventRecord on the auxiliary stream failed"); rc = EMD_ERR_HIP; } return rc; }
     }
-    STAGE_SYNC("preprocess");
+    if ((rc = stage_sync(dbg, st, "preprocess"))) return rc;
     rc = emd_launch_binning(a->s, a->flags, N, g, b, a->bin_capacity, a->status, st);
     if (rc) { (void)join(); return rc; }
-    STAGE_SYNC("binning");
+    if ((rc = stage_sync(dbg, st, "binning"))) return rc;
     a->num_rendered = -1;
     a->num_visible = -1;
     if (!(a->flags & EMD_FLAG_NO_SYNC)) {
@@ -323,8 +348,7 @@ int emd_raster_forward(EmdFwdArgs* a, void* hip_stream) {
                                    (unsigned long long*)a->loop_stats, st);
     emd_prof_end(PROF_RENDER_FWD, st);
     if (rc) return rc;
-    STAGE_SYNC("render_forward");
-    return EMD_OK;
+    return stage_sync(dbg, st, "render_forward");
 }
 
 int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
@@ -334,20 +358,12 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     int rc = check_common(a->s, N, a->sh_coeffs, a->means3D, a->shs, a->colors_precomp, a->opacities, a->scales,
                           a->rotations, a->cov3D_precomp, a->flags, a->motion);
     if (rc) return rc;
-    if (!a->radii || !a->geom_ws || !a->bin_ws || !a->img_ws || !a->bwd_ws || !a->status || !a->out_color || !a->out_depth) {
-        emd_set_error("backward: null state pointer"); return EMD_ERR_INVALID;
-    }
     const int gx = (a->s.image_width + EMD_TILE_X - 1) / EMD_TILE_X, gy = (a->s.image_height + EMD_TILE_Y - 1) / EMD_TILE_Y;
     GeomWs g; BinWs b; ImgWs im;
-    emd_carve_geom((void*)a->geom_ws, N, &g);
     emd_carve_bin((void*)a->bin_ws, a->bin_capacity, gx * gy, &b);
     emd_carve_img((void*)a->img_ws, a->s.image_height, a->s.image_width, &im);
-    if (a->num_extra < 0 || a->num_extra > EMD_MAX_EXTRA) { emd_set_error("backward: num_extra %d not in 0..%d", a->num_extra, EMD_MAX_EXTRA); return EMD_ERR_INVALID; }
-    const size_t need = (size_t)(N > 0 ? N : 1) * emd_bwd_stride(a->num_extra) * sizeof(float);
-    if (g.bytes > a->geom_bytes || b.bytes > a->bin_bytes || im.bytes > a->img_bytes || need > a->bwd_bytes) {
-        emd_set_error("backward: workspace too small"); return EMD_ERR_WORKSPACE;
-    }
-    if ((uintptr_t)a->bwd_ws & 63) { emd_set_error("backward: bwd_ws must be 64-byte aligned (an accumulator row is one 64-byte line)"); return EMD_ERR_INVALID; }
+    rc = check_bwd_state(a, "backward", &g, b.bytes <= a->bin_bytes && im.bytes <= a->img_bytes);
+    if (rc) return rc;
     if ((a->flags & EMD_FLAG_ABSGRAD) && !a->dL_dmeans2D_abs) { emd_set_error("backward: EMD_FLAG_ABSGRAD without dL_dmeans2D_abs"); return EMD_ERR_INVALID; }
     // EMD_FLAG_DETERMINISTIC: no float atomics anywhere in this pass
     const bool det = (a->flags & EMD_FLAG_DETERMINISTIC) != 0;
@@ -370,7 +386,7 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     if (!do_render && !do_project) { emd_set_error("backward: EMD_FLAG_BWD_RENDER_ONLY and EMD_FLAG_BWD_PROJECT_ONLY exclude each other"); return EMD_ERR_INVALID; }
     if (do_render) {
         emd_prof_begin(PROF_OTHER, st);
-        if (!(a->flags & EMD_FLAG_BWD_WS_CLEAN)) { int zrc = emd_zero_async(a->bwd_ws, need, st); if (zrc) return zrc; }
+        if (!(a->flags & EMD_FLAG_BWD_WS_CLEAN)) { int zrc = emd_zero_async(a->bwd_ws, emd_bwd_bytes(N, a->num_extra), st); if (zrc) return zrc; }
         float* pose_grad = nullptr;       // accumulated by K8 with atomics; cleared by K7's first workgroup
         int pose_grad_n = 0;
         if ((a->flags & EMD_FLAG_MOTION) && a->dL_dactor_pose && a->motion.num_actors > 0) {
@@ -391,48 +407,31 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
         }
         rc = emd_launch_render_backward(a->s, a->settings_dev, a->flags, g, b, im, a->out_color, a->out_depth, a->out_normal, a->dL_dcolor,
                                         a->dL_ddepth, a->dL_dalpha, a->dL_dnormal, &ex, (float*)a->bwd_ws, pose_grad, pose_grad_n,
-                                        (unsigned long long*)a->pair_stats, st, det ? dw.part : nullptr);
+                                        (unsigned long long*)a->pair_stats, det ? dw.part : nullptr, st);
         if (rc) return rc;
         if (det) {
             // every contribution row sits in its survivor's slot: list the slots per Gaussian (a stable sort: ascending slot order inside a Gaussian,
             // a function of the bit-exact binning alone) and sum each list in the pinned order into the accumulator rows K8 expects
             rc = emd_launch_det_render_keys(gx * gy, b, a->status, dw.r.keys_in, dw.counts, st);
             if (rc) return rc;
-            RadixSortArgs rs;
-            rs.keys_in = dw.r.keys_in;
-            for (int i = 0; i < 2; i++) { rs.keys[i] = dw.r.keys[i]; rs.vals[i] = dw.r.vals[i]; }
-            rs.hist = dw.r.hist; rs.n_cap = det_slots; rs.n_dev = dw.counts;
-            rs.passes = emd_det_sort_passes(N); rs.bits = emd_det_sort_bits(N);
-            rs.count_out = dw.counts + 1;
-            const int buf = emd_launch_radix_sort(rs, st);
-            if (buf < 0) return buf;
-            SegSumArgs ss;
-            ss.keys = dw.r.keys[buf]; ss.slots = dw.r.vals[buf]; ss.n_dev = dw.counts + 1; ss.n_cap = det_slots;
-            ss.rows = dw.part; ss.row_pitch = emd_bwd_stride(a->num_extra); ss.width = EMD_BWD_PAYLOAD + 4 * a->num_extra;
-            ss.out = (float*)a->bwd_ws; ss.out_pitch = emd_bwd_stride(a->num_extra); ss.partials = dw.r.partials;
-            rc = emd_launch_segmented_row_sum(ss, st);
+            rc = det_sort_and_sum(dw.r, det_slots, N, dw.counts, dw.counts + 1, dw.part, emd_bwd_stride(a->num_extra), EMD_BWD_PAYLOAD + 4 * a->num_extra,
+                                  (float*)a->bwd_ws, emd_bwd_stride(a->num_extra), st);
             if (rc) return rc;
         }
         if (!do_project && a->dL_dsh_color) {      // the SH factor right behind K7: a view-parallel step starts gathering it under K8
             rc = emd_launch_sh_factor(N, a->radii, g, (const float*)a->bwd_ws, emd_bwd_stride(a->num_extra), a->dL_dsh_color, st);
             if (rc) return rc;
         }
-        STAGE_SYNC("render_backward");
+        if ((rc = stage_sync(dbg, st, "render_backward"))) return rc;
         if (!do_project) { emd_prof_end(PROF_RENDER_BWD, st); return EMD_OK; }
     }
     PreBwdArgs pb;
-    pb.s = a->s; pb.N = N; pb.M = a->sh_coeffs; pb.flags = a->flags;
-    pb.means3D = a->means3D; pb.shs = a->shs; pb.colors_precomp = a->colors_precomp; pb.opacities = a->opacities;
-    pb.scales = a->scales; pb.rotations = a->rotations; pb.cov3D_precomp = a->cov3D_precomp;
-    pb.motion = a->motion; pb.radii = a->radii; pb.g = g; pb.grad_rec = (float*)a->bwd_ws;
-    if (!(a->flags & EMD_FLAG_MOTION)) memset(&pb.motion, 0, sizeof(pb.motion));
+    fill_bwd_inputs(pb, *a, g);
     pb.dL_dmeans3D = a->dL_dmeans3D; pb.dL_dmeans2D = a->dL_dmeans2D; pb.dL_dmeans2D_abs = a->dL_dmeans2D_abs;
     pb.dL_dshs = a->dL_dshs; pb.dL_dcolors = a->dL_dcolors; pb.dL_dopacities = a->dL_dopacities;
     pb.dL_dscales = a->dL_dscales; pb.dL_drotations = a->dL_drotations; pb.dL_dcov3D = a->dL_dcov3D;
     pb.dL_dactor_pose = a->dL_dactor_pose; pb.dL_dresidual_dx = a->dL_dresidual_dx; pb.dL_dresidual_dq = a->dL_dresidual_dq;
     pb.dL_dsh_color = a->dL_dsh_color;
-    pb.sdev = a->settings_dev;
-    pb.bwd_stride = emd_bwd_stride(a->num_extra); pb.num_extra = a->num_extra;
     for (int k = 0; k < EMD_MAX_EXTRA; k++) pb.dL_dextra[k] = k < a->num_extra ? a->dL_dcolors_extra[k] : nullptr;
     const bool det_pose = det && (a->flags & EMD_FLAG_MOTION) && a->dL_dactor_pose && a->motion.num_actors > 0;
     pb.pose_rows = det_pose ? dw.pose_rows : nullptr;
@@ -443,24 +442,12 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
         // pinned order.  Actors without a visible point keep the zeros K7's first workgroup wrote.
         rc = emd_launch_det_pose_keys(N, a->radii, a->motion.actor_id, dw.p.keys_in, st);
         if (rc) return rc;
-        RadixSortArgs rs;
-        rs.keys_in = dw.p.keys_in;
-        for (int i = 0; i < 2; i++) { rs.keys[i] = dw.p.keys[i]; rs.vals[i] = dw.p.vals[i]; }
-        rs.hist = dw.p.hist; rs.n_cap = (size_t)N;
-        rs.passes = emd_det_sort_passes(a->motion.num_actors); rs.bits = emd_det_sort_bits(a->motion.num_actors);
-        rs.count_out = dw.counts + 2;
-        const int buf = emd_launch_radix_sort(rs, st);
-        if (buf < 0) return buf;
-        SegSumArgs ss;
-        ss.keys = dw.p.keys[buf]; ss.slots = dw.p.vals[buf]; ss.n_dev = dw.counts + 2; ss.n_cap = (size_t)N;
-        ss.rows = dw.pose_rows; ss.row_pitch = EMD_ACTOR_STRIDE; ss.width = EMD_ACTOR_STRIDE;
-        ss.out = a->dL_dactor_pose; ss.out_pitch = EMD_ACTOR_STRIDE; ss.partials = dw.p.partials;
-        rc = emd_launch_segmented_row_sum(ss, st);
+        rc = det_sort_and_sum(dw.p, (size_t)N, a->motion.num_actors, nullptr, dw.counts + 2, dw.pose_rows, EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, a->dL_dactor_pose,
+                              EMD_ACTOR_STRIDE, st);
     }
     emd_prof_end(PROF_PREPROCESS_BWD, st);
     if (rc) return rc;
-    STAGE_SYNC("preprocess_backward");
-    return EMD_OK;
+    return stage_sync(dbg, st, "preprocess_backward");
 }
 
 static int check_det_dims(const EmdDims* dims, const char* who) {
@@ -512,41 +499,22 @@ int emd_raster_backward_camera(const EmdBwdArgs* a, float* dL_dcamera, void* wor
     int rc = check_common(a->s, N, a->sh_coeffs, a->means3D, a->shs, a->colors_precomp, a->opacities, a->scales,
                           a->rotations, a->cov3D_precomp, a->flags, a->motion);
     if (rc) return rc;
-    if (!a->radii || !a->geom_ws || !a->bin_ws || !a->img_ws || !a->bwd_ws || !a->status || !a->out_color || !a->out_depth) {
-        emd_set_error("backward_camera: null state pointer"); return EMD_ERR_INVALID;
-    }
     if (!dL_dcamera) { emd_set_error("backward_camera: null dL_dcamera"); return EMD_ERR_INVALID; }
     if (a->dL_dnormal) {
         // the normal image depends on the view matrix (nv = V nw and its sign flip): that path has no camera gradient yet -- refused, not left out
         emd_set_error("backward_camera: the camera gradient does not cover the normal image; call without dL_dnormal");
         return EMD_ERR_INVALID;
     }
-    if (a->num_extra < 0 || a->num_extra > EMD_MAX_EXTRA) { emd_set_error("backward_camera: num_extra %d not in 0..%d", a->num_extra, EMD_MAX_EXTRA); return EMD_ERR_INVALID; }
-    if ((a->flags & EMD_FLAG_SDEV_TANFOV) && !a->settings_dev) { emd_set_error("backward_camera: EMD_FLAG_SDEV_TANFOV without settings_dev"); return EMD_ERR_INVALID; }
     GeomWs g;
-    emd_carve_geom((void*)a->geom_ws, N, &g);
-    const size_t need = (size_t)(N > 0 ? N : 1) * emd_bwd_stride(a->num_extra) * sizeof(float);
-    if (g.bytes > a->geom_bytes || need > a->bwd_bytes || !workspace || workspace_bytes < emd_camera_grad_bytes(N)) {
-        emd_set_error("backward_camera: workspace too small (camera %zu/%zu)", workspace_bytes, emd_camera_grad_bytes(N)); return EMD_ERR_WORKSPACE;
-    }
+    rc = check_bwd_state(a, "backward_camera", &g, workspace && workspace_bytes >= emd_camera_grad_bytes(N));
+    if (rc) return rc;
     if ((uintptr_t)workspace & 15) { emd_set_error("backward_camera: workspace must be 16-byte aligned"); return EMD_ERR_INVALID; }
-    if ((uintptr_t)a->bwd_ws & 63) { emd_set_error("backward_camera: bwd_ws must be 64-byte aligned (an accumulator row is one 64-byte line)"); return EMD_ERR_INVALID; }
     PreBwdArgs pb;
     memset(&pb, 0, sizeof(pb));                // (no gradient outputs: the kernel writes the workspace and dL_dcamera only)
-    pb.s = a->s; pb.N = N; pb.M = a->sh_coeffs; pb.flags = a->flags;
-    pb.means3D = a->means3D; pb.shs = a->shs; pb.colors_precomp = a->colors_precomp; pb.opacities = a->opacities;
-    pb.scales = a->scales; pb.rotations = a->rotations; pb.cov3D_precomp = a->cov3D_precomp;
-    if (a->flags & EMD_FLAG_MOTION) pb.motion = a->motion;
-    pb.radii = a->radii; pb.g = g; pb.grad_rec = (float*)a->bwd_ws;
-    pb.sdev = a->settings_dev;
-    pb.bwd_stride = emd_bwd_stride(a->num_extra); pb.num_extra = a->num_extra;
+    fill_bwd_inputs(pb, *a, g);
     rc = emd_launch_camera_backward(pb, (float*)workspace, dL_dcamera, st);
     if (rc) return rc;
-    if (a->s.debug) {
-        hipError_t e_ = hipStreamSynchronize(st);
-        if (e_ != hipSuccess) { emd_set_error("stage camera_backward failed: %s", hipGetErrorString(e_)); return EMD_ERR_HIP; }
-    }
-    return EMD_OK;
+    return stage_sync(a->s.debug != 0, st, "camera_backward");
 }
 
 int emd_raster_export_binning(const EmdDims* dims, const void* geom_ws, size_t geom_bytes, const void* bin_ws, size_t bin_bytes,

@@ -135,46 +135,6 @@ static inline void emd_carve_img(void* base, int H, int W, ImgWs* w) {
     w->bytes = off + 256;
 }
 
-// ---- workspace of the deterministic backward (EMD_FLAG_DETERMINISTIC, EmdBwdArgs.det_ws) ------------------------------------------------
-// A sort of n destination ids: ceil(log2 n) key bits in passes of at most nine.
-static inline int emd_det_sort_passes(int64_t n_ids) { const int b = emd_tile_bits((int)(n_ids > 1 ? n_ids : 2)); return (b + 8) / 9; }
-static inline int emd_det_sort_bits(int64_t n_ids) { const int b = emd_tile_bits((int)(n_ids > 1 ? n_ids : 2)), p = emd_det_sort_passes(n_ids); return (b + p - 1) / p; }
-struct DetSortWs {
-    uint32_t* keys_in;       // [n] raw destination ids, 0xFFFFFFFF = no contribution (dropped by the compacting first pass)
-    uint32_t *keys[2], *vals[2];   // [n] ping-pong of the stable sort: destination id, and the slot / point index it came from
-    uint32_t* hist;          // [512][ceil(n / EMD_SORT_TILE)]
-    double* partials;        // chunk sums of the segmented row sum (segsum.h)
-};
-struct DetWs {
-    float* part;             // [4 * capacity][row pitch] contribution rows of the render backward: the survivor's own slot, as BinWs::surv lays them out
-    DetSortWs r;             // n = 4 * capacity slots -> Gaussian ids
-    uint32_t* counts;        // [16] device-side counts: [0] slots in use (4 D)  [1] contributions the render sort kept  [2] points the pose sort kept
-    float* pose_rows;        // [N][EMD_ACTOR_STRIDE] pose gradient of every visible, actor-bound point (K8)
-    DetSortWs p;             // n = N points -> actor ids
-    size_t bytes;
-};
-static inline void emd_carve_det_sort(char* p, size_t& off, size_t n, int width, DetSortWs* w);
-static inline void emd_carve_det(void* base, int N, int64_t capacity, int num_extra, DetWs* w) {
-    char* p = (char*)base;
-    size_t off = 0;
-    const size_t n = (size_t)(N > 0 ? N : 1), R = 4 * (size_t)(capacity > 0 ? capacity : 1);
-    const size_t pitch = (size_t)((EMD_BWD_PAYLOAD + 4 * num_extra + EMD_BWD_PITCH_ALIGN - 1) / EMD_BWD_PITCH_ALIGN * EMD_BWD_PITCH_ALIGN);
-    w->part = (float*)(p + off); off = emd_align_up(off + R * pitch * sizeof(float), 256);
-    emd_carve_det_sort(p, off, R, EMD_BWD_PAYLOAD + 4 * num_extra, &w->r);
-    w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
-    w->pose_rows = (float*)(p + off); off = emd_align_up(off + n * EMD_ACTOR_STRIDE * sizeof(float), 256);
-    emd_carve_det_sort(p, off, n, EMD_ACTOR_STRIDE, &w->p);
-    w->bytes = off + 256;
-}
-static inline void emd_carve_det_sort(char* p, size_t& off, size_t n, int width, DetSortWs* w) {
-    w->keys_in = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);
-    for (int i = 0; i < 2; i++) { w->keys[i] = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256); }
-    for (int i = 0; i < 2; i++) { w->vals[i] = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256); }
-    w->hist = (uint32_t*)(p + off); off = emd_align_up(off + (n + EMD_SORT_TILE - 1) / EMD_SORT_TILE * EMD_DEPTH_BINS_MAX * 4, 256);
-    // (the chunk sums: two per EMD_SEG_CHUNK elements, one lane group of 16 or 32 doubles each -- emd_segsum_partial_bytes of segsum.h)
-    w->partials = (double*)(p + off); off = emd_align_up(off + 2 * ((n + EMD_SEG_CHUNK - 1) / EMD_SEG_CHUNK) * (size_t)(width <= 16 ? 16 : 32) * sizeof(double), 256);
-}
-
 // ---- error plumbing (api.hip) -------------------------------------------------------------------
 void emd_set_error(const char* fmt, ...);
 #define EMD_HIP_CHECK(expr)                                                                          \
@@ -227,6 +187,8 @@ struct EmdExtra {
 __host__ __device__ constexpr int emd_bwd_stride(int num_extra) {
     return (EMD_BWD_PAYLOAD + 4 * num_extra + EMD_BWD_PITCH_ALIGN - 1) / EMD_BWD_PITCH_ALIGN * EMD_BWD_PITCH_ALIGN;
 }
+// bytes of the accumulator rows of N Gaussians (EmdBwdArgs.bwd_ws; one row when N = 0, as the other workspaces keep one element)
+static inline size_t emd_bwd_bytes(int N, int num_extra) { return (size_t)(N > 0 ? N : 1) * emd_bwd_stride(num_extra) * sizeof(float); }
 int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
                               float* out_color, float* out_depth, float* out_normal, float* out_alpha, const EmdExtra* x,
                               unsigned long long* loop_stats, hipStream_t st);   // render.hip
@@ -234,8 +196,8 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
                                const float* out_color, const float* out_depth, const float* out_normal,
                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
                                const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
-                               unsigned long long* pair_stats, hipStream_t st, float* det_part = nullptr);  // render.hip (zero_buf: small table cleared by
-                               // block 0 for K8; det_part: the deterministic variant -- every row STORED to its survivor's slot there, grad_rec untouched)
+                               unsigned long long* pair_stats, float* det_part, hipStream_t st);  // render.hip (zero_buf: small table cleared by block 0
+                               // for K8; det_part: null, or the deterministic variant -- every row STORED to its survivor's slot there, grad_rec untouched)
 // EMD_FLAG_DETERMINISTIC: keys_in[slot] = Gaussian id of the survivor that owns contribution slot `slot` (below 4 D; 0xFFFFFFFF for the survivors
 // the render backward does not walk), *count = 4 D                                                                                     // render.hip
 int emd_launch_det_render_keys(int num_tiles, const BinWs& b, const EmdStatus* status, uint32_t* keys_in, uint32_t* count, hipStream_t st);
@@ -277,3 +239,29 @@ int emd_launch_sh_factor(int N, const int32_t* radii, const GeomWs& g, const flo
 size_t emd_camera_grad_rows(int N);
 size_t emd_camera_grad_bytes(int N);
 int emd_launch_camera_backward(const PreBwdArgs& a, float* partials, float* dL_dcamera, hipStream_t st);
+
+// ---- launchers behind the stand-alone entry points of api.hip ----------------------------------------------------------------------------
+int emd_launch_export_geometry(int N, const GeomWs& g, float* means2D, float* depths, float* conic_opacity, float* rgb,
+                               float* normal, uint32_t* tiles_touched, hipStream_t st);                                                  // preprocess.hip
+// standalone_ops.hip
+int emd_launch_abs_mean_backward(size_t n, const float* x, const float* g, float* out, hipStream_t st);
+int emd_launch_residual_l1_backward(size_t n, const float* up_a, const float* up_b, const float* x_a, const float* x_b, const float* g_a,
+                                    const float* g_b, float* out_a, float* out_b, hipStream_t st);
+int emd_launch_motion_forward(int n, const float* means, const float* quats, const float* opac, const EmdMotion& mo,
+                              float* wm, float* wq, float* wo, hipStream_t st);
+int emd_launch_motion_backward(int n, const float* means, const float* quats, const float* opac, const EmdMotion& mo,
+                               const float* g_wm, const float* g_wq, const float* g_wo, float* d_means, float* d_quats,
+                               float* d_opac, float* d_pose, float* d_rdx, float* d_rdq, hipStream_t st);
+int emd_launch_sh_forward(int n, int deg, int M, const float* dirs, const float* coeffs, float* rgb, hipStream_t st);
+int emd_launch_sh_backward(int n, int deg, int M, const float* dirs, const float* coeffs, const float* g_rgb,
+                           float* d_coeffs, float* d_dirs, hipStream_t st);
+int emd_launch_sh_grad_from_factors(int n, int V, int deg, int M, const float* means, const EmdMotion& mo, int pose_per_view,
+                                    const float* campos, const float* gc, float scale, float* d_shs, hipStream_t st);
+int emd_launch_densification_stats(int n, const int32_t* radii, const float* g2d, float* accum, float* denom, float* max_radii,
+                                   hipStream_t st);
+int emd_launch_actor_pose_forward(int A, const float* q, const float* t, const uint8_t* valid, const float* dt, const float* dq,
+                                  float* pose, const int32_t* frame_dev, hipStream_t st);
+int emd_launch_actor_pose_backward(int A, const float* q, const float* dt, const float* dq, const float* g_pose, float* d_q,
+                                   float* d_t, float* d_dt, float* d_dq, const int32_t* frame_dev, hipStream_t st);
+int emd_launch_l1_loss(size_t n, const float* a, const float* b, float* loss, float* grad, uint32_t* scratch, hipStream_t st);
+int emd_launch_activations(int n, const float* ls, float* sc, const float* rq, float* q, const float* lo, float* o, hipStream_t st);

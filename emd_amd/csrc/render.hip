@@ -668,115 +668,8 @@ __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(N
 #undef K7_PARAMS
 #undef K7_ARGS
 
-RenderDims make_dims(const EmdSettings& s, const float* sdev, const EmdExtra* x) {
-    RenderDims d;
-    d.bg_dev = sdev;
-    d.W = s.image_width; d.H = s.image_height;
-    d.gx = (d.W + EMD_TILE_X - 1) / EMD_TILE_X; d.gy = (d.H + EMD_TILE_Y - 1) / EMD_TILE_Y;
-    d.bg[0] = s.bg[0]; d.bg[1] = s.bg[1]; d.bg[2] = s.bg[2];
-    for (int k = 0; k < EMD_MAX_EXTRA; k++) {
-        const bool on = x && k < x->num;
-        d.xcol[k] = on ? x->colors[k] : nullptr;
-        d.xout[k] = on ? x->out[k] : nullptr;
-        d.xgrad[k] = on ? x->dL_dout[k] : nullptr;
-    }
-    return d;
-}
-
-}  // namespace
-
-int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
-                              float* out_color, float* out_depth, float* out_normal, float* out_alpha, const EmdExtra* x,
-                              unsigned long long* loop_stats, hipStream_t st) {
-    const RenderDims d = make_dims(s, sdev, x);
-    const int T = d.gx * d.gy;
-    if (T <= 0) return EMD_OK;
-    const uint32_t* pl = b.vals[b.sorted_buf];
-    const int nx = x ? x->num : 0;
-#define LAUNCH_FWD(N_, X_)                                                                                                          \
-    hipLaunchKernelGGL((k_render_forward_q<N_, X_>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, pl, g.rec, \
-                       out_color, out_depth, out_normal, out_alpha, im.final_T, im.n_contrib, b.surv, b.quad_need, nullptr)
-    const bool nrm = (flags & EMD_FLAG_NORMAL) != 0;
-    if (nx == 0 && loop_stats) {          // diagnostic: the same kernel with the loop counters compiled in
-        if (nrm) hipLaunchKernelGGL((k_render_forward_q<true, 0, true>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, pl, g.rec,
-                                    out_color, out_depth, out_normal, out_alpha, im.final_T, im.n_contrib, b.surv, b.quad_need, loop_stats);
-        else hipLaunchKernelGGL((k_render_forward_q<false, 0, true>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, pl, g.rec,
-                                out_color, out_depth, out_normal, out_alpha, im.final_T, im.n_contrib, b.surv, b.quad_need, loop_stats);
-    }
-    else if (nx == 0) { if (nrm) LAUNCH_FWD(true, 0); else LAUNCH_FWD(false, 0); }
-    else if (nx == 1) { if (nrm) LAUNCH_FWD(true, 1); else LAUNCH_FWD(false, 1); }
-    else { if (nrm) LAUNCH_FWD(true, 2); else LAUNCH_FWD(false, 2); }
-#undef LAUNCH_FWD
-    EMD_LAUNCH_CHECK();
-    return EMD_OK;
-}
-
-static int launch_render_backward_det(const RenderDims& d, int T, bool nrm, bool ab, int nx, const GeomWs& g, const BinWs& b, const ImgWs& im, const float* out_color,
-                                      const float* out_depth, const float* out_normal, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                                      const float* dL_dnormal, float* det_part, float* zero_buf, int zero_n, hipStream_t st);
-
-int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
-                               const float* out_color, const float* out_depth, const float* out_normal,
-                               const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                               const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
-                               unsigned long long* pair_stats, hipStream_t st, float* det_part) {
-    const RenderDims d = make_dims(s, sdev, x);
-    const int T = d.gx * d.gy;
-    if (T <= 0) return EMD_OK;
-    const bool nrm = (flags & EMD_FLAG_NORMAL) && dL_dnormal && out_normal, ab = flags & EMD_FLAG_ABSGRAD;
-    const int nx = x ? x->num : 0;
-#define LAUNCH_BWD(N_, A_, X_)                                                                                          \
-    hipLaunchKernelGGL((k_render_backward_q<N_, A_, X_>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv, b.quad_need, g.rec,   \
-                       im.final_T, im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha,    \
-                       dL_dnormal, grad_rec, zero_buf, zero_n, pair_stats)
-#define LAUNCH_BWD_X(X_)                                   \
-    if (nrm && ab) LAUNCH_BWD(true, true, X_);             \
-    else if (nrm) LAUNCH_BWD(true, false, X_);             \
-    else if (ab) LAUNCH_BWD(false, true, X_);              \
-    else LAUNCH_BWD(false, false, X_)
-    if (det_part) return launch_render_backward_det(d, T, nrm, ab, nx, g, b, im, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, det_part, zero_buf, zero_n, st);
-    if (nx == 0 && pair_stats) {          // diagnostic: the same kernel with the pair counters compiled in
-        hipLaunchKernelGGL((k_render_backward_q<false, false, 0, true>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv,
-                           b.quad_need, g.rec, im.final_T, im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, nullptr, grad_rec,
-                           zero_buf, zero_n, pair_stats);
-    }
-    else if (nx == 0) { LAUNCH_BWD_X(0); }
-    else if (nx == 1) { LAUNCH_BWD_X(1); }
-    else { LAUNCH_BWD_X(2); }
-#undef LAUNCH_BWD_X
-#undef LAUNCH_BWD
-    EMD_LAUNCH_CHECK();
-    return EMD_OK;
-}
-
-// EMD_FLAG_DETERMINISTIC: the same walk, every row STORED to its survivor's slot of det_part (api.hip sorts and sums them).  Defined behind the default
-// launcher so that the default kernels are instantiated first: their code objects keep their order (profiles/make_isa_mix.py names loops by it).
-static int launch_render_backward_det(const RenderDims& d, int T, bool nrm, bool ab, int nx, const GeomWs& g, const BinWs& b, const ImgWs& im, const float* out_color,
-                                      const float* out_depth, const float* out_normal, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
-                                      const float* dL_dnormal, float* det_part, float* zero_buf, int zero_n, hipStream_t st) {
-#define LAUNCH_DET(N_, A_, X_)                                                                                          \
-    hipLaunchKernelGGL((k_render_backward_det_q<N_, A_, X_>), dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv, b.quad_need, g.rec,   \
-                       im.final_T, im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha,    \
-                       dL_dnormal, det_part, zero_buf, zero_n, nullptr)
-#define LAUNCH_DET_X(X_)                                   \
-    if (nrm && ab) LAUNCH_DET(true, true, X_);             \
-    else if (nrm) LAUNCH_DET(true, false, X_);             \
-    else if (ab) LAUNCH_DET(false, true, X_);              \
-    else LAUNCH_DET(false, false, X_)
-    if (nx == 0) { LAUNCH_DET_X(0); }
-    else if (nx == 1) { LAUNCH_DET_X(1); }
-    else { LAUNCH_DET_X(2); }
-#undef LAUNCH_DET_X
-#undef LAUNCH_DET
-    EMD_LAUNCH_CHECK();
-    return EMD_OK;
-}
-
-namespace {
 // EMD_FLAG_DETERMINISTIC: the destination of every contribution slot.  One workgroup per tile: its 4 x n_tile slots start at 4 x the list start; slot
 // quad * n_tile + i belongs to survivor i of the quadrant -- a contribution iff the render backward walks it (i < min(quad_need, n_tile), as K7 reads it).
-// (a template only so that it is emitted behind the kernels above, which keep their positions in the code object)
-template <int UNUSED>
 __global__ void __launch_bounds__(EMD_BLOCK) k_det_render_keys(int T, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ surv,
                                                                const uint32_t* __restrict__ quad_need, const EmdStatus* __restrict__ status,
                                                                uint32_t* __restrict__ keys_in, uint32_t* __restrict__ count) {
@@ -795,10 +688,85 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_det_render_keys(int T, const uint
             keys_in[slot] = i < need[q] ? surv[slot] : 0xFFFFFFFFu;
         }
 }
+
+RenderDims make_dims(const EmdSettings& s, const float* sdev, const EmdExtra* x) {
+    RenderDims d;
+    d.bg_dev = sdev;
+    d.W = s.image_width; d.H = s.image_height;
+    d.gx = (d.W + EMD_TILE_X - 1) / EMD_TILE_X; d.gy = (d.H + EMD_TILE_Y - 1) / EMD_TILE_Y;
+    d.bg[0] = s.bg[0]; d.bg[1] = s.bg[1]; d.bg[2] = s.bg[2];
+    for (int k = 0; k < EMD_MAX_EXTRA; k++) {
+        const bool on = x && k < x->num;
+        d.xcol[k] = on ? x->colors[k] : nullptr;
+        d.xout[k] = on ? x->out[k] : nullptr;
+        d.xgrad[k] = on ? x->dL_dout[k] : nullptr;
+    }
+    return d;
+}
+
 }  // namespace
 
+// Runtime flags -> template arguments: f is called with a std::integral_constant of the value.
+template <class F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_nx(int nx, F&& f) {          // extra colour sets: 0, 1, EMD_MAX_EXTRA = 2
+    if (nx == 0) f(std::integral_constant<int, 0>{});
+    else if (nx == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
+
+int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
+                              float* out_color, float* out_depth, float* out_normal, float* out_alpha, const EmdExtra* x,
+                              unsigned long long* loop_stats, hipStream_t st) {
+    const RenderDims d = make_dims(s, sdev, x);
+    const int T = d.gx * d.gy;
+    if (T <= 0) return EMD_OK;
+    const uint32_t* pl = b.vals[b.sorted_buf];
+    auto launch = [&](auto kernel, unsigned long long* stats) {
+        hipLaunchKernelGGL(kernel, dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, pl, g.rec, out_color, out_depth, out_normal,
+                           out_alpha, im.final_T, im.n_contrib, b.surv, b.quad_need, stats);
+    };
+    with_bool((flags & EMD_FLAG_NORMAL) != 0, [&](auto n) { with_nx(x ? x->num : 0, [&](auto xs) {
+        constexpr bool NORMAL = decltype(n)::value;
+        constexpr int NX = decltype(xs)::value;
+        if constexpr (NX == 0) {          // diagnostic: the same kernel with the loop counters compiled in (without extra colour sets only)
+            if (loop_stats) { launch(k_render_forward_q<NORMAL, 0, true>, loop_stats); return; }
+        }
+        launch(k_render_forward_q<NORMAL, NX>, nullptr);
+    }); });
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
+                               const float* out_color, const float* out_depth, const float* out_normal,
+                               const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                               const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
+                               unsigned long long* pair_stats, float* det_part, hipStream_t st) {
+    const RenderDims d = make_dims(s, sdev, x);
+    const int T = d.gx * d.gy;
+    if (T <= 0) return EMD_OK;
+    const bool nrm = (flags & EMD_FLAG_NORMAL) && dL_dnormal && out_normal, ab = flags & EMD_FLAG_ABSGRAD;
+    const int nx = x ? x->num : 0;
+    auto launch = [&](auto kernel, const float* dnormal, float* rows, unsigned long long* stats) {
+        hipLaunchKernelGGL(kernel, dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv, b.quad_need, g.rec, im.final_T,
+                           im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dnormal, rows, zero_buf, zero_n, stats);
+    };
+    if (!det_part && nx == 0 && pair_stats)          // diagnostic: the plain kernel with the pair counters compiled in
+        launch(k_render_backward_q<false, false, 0, true>, nullptr, grad_rec, pair_stats);
+    else
+        with_bool(nrm, [&](auto n) { with_bool(ab, [&](auto a) { with_nx(nx, [&](auto xs) {
+            constexpr bool NORMAL = decltype(n)::value, ABS = decltype(a)::value;
+            constexpr int NX = decltype(xs)::value;
+            // EMD_FLAG_DETERMINISTIC: the same walk, every row STORED to its survivor's slot of det_part (api.hip sorts and sums them), grad_rec untouched
+            if (det_part) launch(k_render_backward_det_q<NORMAL, ABS, NX>, dL_dnormal, det_part, nullptr);
+            else launch(k_render_backward_q<NORMAL, ABS, NX>, dL_dnormal, grad_rec, pair_stats);
+        }); }); });
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
 int emd_launch_det_render_keys(int num_tiles, const BinWs& b, const EmdStatus* status, uint32_t* keys_in, uint32_t* count, hipStream_t st) {
-    hipLaunchKernelGGL(k_det_render_keys<0>, dim3((unsigned)(num_tiles > 0 ? num_tiles : 1)), dim3(EMD_BLOCK), 0, st, num_tiles, b.ranges, b.surv, b.quad_need, status,
+    hipLaunchKernelGGL(k_det_render_keys, dim3((unsigned)(num_tiles > 0 ? num_tiles : 1)), dim3(EMD_BLOCK), 0, st, num_tiles, b.ranges, b.surv, b.quad_need, status,
                        keys_in, count);
     EMD_LAUNCH_CHECK();
     return EMD_OK;

@@ -347,7 +347,7 @@ int emd_raster_backward(const EmdBwdArgs* args, void* hip_stream);
  *                  raw keys and two ping-pong pairs, the histograms, the fp64 chunk sums of the segmented sum (g doubles each)
  *     bytes      = up(4 R p) + sort(R, 12 + 4 x <= 16 ? 16 : 32) + up(64) + up(48 n) + sort(n, 16) + 256
  *                  contribution rows, the render sort, the count words, the [N, 12] pose rows, the pose sort
- * The layout is emd_carve_det of csrc/common.h.  Nothing in it needs clearing. */
+ * The layout is emd_carve_det of csrc/det_backward.h.  Nothing in it needs clearing. */
 int emd_raster_det_workspace_size(const EmdDims* dims, size_t* bytes);
 /* Byte offsets inside det_ws, for tests and profiles: [0] contribution rows  [1] / [2] the two key buffers and [3] / [4] the two slot buffers of
  * the render sort  [5] the count words (uint32: [0] slots in use = 4 D, [1] contributions the sort kept, [2] actor-bound visible points)

@@ -79,13 +79,14 @@ def function_body(lines, mangled_part):
 
 
 def blocks_of(body):
-    """-> [(label, [(op, text)])] in layout order; the entry block is labelled '<entry>'."""
+    """-> [(label, [(op, text)])] in layout order; the entry block is labelled '<entry>'.  Labels lose the function index (.LBB<n>_<m> -> .LBB_<m>, as
+    profiles/compare_kernel_isa.py normalises them): it is the kernel's position in the unit and says nothing about the block."""
     blocks, cur, name = [], [], "<entry>"
     for l in body:
-        s = l.strip()
-        if not s or s.startswith((";", ".")) and not re.match(r"^\.LBB\d+_\d+:", s):
+        s = re.sub(r"\.LBB\d+_", ".LBB_", l.strip())
+        if not s or s.startswith((";", ".")) and not re.match(r"^\.LBB_\d+:", s):
             continue
-        m = re.match(r"^(\.LBB\d+_\d+):", s)
+        m = re.match(r"^(\.LBB_\d+):", s)
         if m:
             blocks.append((name, cur))
             name, cur = m.group(1), []
