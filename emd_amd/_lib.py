@@ -108,6 +108,7 @@ class EmdLossArgs(C.Structure):
                 ("dL_dweight", _f)]
 
 
+HEX_FLAG_DETERMINISTIC = 1
 HEX_MAX_SCALES = 8
 
 
@@ -119,7 +120,8 @@ class EmdHexArgs(C.Structure):
 
 class EmdHexGrads(C.Structure):
     _fields_ = [("dL_dout", _f), ("dL_dplanes", (_f * 6) * HEX_MAX_SCALES), ("dL_dpts", _f), ("dL_dtimes", _f),
-                ("order2d", C.c_void_p * 3), ("pos2d", C.c_void_p * 3), ("defer_rows", _f), ("defer_mask", C.c_uint32), ("reserved", C.c_uint32), ("dL_dtime_sum", _f)]
+                ("order2d", C.c_void_p * 3), ("pos2d", C.c_void_p * 3), ("defer_rows", _f), ("defer_mask", C.c_uint32), ("flags", C.c_uint32), ("dL_dtime_sum", _f),
+                ("det_ws", C.c_void_p), ("det_bytes", C.c_size_t), ("det_keep_plane", C.c_uint32)]       # (read only with HEX_FLAG_DETERMINISTIC)
 
 
 class EmdDeformInArgs(C.Structure):
@@ -247,7 +249,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
                     "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward",
                     "emd_radix_sort", "emd_camera_grad_workspace_size", "emd_raster_backward_camera",
-                    "emd_raster_det_workspace_size", "emd_raster_det_layout", "emd_segmented_row_sum_workspace", "emd_segmented_row_sum")
+                    "emd_raster_det_workspace_size", "emd_raster_det_layout", "emd_segmented_row_sum_workspace", "emd_segmented_row_sum",
+                    "emd_hexplane_det_workspace_size", "emd_hexplane_det_workspace_offsets")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -308,6 +311,8 @@ def load():
                                      C.c_void_p, C.c_void_p]
     lib.emd_hexplane_forward.argtypes = [C.POINTER(EmdHexArgs), C.c_void_p]
     lib.emd_hexplane_backward.argtypes = [C.POINTER(EmdHexArgs), C.POINTER(EmdHexGrads), C.c_void_p]
+    lib.emd_hexplane_det_workspace_size.argtypes = [C.POINTER(EmdHexArgs), C.POINTER(C.c_size_t)]
+    lib.emd_hexplane_det_workspace_offsets.argtypes = [C.POINTER(EmdHexArgs), C.c_int32, C.POINTER(C.c_size_t)]
     lib.emd_hexplane_order_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.emd_temporal_embed_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emd_temporal_embed_backward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
@@ -412,3 +417,18 @@ def det_layout(N, capacity, num_extra=0, num_actors=0):
     o = [int(x) for x in out]
     return dict(rows=o[0], keys=(o[1], o[2]), slots=(o[3], o[4]), counts=o[5], pose_rows=o[6], pose_keys=(o[7], o[8]), pose_points=(o[9], o[10]),
                 sorted_buf=o[11], pose_sorted_buf=o[12], raw_keys=o[13], pose_raw_keys=o[14])
+
+
+def hex_det_workspace_size(args):
+    """Bytes of EmdHexGrads.det_ws for the call described by `args` (an EmdHexArgs: num_points and channels count)."""
+    out = C.c_size_t()
+    check(load().emd_hexplane_det_workspace_size(C.byref(args), C.byref(out)), "emd_hexplane_det_workspace_size")
+    return int(out.value)
+
+
+def hex_det_layout(args, plane):
+    """Byte offsets inside EmdHexGrads.det_ws for plane `plane` = 1 + 6 s + p (emd_hexplane_det_workspace_offsets): a dict."""
+    out = (C.c_size_t * 8)()
+    check(load().emd_hexplane_det_workspace_offsets(C.byref(args), int(plane), out), "emd_hexplane_det_workspace_offsets")
+    o = [int(x) for x in out]
+    return dict(rows=o[0], keys=o[1], slots=o[2], time_column=o[3], raw_keys=o[4], counts=o[5], passes=o[6], bytes=o[7])

@@ -1,0 +1,37 @@
+// hexplane_det.h -- workspace and launcher of the deterministic HexPlane backward (EMD_HEX_FLAG_DETERMINISTIC, EmdHexGrads.det_ws; DESIGN.md section
+// 8.9; hexplane_det.hip): the [4 N][C] contribution rows of ONE plane with the buffers of the stable sort (radix_sort.h) that lists them per texel and
+// of the segmented row sum (segsum.h) that adds each list, reused from plane to plane, and the per-point time column with its one-run sum.
+// include/emd_raster.h states the size formula.
+#pragma once
+#include "det_backward.h"
+
+struct HexDetWs {
+    float* rows;             // [4 N][C] rows of the plane in flight: slot e = k N + n holds tap k of point n
+    DetSortWs r;             // n = 4 N slots -> texels
+    uint32_t* counts;        // [16] device-side counts: [0] slots the sort kept (= 4 N: every slot has a texel)
+    float* tcol;             // [N] dL/dtimes of every point, when only its sum is asked for (EmdHexGrads.dL_dtime_sum)
+    uint32_t *tkeys, *tslots;   // [N] each: one run under key 0, slots 0 .. N - 1
+    double* tpartials;       // chunk sums of that run
+    size_t bytes;
+};
+static inline void emd_carve_hex_det(void* base, int64_t N, int C, HexDetWs* w) {
+    char* p = (char*)base;
+    size_t off = 0;
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    w->rows = (float*)(p + off); off = emd_align_up(off + 4 * n * (size_t)C * sizeof(float), 256);
+    emd_carve_det_sort(p, off, 4 * n, C, &w->r);
+    w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
+    w->tcol = (float*)(p + off); off = emd_align_up(off + n * 4, 256);
+    w->tkeys = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);
+    w->tslots = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);
+    w->tpartials = (double*)(p + off); off = emd_align_up(off + emd_segsum_partial_bytes(n, 1), 256);
+    w->bytes = off + 256;
+}
+// sort passes of plane p of scale s: its W x H texels are the destination ids
+static inline int64_t emd_hex_plane_texels(const EmdHexArgs* a, int s, int p) {
+    const int A_[6] = {0, 0, 0, 1, 1, 2}, B_[6] = {1, 2, 3, 2, 3, 3};
+    return (int64_t)a->res[s][A_[p]] * a->res[s][B_[p]];
+}
+
+// the branch of emd_hexplane_backward behind EMD_HEX_FLAG_DETERMINISTIC (args already through check_hex, num_points > 0)
+int emd_hexplane_backward_det(const EmdHexArgs* a, const EmdHexGrads* g, hipStream_t st);

@@ -54,6 +54,7 @@ class DeformOptions:
         self.apply_coarse_dx = self.apply_final_dx = True
         self.direct_add_dx = self.direct_add_ds = self.direct_add_dr = self.direct_add_do = self.direct_add_dshs = True
         self.no_ds = self.no_dr = self.no_fine_hexplane_features = True          # run_dynamic_nvs.sh
+        self.deterministic = False   # (not a reference option) bit-reproducible HexPlane gradients: HexPlaneField.deterministic
         self.fused_mlp = True        # (not a reference option) trunk + heads on the fused fp32-MFMA kernels of csrc/mlp.hip; False: rocBLAS GEMMs
         for k, v in kw.items():
             setattr(self, k, v)
@@ -223,6 +224,7 @@ class Deformation(nn.Module):
             raise NotImplementedError("grid_pe > 1 is outside the hot-path scope")
         self.D, self.W, self.input_ch, self.input_ch_time, self.skips, self.grid_pe = D, W, input_ch, input_ch_time, list(skips), grid_pe
         self.grid = HexPlaneField(a.bounds, a.kplanes_config, a.multires)
+        self.grid.deterministic = bool(getattr(a, "deterministic", False))
         self.min_embeddings, self.max_embeddings = a.min_embeddings, a.max_embeddings
         self.temporal_embedding_dim, self.gaussian_embedding_dim = a.temporal_embedding_dim, a.gaussian_embedding_dim
         self.c2f_temporal_iter = a.c2f_temporal_iter

@@ -16,10 +16,36 @@ from . import _lib as L
 PAIRS = list(itertools.combinations(range(4), 2))
 
 
+class DeterministicSum:
+    """Travels in `_HexLookup.apply`'s `order` position and switches that call's backward to the deterministic mode (EMD_HEX_FLAG_DETERMINISTIC,
+    DESIGN.md section 8.9): every gradient of the call is a fixed function of its inputs -- no float atomics, per-texel sums in a pinned order.
+    `order`: what the position otherwise holds (None, a permutation, a VisitingOrders record); it serves the forward alone, the backward ignores it.
+    `keep_plane`: None or (scale, plane): the backward processes that plane last and leaves `det_state` on this record -- views into the call's
+    workspace: dict(rows=[4 N, C] contribution rows (slot k N + n: tap k of point n), keys / slots = the sorted texels and slots (int32 views of
+    uint32), raw_keys = the texel of every slot, counts = int32[16] ([0]: slots kept = 4 N), time_column = [N] per-point dL/dtimes (written only for
+    a broadcast timestamp), passes = sort passes of that plane).  Without `keep_plane`, or when no workspace was needed, det_state is None."""
+
+    def __init__(self, keep_plane=None, order=None):
+        self.keep_plane, self.order, self.det_state = keep_plane, order, None
+
+
+def _hex_det_views(ws, args, plane):
+    lay = L.hex_det_layout(args, plane)
+    N, Cc = args.num_points, args.channels
+    i32 = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32)
+    return dict(rows=ws[lay["rows"]:lay["rows"] + 16 * N * Cc].view(torch.float32).view(4 * N, Cc), keys=i32(lay["keys"], 4 * N), slots=i32(lay["slots"], 4 * N),
+                raw_keys=i32(lay["raw_keys"], 4 * N), counts=i32(lay["counts"], 16),
+                time_column=ws[lay["time_column"]:lay["time_column"] + 4 * N].view(torch.float32), passes=lay["passes"])
+
+
 class _HexLookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pts, times, aabb, res, order, *planes):
-        # `order`: None, an int32 permutation, or a VisitingOrders record (the permutation + the per-plane orders of the fine scales)
+        # `order`: None, an int32 permutation, a VisitingOrders record (the permutation + the per-plane orders of the fine scales), or a
+        # DeterministicSum record around one of those (deterministic backward)
+        ctx.det = order if isinstance(order, DeterministicSum) else None
+        if ctx.det is not None:
+            order = ctx.det.order
         plane_orders = order if isinstance(order, VisitingOrders) else None
         if plane_orders is not None:
             order = plane_orders.order
@@ -92,13 +118,24 @@ class _HexLookup(torch.autograd.Function):
                 g.dL_dtimes = d_times.data_ptr()
         po = ctx.keep[4]
         rows = None
-        if po is not None and po.defer_mask and need_planes and a.num_points * Cc * 4 < 2 ** 32:
+        det, det_ws = ctx.det, None
+        if det is not None:
+            # caller-owned, never cleared: nothing in it is read before the same backward wrote it (a captured step takes it from the graph's pool)
+            g.flags = L.HEX_FLAG_DETERMINISTIC
+            if a.num_points > 0 and (need_planes or g.dL_dtime_sum):
+                det_ws = torch.empty(L.hex_det_workspace_size(a), device=g_out.device, dtype=torch.uint8)
+                g.det_ws, g.det_bytes = det_ws.data_ptr(), det_ws.numel()
+                if det.keep_plane is not None:
+                    g.det_keep_plane = 1 + 6 * int(det.keep_plane[0]) + int(det.keep_plane[1])
+        elif po is not None and po.defer_mask and need_planes and a.num_points * Cc * 4 < 2 ** 32:
             for k in range(3):
                 g.order2d[k], g.pos2d[k] = po.order2d[k].data_ptr(), po.pos2d[k].data_ptr()
             rows = torch.empty(bin(po.defer_mask).count("1") * 3 * a.num_points * Cc + 6 * a.num_points, device=g_out.device, dtype=torch.float32)
             g.defer_rows, g.defer_mask = rows.data_ptr(), po.defer_mask
         L.check(lib.emd_hexplane_backward(C.byref(a), C.byref(g), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                 "emd_hexplane_backward")
+        if det is not None:
+            det.det_state = _hex_det_views(det_ws, a, g.det_keep_plane) if (det_ws is not None and g.det_keep_plane) else None
         grads = [t.permute(2, 0, 1)[None] for t in gcl] if need_planes else [None] * len(ctx.shapes)   # channel-last, like the planes
         return (d_pts, d_times, None, None, None, *grads)
 
@@ -201,6 +238,8 @@ class HexPlaneField(nn.Module):
     """S3Gaussian/scene/hexplane.py:112-183"""
     reorder_every = 64        # lookups between refreshes of the cached visiting order (positions drift slowly; any order is correct)
     reorder_min_points = 8192
+    deterministic = False     # bit-reproducible backward: every lookup travels with a DeterministicSum record (DESIGN.md section 8.9)
+    det_keep_plane = None     # with `deterministic`: (scale, plane) whose rows and sorted lists the next backward leaves in `det_state`
 
     def __init__(self, bounds, planeconfig, multires):
         super().__init__()
@@ -253,7 +292,15 @@ class HexPlaneField(nn.Module):
             # the scalar into row 0 and sum N values again -- the column the in-kernel sum (dL_dtime_sum) exists to avoid
             base = getattr(timestamps, "_base", None)
             t = base if (base is not None and tuple(base.shape) == (1, 1) and base.dtype == t.dtype) else t[:1]
-        return _HexLookup.apply(pts, t, self._aabb_host(), self._res, self._visiting_order(pts), *planes)
+        order = self._visiting_order(pts)
+        self._det_record = DeterministicSum(self.det_keep_plane, order) if self.deterministic else None
+        return _HexLookup.apply(pts, t, self._aabb_host(), self._res, self._det_record or order, *planes)
+
+    @property
+    def det_state(self):
+        """`DeterministicSum.det_state` of the latest lookup's backward; None in the default mode (no workspace exists there)."""
+        rec = getattr(self, "_det_record", None)
+        return None if rec is None else rec.det_state
 
     def _visiting_order(self, pts):
         """Morton order of the points, cached across steps: with it 256 consecutive points share plane cells, and the backward

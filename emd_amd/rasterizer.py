@@ -83,7 +83,7 @@ class RasterOptions:
                                     # the render backward stores one row per (quadrant, survivor) and a stable sort + a segmented sum with a pinned
                                     # association replace its float atomics, the actor-pose gradient likewise.  The forward is untouched.  Costs a
                                     # workspace of 64 B x 4 x capacity and five more launches; emd_amd.nodes' stand-alone motion
-                                    # op, the HexPlane and the sky backward keep their atomics
+                                    # op and the sky backward keep their atomics; the HexPlane backward has its own switch (HexPlaneField.deterministic)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **{k: v for k, v in kw.items() if v is not None})

@@ -576,7 +576,7 @@ typedef struct EmdHexArgs {
 
 typedef struct EmdHexGrads {
     const float* dL_dout;                        /* [N, num_scales * C] */
-    float* dL_dplanes[EMD_HEX_MAX_SCALES][6];    /* channel-last like planes; ZEROED BY THE CALLER, accumulated with float atomics; may be NULL */
+    float* dL_dplanes[EMD_HEX_MAX_SCALES][6];    /* channel-last like planes; ZEROED BY THE CALLER, accumulated with float atomics (EMD_HEX_FLAG_DETERMINISTIC: written per texel); may be NULL */
     float* dL_dpts;                              /* [N,3] or NULL */
     float* dL_dtimes;                            /* [N] or NULL (reaches the reference's time_offset parameter, deformation.py:325-328) */
     /* Optional per-plane pass for the fine scales (ABI 19; needs args->order and 16 or 32 channels).  On the scales named by
@@ -590,14 +590,53 @@ typedef struct EmdHexGrads {
     const int32_t* pos2d[3];                     /* [N] each: the inverse permutations, pos2d[p][order2d[p][i]] = i */
     float* defer_rows;                           /* scratch of popcount(defer_mask) * 3 * N * C + 6 * N floats (the rows, then the planes' coordinates); written and read by the call */
     uint32_t defer_mask;                         /* bit s set: the spatial planes of scale s go through the per-plane pass */
-    uint32_t reserved;
+    uint32_t flags;                              /* EMD_HEX_FLAG_*; 0 from every caller that knew the field as `reserved` */
     float* dL_dtime_sum;                         /* (ABI 24) NULL, or one float ZEROED BY THE CALLER that receives sum_n dL/dtimes[n] (float atomics, one per
                                                     workgroup): the gradient of a broadcast timestamp -- S3Gaussian's time_offset parameter,
-                                                    deformation.py:325-328 -- without the [N] gradient and its reduction; used when dL_dtimes is NULL */
+                                                    deformation.py:325-328 -- without the [N] gradient and its reduction; used when dL_dtimes is NULL.
+                                                    With EMD_HEX_FLAG_DETERMINISTIC the call WRITES the float (the pinned sum below) instead of adding to it */
+    /* ABI 30 extension, read only with EMD_HEX_FLAG_DETERMINISTIC (below) */
+    void* det_ws;  size_t det_bytes;             /* emd_hexplane_det_workspace_size() bytes, caller-owned, 256-byte aligned, never cleared; needed when a plane
+                                                    gradient or dL_dtime_sum is asked for */
+    uint32_t det_keep_plane;                     /* 0: none; 1 + 6 s + p: plane p of scale s is processed LAST, so that after the call det_ws still holds its
+                                                    rows, sorted keys and sorted slots (emd_hexplane_det_workspace_offsets).  Changes no output bit: the order
+                                                    in which planes are processed is part of no sum.  For tests and profiles */
 } EmdHexGrads;
 
 int emd_hexplane_forward(const EmdHexArgs* args, void* hip_stream);
 int emd_hexplane_backward(const EmdHexArgs* args, const EmdHexGrads* grads, void* hip_stream);
+
+/* ---- ABI 30 extension: the deterministic HexPlane backward (opt-in, EmdHexGrads.flags) -----------------------------------
+ * With the flag every output of ONE emd_hexplane_backward call -- every dL_dplanes[s][p], dL_dpts, dL_dtimes, dL_dtime_sum -- is a fixed function
+ * of that call's inputs: workgroup scheduling, the stream, other work on the device, eager execution against hipGraph replay have no influence, and
+ * EmdHexArgs.order and EmdHexGrads.order2d / pos2d / defer_rows / defer_mask are ignored.  No float atomics, no LDS adds shared between points.
+ *   Plane (s, p), W x H texels: a CONTRIBUTION is one (point n, tap k) pair, k = 0..3 for the taps (x0,y0), (x1,y0), (x0,y1), (x1,y1).  Its
+ *     destination is the tap's texel y W + x, the clamped neighbour included (at the border x1 == x0: several taps of a point then share a texel
+ *     and stay separate contributions, weight-0 rows included).  Its value is the C-float row gi w_k the default backward would add; every row is
+ *     stored, zeros too (no gi != 0 skip).  A texel's gradient is the sum of its contributions in ascending (k, n) order -- tap-major, then point
+ *     index -- with the association of emd_segmented_row_sum: chunks of EMD_SEG_CHUNK = 512, each summed in fp64 in ascending order from 0.0, the
+ *     chunk sums added in ascending order from 0.0, one rounding to fp32.  Texels without a contribution keep the caller's zeros.
+ *   dL_dpts, dL_dtimes: formed by the point's own C lanes -- over scales, then planes, in registers, then a fixed xor-shuffle tree over the lanes.
+ *   dL_dtime_sum: the emd_segmented_row_sum of the per-point values in ascending n, one run under one key; written, not added to.
+ * Layout: per plane with a gradient, on the caller's stream: a row kernel (lane = channel) stores the four rows of point n at slots e = k N + n of
+ * a [4 N][C] buffer and the texel as key[e]; the stable compacting radix sort lists the slots per texel (ceil(log2(W H)) key bits in passes of at
+ * most nine; stable, so ascending e inside a texel = ascending (k, n)); the segmented row sum writes dL_dplanes[s][p].  The workspace is reused
+ * from plane to plane.  One more launch forms dL_dpts / dL_dtimes / the time column.
+ * Accepts the channel counts of the default path up to 32 (the segmented sum's row width): more is EMD_ERR_INVALID; the flag without a large
+ * enough det_ws is EMD_ERR_WORKSPACE (when a plane gradient or dL_dtime_sum is asked for); both are decided before anything is launched.
+ *
+ * Bytes of det_ws, n = max(num_points, 1), C = channels, g = (C <= 16 ? 16 : 32), up(b) = b rounded up to 256, sort(m, g) as for
+ * emd_raster_det_workspace_size:
+ *     bytes = up(16 n C) + sort(4 n, g) + up(64) + 3 up(4 n) + up(8 * 16 * 2 ceil(n / EMD_SEG_CHUNK)) + 256
+ *             the [4 n][C] rows, the sort and sum of 4 n slots, the count words, the time column with its keys and slots, its chunk sums
+ * The size does not depend on the resolutions: the largest plane of the call decides the number of sort passes only. */
+#define EMD_HEX_FLAG_DETERMINISTIC 1u
+int emd_hexplane_det_workspace_size(const EmdHexArgs* args, size_t* bytes);                 /* host-only: reads num_points and channels */
+/* Byte offsets inside det_ws for plane `plane` = 1 + 6 s + p (the coding of det_keep_plane), for tests and profiles: out[0] the [4 N][C] rows
+ * out[1] / out[2] the key and slot buffers that hold the SORTED lists after that plane's number of sort passes  out[3] the [N] time column
+ * out[4] the raw keys  out[5] the count words (uint32; [0] = slots the sort kept = 4 N)  out[6] = that number of passes (a value, not an offset)
+ * out[7] = the total, as emd_hexplane_det_workspace_size reports it */
+int emd_hexplane_det_workspace_offsets(const EmdHexArgs* args, int32_t plane, size_t out[8]);
 
 /* Sort keys of the visiting orders the aggregating backward is handed (EmdHexArgs.order, EmdHexGrads.order2d): in ONE launch, per point, the
  * 30-bit Z-order key of its box-normalised position (10 bits per axis) -> keys[0 .. N) and the 24-bit HILBERT keys of its (x, y), (x, z),
