@@ -164,26 +164,6 @@ static int check_bwd_state(const EmdBwdArgs* a, const char* who, GeomWs* g, bool
     return EMD_OK;
 }
 
-// One reduction of the deterministic backward.  The caller's key-build launch left every row's destination id in w.keys_in (0xFFFFFFFF: no contribution): a
-// stable compacting sort lists the rows per destination -- in ascending row order inside a destination, a function of the bit-exact forward alone -- and
-// every list is summed in the pinned order (segsum.h) into out[destination].  *count_out: the rows the sort kept, on the device.
-static int det_sort_and_sum(const DetSortWs& w, size_t n_cap, int64_t n_ids, const uint32_t* n_dev_in, uint32_t* count_out, const float* rows, int row_pitch,
-                            int width, float* out, int out_pitch, hipStream_t st) {
-    RadixSortArgs rs;
-    rs.keys_in = w.keys_in;
-    for (int i = 0; i < 2; i++) { rs.keys[i] = w.keys[i]; rs.vals[i] = w.vals[i]; }
-    rs.hist = w.hist; rs.n_cap = n_cap; rs.n_dev = n_dev_in;
-    rs.passes = emd_det_sort_passes(n_ids); rs.bits = emd_det_sort_bits(n_ids);
-    rs.count_out = count_out;
-    const int buf = emd_launch_radix_sort(rs, st);
-    if (buf < 0) return buf;
-    SegSumArgs ss;
-    ss.keys = w.keys[buf]; ss.slots = w.vals[buf]; ss.n_dev = count_out; ss.n_cap = n_cap;
-    ss.rows = rows; ss.row_pitch = row_pitch; ss.width = width;
-    ss.out = out; ss.out_pitch = out_pitch; ss.partials = w.partials;
-    return emd_launch_segmented_row_sum(ss, st);
-}
-
 extern "C" {
 
 int emd_abi_version(void) { return EMD_ABI_VERSION; }
@@ -414,8 +394,8 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
             // a function of the bit-exact binning alone) and sum each list in the pinned order into the accumulator rows K8 expects
             rc = emd_launch_det_render_keys(gx * gy, b, a->status, dw.r.keys_in, dw.counts, st);
             if (rc) return rc;
-            rc = det_sort_and_sum(dw.r, det_slots, N, dw.counts, dw.counts + 1, dw.part, emd_bwd_stride(a->num_extra), EMD_BWD_PAYLOAD + 4 * a->num_extra,
-                                  (float*)a->bwd_ws, emd_bwd_stride(a->num_extra), st);
+            rc = emd_det_sort_and_sum(dw.r, det_slots, N, dw.counts, dw.counts + 1, dw.part, emd_bwd_stride(a->num_extra), EMD_BWD_PAYLOAD + 4 * a->num_extra,
+                                      (float*)a->bwd_ws, emd_bwd_stride(a->num_extra), st);
             if (rc) return rc;
         }
         if (!do_project && a->dL_dsh_color) {      // the SH factor right behind K7: a view-parallel step starts gathering it under K8
@@ -442,8 +422,8 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
         // pinned order.  Actors without a visible point keep the zeros K7's first workgroup wrote.
         rc = emd_launch_det_pose_keys(N, a->radii, a->motion.actor_id, dw.p.keys_in, st);
         if (rc) return rc;
-        rc = det_sort_and_sum(dw.p, (size_t)N, a->motion.num_actors, nullptr, dw.counts + 2, dw.pose_rows, EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, a->dL_dactor_pose,
-                              EMD_ACTOR_STRIDE, st);
+        rc = emd_det_sort_and_sum(dw.p, (size_t)N, a->motion.num_actors, nullptr, dw.counts + 2, dw.pose_rows, EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, a->dL_dactor_pose,
+                                  EMD_ACTOR_STRIDE, st);
     }
     emd_prof_end(PROF_PREPROCESS_BWD, st);
     if (rc) return rc;

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "../../include/emd_raster.h"
 
 #define EMD_WAVE 64
@@ -146,6 +148,18 @@ void emd_set_error(const char* fmt, ...);
         }                                                                                            \
     } while (0)
 #define EMD_LAUNCH_CHECK() EMD_HIP_CHECK(hipGetLastError())
+
+// Runtime flags -> template arguments (host code): f is called with a std::integral_constant of the value and its result is returned, so a launcher
+// nests these around one generic lambda that names the kernel.  with_int serves LO .. HI: values at or below LO take LO, at or above HI take HI.
+template <class F> static auto with_bool(bool b, F&& f) {
+    if (b) return f(std::true_type{});
+    else return f(std::false_type{});
+}
+template <int LO, int HI, class F> static auto with_int(int v, F&& f) {
+    if constexpr (LO == HI) return f(std::integral_constant<int, LO>{});
+    else if (v <= LO) return f(std::integral_constant<int, LO>{});
+    else return with_int<LO + 1, HI>(v, f);
+}
 
 // Zero `bytes` (a multiple of 4, `p` 4-byte aligned) with a KERNEL on `st` (api.hip).  Not hipMemsetAsync: a memset node captured into a
 // hipGraph on ROCm 7.2 / gfx950 replays with a corrupt 16-byte fill pattern from the second replay on (every fourth word of the

@@ -818,8 +818,7 @@ int check_hex(const EmdHexArgs* a, const char* who) {
         for (int p = 0; p < 6; p++) {
             if (!a->planes[s][p]) { emd_set_error("%s: plane %d of scale %d is null", who, p, s); return EMD_ERR_INVALID; }
             if (a->res[s][0] < 1 || a->res[s][1] < 1 || a->res[s][2] < 1 || a->res[s][3] < 1) { emd_set_error("%s: bad resolution", who); return EMD_ERR_INVALID; }
-            const int A_[6] = {0, 0, 0, 1, 1, 2}, B_[6] = {1, 2, 3, 2, 3, 3};
-            if ((int64_t)a->res[s][A_[p]] * a->res[s][B_[p]] * C >= ((int64_t)1 << 30)) {       // the kernels address a plane with 32-bit BYTE offsets
+            if (emd_hex_plane_texels(a, s, p) * C >= ((int64_t)1 << 30)) {       // the kernels address a plane with 32-bit BYTE offsets
                 emd_set_error("%s: plane %d of scale %d holds 2^30 floats or more", who, p, s); return EMD_ERR_INVALID;
             }
         }
@@ -914,10 +913,8 @@ extern "C" int emd_hexplane_backward(const EmdHexArgs* a, const EmdHexGrads* g, 
     // with 32-bit BYTE offsets, so planes of 2^30 floats or more take the direct kernel)
     bool small_planes = true;
     for (int s = 0; s < a->num_scales; s++)
-        for (int p = 0; p < 6; p++) {
-            const int A_[6] = {0, 0, 0, 1, 1, 2}, B_[6] = {1, 2, 3, 2, 3, 3};
-            if ((int64_t)a->res[s][A_[p]] * a->res[s][B_[p]] * a->channels >= ((int64_t)1 << 30)) small_planes = false;
-        }
+        for (int p = 0; p < 6; p++)
+            if (emd_hex_plane_texels(a, s, p) * a->channels >= ((int64_t)1 << 30)) small_planes = false;
     if (a->order && small_planes && a->channels == 32) launch_bwd_agg<32>(a, g, (hipStream_t)hip_stream);
     else if (a->order && small_planes && a->channels == 16) launch_bwd_agg<16>(a, g, (hipStream_t)hip_stream);
     else {

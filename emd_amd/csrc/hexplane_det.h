@@ -1,9 +1,9 @@
 // hexplane_det.h -- workspace and launcher of the deterministic HexPlane backward (EMD_HEX_FLAG_DETERMINISTIC, EmdHexGrads.det_ws; DESIGN.md section
-// 8.9; hexplane_det.hip): the [4 N][C] contribution rows of ONE plane with the buffers of the stable sort (radix_sort.h) that lists them per texel and
-// of the segmented row sum (segsum.h) that adds each list, reused from plane to plane, and the per-point time column with its one-run sum.
+// 8.9; hexplane_det.hip): the [4 N][C] contribution rows of ONE plane with the buffers of the reduction (det_reduce.h) that lists them per texel and
+// adds each list, reused from plane to plane, and the per-point time column with its one-run sum.
 // include/emd_raster.h states the size formula.
 #pragma once
-#include "det_backward.h"
+#include "det_reduce.h"
 
 struct HexDetWs {
     float* rows;             // [4 N][C] rows of the plane in flight: slot e = k N + n holds tap k of point n
@@ -27,7 +27,7 @@ static inline void emd_carve_hex_det(void* base, int64_t N, int C, HexDetWs* w) 
     w->tpartials = (double*)(p + off); off = emd_align_up(off + emd_segsum_partial_bytes(n, 1), 256);
     w->bytes = off + 256;
 }
-// sort passes of plane p of scale s: its W x H texels are the destination ids
+// plane p of scale s spans axes (A_[p], B_[p]): its W x H texels are the destination ids of its sort
 static inline int64_t emd_hex_plane_texels(const EmdHexArgs* a, int s, int p) {
     const int A_[6] = {0, 0, 0, 1, 1, 2}, B_[6] = {1, 2, 3, 2, 3, 3};
     return (int64_t)a->res[s][A_[p]] * a->res[s][B_[p]];

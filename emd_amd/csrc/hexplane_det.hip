@@ -3,8 +3,8 @@
 // workgroups run.  Here every contribution is STORED once, a stable sort lists the contributions per texel in a fixed order, and the segmented row
 // sum adds each list with its pinned association (segsum.h) -- the construction of the deterministic render backward (section 8.8), plane by plane:
 //   k_hexplane_det_rows<P>   lane = channel: the six samples of the scale, gi of plane P, the four weighted rows to slots k N + n, the texels as keys
-//   emd_launch_radix_sort    compacting, stable: slots per texel in ascending slot order = ascending (tap, point)
-//   emd_launch_segmented_row_sum   -> dL_dplanes[s][P]
+//   emd_det_sort_and_sum     (det_reduce.h) the compacting, stable sort: slots per texel in ascending slot order = ascending (tap, point);
+//                            the segmented row sum -> dL_dplanes[s][P]
 // and one k_hexplane_det_points launch for dL_dpts / dL_dtimes / the time column, whose one-run sum is dL_dtime_sum.  No atomics anywhere.
 #include <string.h>
 
@@ -121,39 +121,16 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_hexplane_det_points(EmdHexArgs a,
     }
 }
 
-template <int P>
-void launch_rows(const EmdHexArgs* a, const EmdHexGrads* g, int s, const HexDetWs& w, hipStream_t st) {
-    const int per_block = EMD_BLOCK / a->channels;
-    hipLaunchKernelGGL(k_hexplane_det_rows<P>, dim3((unsigned)((a->num_points + per_block - 1) / per_block)), dim3(EMD_BLOCK), 0, st, *a, g->dL_dout, s,
-                       w.rows, w.r.keys_in);
-}
-
 // rows, sort, sum of one plane
 int det_plane(const EmdHexArgs* a, const EmdHexGrads* g, int s, int p, const HexDetWs& w, hipStream_t st) {
-    switch (p) {
-        case 0: launch_rows<0>(a, g, s, w, st); break;
-        case 1: launch_rows<1>(a, g, s, w, st); break;
-        case 2: launch_rows<2>(a, g, s, w, st); break;
-        case 3: launch_rows<3>(a, g, s, w, st); break;
-        case 4: launch_rows<4>(a, g, s, w, st); break;
-        default: launch_rows<5>(a, g, s, w, st); break;
-    }
+    const int per_block = EMD_BLOCK / a->channels;
+    with_int<0, 5>(p, [&](auto pc) {
+        hipLaunchKernelGGL(k_hexplane_det_rows<decltype(pc)::value>, dim3((unsigned)((a->num_points + per_block - 1) / per_block)), dim3(EMD_BLOCK), 0, st, *a,
+                           g->dL_dout, s, w.rows, w.r.keys_in);
+    });
     EMD_LAUNCH_CHECK();
-    const size_t n4 = 4 * (size_t)a->num_points;
-    const int64_t texels = emd_hex_plane_texels(a, s, p);
-    RadixSortArgs rs;
-    rs.keys_in = w.r.keys_in;
-    for (int i = 0; i < 2; i++) { rs.keys[i] = w.r.keys[i]; rs.vals[i] = w.r.vals[i]; }
-    rs.hist = w.r.hist; rs.n_cap = n4;
-    rs.passes = emd_det_sort_passes(texels); rs.bits = emd_det_sort_bits(texels);
-    rs.count_out = w.counts;
-    const int buf = emd_launch_radix_sort(rs, st);
-    if (buf < 0) return buf;
-    SegSumArgs ss;
-    ss.keys = w.r.keys[buf]; ss.slots = w.r.vals[buf]; ss.n_dev = w.counts; ss.n_cap = n4;
-    ss.rows = w.rows; ss.row_pitch = a->channels; ss.width = a->channels;
-    ss.out = g->dL_dplanes[s][p]; ss.out_pitch = a->channels; ss.partials = w.r.partials;
-    return emd_launch_segmented_row_sum(ss, st);
+    return emd_det_sort_and_sum(w.r, 4 * (size_t)a->num_points, emd_hex_plane_texels(a, s, p), nullptr, w.counts, w.rows, a->channels, a->channels,
+                                g->dL_dplanes[s][p], a->channels, st);
 }
 
 }  // namespace

@@ -1232,48 +1232,25 @@ int mlp_launch(int floats, int num_points, hipStream_t st, Args... args) {
 
 }  // namespace
 
-// the launchers derive the LDS floats, the recomputed-h addend and the workgroups per CU from the kernel's template arguments
-template <int DEPTH, int NTO, bool L1, bool RC>
-int launch_branch_fwd(const EmdMlpBranch* a, hipStream_t st) {
-    typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, false)> L;
-    return mlp_launch<k_mlp_branch_fwd<DEPTH, NTO, L1, RC>, branch_fwd_waves(DEPTH, NTO)>(L::fwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a);
-}
-
+// The entry points turn the runtime shape of a call into the kernel's template arguments (with_bool / with_int: common.h); the LDS floats, the
+// recomputed-h addend and the workgroups per CU follow from those arguments.  A combination the checks refuse or the rules below never choose is
+// pruned with `if constexpr`: no kernel is instantiated for it.
 extern "C" int emd_mlp_branch_forward(const EmdMlpBranch* a, void* hip_stream) {
     int rc = check_branch(a, "mlp_branch_forward");
     if (rc || a->num_points == 0) return rc;
     if (!a->out) { emd_set_error("mlp_branch_forward: null output"); return EMD_ERR_INVALID; }
     hipStream_t st = (hipStream_t)hip_stream;
-    const int nto = a->out_dim > 32 ? 2 : 1;
-    const bool l1 = a->l1_sum != nullptr;
-    if (a->xb) {          // recomputed h: one hidden layer (check_branch)
-        if (nto == 1) return l1 ? launch_branch_fwd<1, 1, true, true>(a, st) : launch_branch_fwd<1, 1, false, true>(a, st);
-        return l1 ? launch_branch_fwd<1, 2, true, true>(a, st) : launch_branch_fwd<1, 2, false, true>(a, st);
-    }
-    if (a->depth == 1) {
-        if (nto == 1) return l1 ? launch_branch_fwd<1, 1, true, false>(a, st) : launch_branch_fwd<1, 1, false, false>(a, st);
-        return l1 ? launch_branch_fwd<1, 2, true, false>(a, st) : launch_branch_fwd<1, 2, false, false>(a, st);
-    }
-    if (nto == 1) return l1 ? launch_branch_fwd<2, 1, true, false>(a, st) : launch_branch_fwd<2, 1, false, false>(a, st);
-    return l1 ? launch_branch_fwd<2, 2, true, false>(a, st) : launch_branch_fwd<2, 2, false, false>(a, st);
-}
-
-template <int DEPTH, int NTO, bool L1, bool RC, int GO, bool CHAIN = false>
-int launch_branch_bwd(const EmdMlpBranch* a, const EmdMlpBranchGrads* g, hipStream_t st) {
-    typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, true)> L;
-    return mlp_launch<k_mlp_branch_bwd<DEPTH, NTO, L1, RC, GO, CHAIN>, branch_bwd_waves>(L::bwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a, *g);
-}
-// one-hidden-layer heads: by output tiles, regulariser, recomputed h, the form dL/dout is loaded in and the chained dL/dh (k_mlp_branch_bwd's GO / CHAIN)
-template <int NTO, bool L1, bool RC>
-int launch_branch_bwd1(const EmdMlpBranch* a, const EmdMlpBranchGrads* g, hipStream_t st) {
-    const bool chain = g->g_h_in != nullptr;
-    if (g->g_out) {
-        if constexpr (NTO == 1) {
-            if (a->out_dim <= 4) return chain ? launch_branch_bwd<1, 1, L1, RC, 0, true>(a, g, st) : launch_branch_bwd<1, 1, L1, RC, 0, false>(a, g, st);
-        }
-        if ((a->out_dim & 3) == 0) return chain ? launch_branch_bwd<1, NTO, L1, RC, 1, true>(a, g, st) : launch_branch_bwd<1, NTO, L1, RC, 1, false>(a, g, st);
-    }
-    return launch_branch_bwd<1, NTO, L1, RC, 2>(a, g, st);
+    return with_int<1, 2>(a->depth, [&](auto d) { return with_int<1, 2>(a->out_dim > 32 ? 2 : 1, [&](auto t) {
+        return with_bool(a->l1_sum != nullptr, [&](auto l) { return with_bool(a->xb != nullptr, [&](auto r) -> int {
+            constexpr int DEPTH = decltype(d)::value, NTO = decltype(t)::value;
+            constexpr bool L1 = decltype(l)::value, RC = decltype(r)::value;
+            if constexpr (DEPTH == 2 && RC) return EMD_ERR_INVALID;          // recomputed h: one hidden layer (check_branch)
+            else {
+                typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, false)> L;
+                return mlp_launch<k_mlp_branch_fwd<DEPTH, NTO, L1, RC>, branch_fwd_waves(DEPTH, NTO)>(L::fwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a);
+            }
+        }); });
+    }); });
 }
 
 extern "C" int emd_mlp_branch_backward(const EmdMlpBranch* a, const EmdMlpBranchGrads* g, void* hip_stream) {
@@ -1289,48 +1266,32 @@ extern "C" int emd_mlp_branch_backward(const EmdMlpBranch* a, const EmdMlpBranch
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const int nto = a->out_dim > 32 ? 2 : 1;
-    const bool l1 = g->l1_grad != nullptr, rcm = a->xb != nullptr;
-    if (a->depth == 1) {
-        if (nto == 1) {
-            if (l1) return rcm ? launch_branch_bwd1<1, true, true>(a, g, st) : launch_branch_bwd1<1, true, false>(a, g, st);
-            return rcm ? launch_branch_bwd1<1, false, true>(a, g, st) : launch_branch_bwd1<1, false, false>(a, g, st);
-        }
-        if (l1) return rcm ? launch_branch_bwd1<2, true, true>(a, g, st) : launch_branch_bwd1<2, true, false>(a, g, st);
-        return rcm ? launch_branch_bwd1<2, false, true>(a, g, st) : launch_branch_bwd1<2, false, false>(a, g, st);
-    }
-    // two hidden layers (the feature head): the raw-load forms where dL/dout allows them (no chained dL/dh: refused above)
-    if (g->g_out && nto == 1 && a->out_dim <= 4)
-        return l1 ? launch_branch_bwd<2, 1, true, false, 0>(a, g, st) : launch_branch_bwd<2, 1, false, false, 0>(a, g, st);
-    if (g->g_out && (a->out_dim & 3) == 0) {
-        if (l1) return nto == 1 ? launch_branch_bwd<2, 1, true, false, 1>(a, g, st) : launch_branch_bwd<2, 2, true, false, 1>(a, g, st);
-        return nto == 1 ? launch_branch_bwd<2, 1, false, false, 1>(a, g, st) : launch_branch_bwd<2, 2, false, false, 1>(a, g, st);
-    }
-    if (l1) return nto == 1 ? launch_branch_bwd<2, 1, true, false, 2>(a, g, st) : launch_branch_bwd<2, 2, true, false, 2>(a, g, st);
-    return nto == 1 ? launch_branch_bwd<2, 1, false, false, 2>(a, g, st) : launch_branch_bwd<2, 2, false, false, 2>(a, g, st);
-}
-
-template <int KTA>
-int launch_trunk_fwd(const EmdMlpTrunk* a, hipStream_t st) {
-    return mlp_launch<k_mlp_trunk_fwd<KTA>, trunk_fwd_waves(KTA)>(TrunkLds<KTA>::fwd_floats, a->num_points, st, *a);
+    // THE rule for k_mlp_branch_bwd's GO / CHAIN.  GO, the form dL/dout is loaded in: 0 for at most four outputs in one tile, 1 for out_dim a multiple of
+    // 4, 2 (guarded loads) otherwise or without g_out.  CHAIN, the chained dL/dh as a template argument: the raw-load forms only (GO 2 tests g_h_in itself).
+    const int go = !g->g_out ? 2 : (nto == 1 && a->out_dim <= 4) ? 0 : (a->out_dim & 3) == 0 ? 1 : 2;
+    const bool chain = g->g_h_in != nullptr && go != 2;
+    return with_int<1, 2>(a->depth, [&](auto d) { return with_int<1, 2>(nto, [&](auto t) { return with_bool(g->l1_grad != nullptr, [&](auto l) {
+        return with_bool(a->xb != nullptr, [&](auto r) { return with_int<0, 2>(go, [&](auto f) { return with_bool(chain, [&](auto c) -> int {
+            constexpr int DEPTH = decltype(d)::value, NTO = decltype(t)::value, GO = decltype(f)::value;
+            constexpr bool L1 = decltype(l)::value, RC = decltype(r)::value, CHAIN = decltype(c)::value;
+            // two hidden layers: neither recomputed h (check_branch) nor g_h_in (above); GO 0 is one tile; GO 2 has no CHAIN form
+            if constexpr ((DEPTH == 2 && (RC || CHAIN)) || (GO == 0 && NTO == 2) || (GO == 2 && CHAIN)) return EMD_ERR_INVALID;
+            else {
+                typedef BranchLds<DEPTH, NTO, branch_mode(DEPTH, NTO, true)> L;
+                return mlp_launch<k_mlp_branch_bwd<DEPTH, NTO, L1, RC, GO, CHAIN>, branch_bwd_waves>(L::bwd_floats + (RC ? L::rc_floats : 0), a->num_points, st, *a, *g);
+            }
+        }); }); });
+    }); }); });
 }
 
 extern "C" int emd_mlp_trunk_forward(const EmdMlpTrunk* a, void* hip_stream) {
     int rc = check_trunk(a, "mlp_trunk_forward");
     if (rc || a->num_points == 0) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    switch ((a->ka + 31) / 32) {            // input tiles of 32 columns (the last one zero-padded)
-        case 0: return launch_trunk_fwd<0>(a, st);
-        case 1: return launch_trunk_fwd<1>(a, st);
-        case 2: return launch_trunk_fwd<2>(a, st);
-        case 3: return launch_trunk_fwd<3>(a, st);
-        default: return launch_trunk_fwd<4>(a, st);
-    }
-}
-
-template <int KTA>
-int launch_trunk_bwd(const EmdMlpTrunk* a, const EmdMlpTrunkGrads* g, hipStream_t st) {
-    if (g->num_gh == 1) return mlp_launch<k_mlp_trunk_bwd<KTA, false>, trunk_bwd_waves(KTA)>(TrunkLds<KTA>::bwd_floats, a->num_points, st, *a, *g);
-    return mlp_launch<k_mlp_trunk_bwd<KTA, true>, trunk_bwd_waves(KTA)>(TrunkLds<KTA>::bwd_floats, a->num_points, st, *a, *g);
+    return with_int<0, 4>((a->ka + 31) / 32, [&](auto k) {            // input tiles of 32 columns (the last one zero-padded)
+        constexpr int KTA = decltype(k)::value;
+        return mlp_launch<k_mlp_trunk_fwd<KTA>, trunk_fwd_waves(KTA)>(TrunkLds<KTA>::fwd_floats, a->num_points, st, *a);
+    });
 }
 
 extern "C" int emd_mlp_trunk_backward(const EmdMlpTrunk* a, const EmdMlpTrunkGrads* g, void* hip_stream) {
@@ -1341,18 +1302,14 @@ extern "C" int emd_mlp_trunk_backward(const EmdMlpTrunk* a, const EmdMlpTrunkGra
         if (!g->g_h[k] || ((uintptr_t)g->g_h[k] & 15)) { emd_set_error("mlp_trunk_backward: g_h[%d] null or unaligned", k); return EMD_ERR_INVALID; }
     if (g->d_xa && ((uintptr_t)g->d_xa & 15)) { emd_set_error("mlp_trunk_backward: d_xa must be 16-byte aligned"); return EMD_ERR_INVALID; }
     hipStream_t st = (hipStream_t)hip_stream;
-    switch ((a->ka + 31) / 32) {
-        case 0:
-            if (a->kb == 4 && !((uintptr_t)a->xb & 15) && !((uintptr_t)g->d_xb & 15)) {     // (the reference's embedding width; static LDS)
-                if (g->num_gh == 1) hipLaunchKernelGGL((k_mlp_embed_bwd<4, false>), dim3(mlp_grid(a->num_points, embed_bwd_waves)), dim3(MLP_THREADS), 0, st, *a, *g);
-                else hipLaunchKernelGGL((k_mlp_embed_bwd<4, true>), dim3(mlp_grid(a->num_points, embed_bwd_waves)), dim3(MLP_THREADS), 0, st, *a, *g);
-                EMD_LAUNCH_CHECK();
-                return EMD_OK;
-            }
-            return launch_trunk_bwd<0>(a, g, st);
-        case 1: return launch_trunk_bwd<1>(a, g, st);
-        case 2: return launch_trunk_bwd<2>(a, g, st);
-        case 3: return launch_trunk_bwd<3>(a, g, st);
-        default: return launch_trunk_bwd<4>(a, g, st);
-    }
+    // the embedding alone, at the reference's width and in whole 16-byte rows: its own kernel (static LDS)
+    const bool embed = a->ka == 0 && a->kb == 4 && !((uintptr_t)a->xb & 15) && !((uintptr_t)g->d_xb & 15);
+    return with_bool(g->num_gh != 1, [&](auto m) {
+        constexpr bool MULTI = decltype(m)::value;
+        if (embed) return mlp_launch<k_mlp_embed_bwd<4, MULTI>, embed_bwd_waves>(0, a->num_points, st, *a, *g);
+        return with_int<0, 4>((a->ka + 31) / 32, [&](auto k) {
+            constexpr int KTA = decltype(k)::value;
+            return mlp_launch<k_mlp_trunk_bwd<KTA, MULTI>, trunk_bwd_waves(KTA)>(TrunkLds<KTA>::bwd_floats, a->num_points, st, *a, *g);
+        });
+    });
 }

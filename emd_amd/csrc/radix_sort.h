@@ -1,5 +1,6 @@
 // radix_sort.h -- stable LSD radix sort of (32-bit key, 32-bit value) pairs on the device (radix_sort.hip).
-// Callers: the depth sort and the tile sort of the binning stage (binning.hip), the Z-order sort and the reverse lists of knn.hip.
+// Callers: the depth sort and the tile sort of the binning stage (binning.hip), the Z-order sort and the reverse lists of knn.hip, and the compacting
+// sort of the deterministic reduction (det_reduce.h: the rasterizer's backward in api.hip, the HexPlane's in hexplane_det.hip).
 #pragma once
 #include "common.h"
 

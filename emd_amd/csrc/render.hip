@@ -19,8 +19,6 @@
 //     lane adds ONE 48-byte row (+16 B per extra colour set) to its Gaussian with global float atomics.
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "common.h"
 #include "device_utils.h"
 #include "footprint.h"
@@ -706,14 +704,6 @@ RenderDims make_dims(const EmdSettings& s, const float* sdev, const EmdExtra* x)
 
 }  // namespace
 
-// Runtime flags -> template arguments: f is called with a std::integral_constant of the value.
-template <class F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <class F> static void with_nx(int nx, F&& f) {          // extra colour sets: 0, 1, EMD_MAX_EXTRA = 2
-    if (nx == 0) f(std::integral_constant<int, 0>{});
-    else if (nx == 1) f(std::integral_constant<int, 1>{});
-    else f(std::integral_constant<int, 2>{});
-}
-
 int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags, const GeomWs& g, const BinWs& b, const ImgWs& im,
                               float* out_color, float* out_depth, float* out_normal, float* out_alpha, const EmdExtra* x,
                               unsigned long long* loop_stats, hipStream_t st) {
@@ -725,7 +715,7 @@ int emd_launch_render_forward(const EmdSettings& s, const float* sdev, int flags
         hipLaunchKernelGGL(kernel, dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, pl, g.rec, out_color, out_depth, out_normal,
                            out_alpha, im.final_T, im.n_contrib, b.surv, b.quad_need, stats);
     };
-    with_bool((flags & EMD_FLAG_NORMAL) != 0, [&](auto n) { with_nx(x ? x->num : 0, [&](auto xs) {
+    with_bool((flags & EMD_FLAG_NORMAL) != 0, [&](auto n) { with_int<0, EMD_MAX_EXTRA>(x ? x->num : 0, [&](auto xs) {
         constexpr bool NORMAL = decltype(n)::value;
         constexpr int NX = decltype(xs)::value;
         if constexpr (NX == 0) {          // diagnostic: the same kernel with the loop counters compiled in (without extra colour sets only)
@@ -754,7 +744,7 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
     if (!det_part && nx == 0 && pair_stats)          // diagnostic: the plain kernel with the pair counters compiled in
         launch(k_render_backward_q<false, false, 0, true>, nullptr, grad_rec, pair_stats);
     else
-        with_bool(nrm, [&](auto n) { with_bool(ab, [&](auto a) { with_nx(nx, [&](auto xs) {
+        with_bool(nrm, [&](auto n) { with_bool(ab, [&](auto a) { with_int<0, EMD_MAX_EXTRA>(nx, [&](auto xs) {
             constexpr bool NORMAL = decltype(n)::value, ABS = decltype(a)::value;
             constexpr int NX = decltype(xs)::value;
             // EMD_FLAG_DETERMINISTIC: the same walk, every row STORED to its survivor's slot of det_part (api.hip sorts and sums them), grad_rec untouched

@@ -1,6 +1,7 @@
 // segsum.h -- segmented row sum with a PINNED association (segsum.hip): the deterministic replacement of "every contribution adds itself to its
-// destination with a float atomic".  Callers: the deterministic render backward (per-Gaussian accumulator rows) and the deterministic actor-pose
-// gradient (api.hip, EMD_FLAG_DETERMINISTIC); the C entry emd_segmented_row_sum (include/emd_raster.h) for the tests.
+// destination with a float atomic".  Callers: the deterministic reduction (det_reduce.h) for the render backward's per-Gaussian accumulator rows and
+// the actor-pose gradient (api.hip, EMD_FLAG_DETERMINISTIC) and for the HexPlane's plane gradients (hexplane_det.hip, EMD_HEX_FLAG_DETERMINISTIC), whose
+// time-column sum calls it directly; the C entry emd_segmented_row_sum (include/emd_raster.h) for the tests.
 //
 // Input: n elements in a fixed order; element e has a destination keys[e] (NON-DECREASING in e) and a row slots[e] of `rows` (row_pitch floats
 // apart, the first `width` of them payload).  A RUN is a maximal range of elements with equal keys.  For every run the launcher writes

@@ -18,8 +18,8 @@ def _net(g, ka, kb, heads):
     return net
 
 
-def _reference(net, xa, xb, kink=None):
-    """`kink` (a list) receives the smallest |pre-activation| per row of every ReLU: a value at its kink (1e-8 happens) makes the float32
+def _reference(net, xa, xb, kink=None, l1_heads=()):
+    """The head outputs followed, as level_mlp returns them, by the regulariser mean |out| of every head in `l1_heads`.  `kink` (a list) receives the smallest |pre-activation| per row of every ReLU: a value at its kink (1e-8 happens) makes the float32
     and float64 masks differ for that row -- a measure-zero disagreement, not an error; the test sends no gradient into such rows."""
     ka = 0 if xa is None else xa.shape[1]
     h = net["b"]
@@ -38,7 +38,7 @@ def _reference(net, xa, xb, kink=None):
                 kink.append(pre.detach().abs().min(dim=1).values)
             x = torch.relu(pre)
         outs.append(x @ wo.t() + bo)
-    return outs
+    return outs + [outs[k].abs().mean() for k in l1_heads]
 
 
 def _leaves(net):
@@ -50,45 +50,75 @@ def _leaves(net):
     return out
 
 
-@pytest.mark.parametrize("N,ka,kb,heads", [
-    (1000, 128, 4, [(True, 1, 3), (True, 1, 1), (True, 1, 48), (False, 2, 3)]),          # the coarse level of the reference configuration
-    (1000, 0, 4, [(True, 1, 3), (True, 1, 1), (True, 1, 48), (False, 2, 3)]),            # its fine level (no HexPlane features)
-    (37, 128, 8, [(True, 1, 4), (False, 1, 64), (True, 2, 33)]),                          # ragged tile, other widths
-    (96, 16, 4, [(True, 1, 3), (True, 1, 3), (True, 1, 4), (True, 1, 1), (True, 1, 48), (False, 2, 3)]),   # the goldens' network: 16 HexPlane features, six heads
-    (500, 72, 5, [(True, 1, 7)]),                                                         # xa ends inside its third tile, odd embedding width
-    (70001, 128, 4, [(True, 1, 3), (True, 1, 48)]),                                       # many tiles per wave
+# One-hidden-layer forms by out_dim -- 3: at most four outputs (GO 0), 8: 16-byte pieces in one tile (GO 1), 7: guarded loads (GO 2), 48 / 64: two tiles
+# of 16-byte pieces, 33: two guarded tiles -- in three orders: the first head of a level writes dL/dh, every later one-hidden-layer head chains onto it.
+_ORDER_3 = [(True, 1, 3), (True, 1, 8), (False, 1, 48), (True, 1, 7), (True, 1, 33), (True, 1, 64)]
+_ORDER_8 = [(True, 1, 8), (True, 1, 64), (True, 1, 3), (False, 1, 33), (True, 1, 7), (True, 1, 48)]
+_ORDER_64 = [(False, 1, 64), (True, 1, 7), (True, 1, 33), (True, 1, 3), (True, 1, 8), (True, 1, 48)]
+# ... and the same forms with two hidden layers (no chaining, no recomputed h), around one chained one-hidden-layer head
+_DEEP = [(False, 2, 3), (True, 2, 8), (False, 2, 64), (True, 1, 48), (False, 2, 7), (True, 2, 33)]
+_ALL = (0, 1, 2, 3, 4, 5)
+
+
+def _case(N, ka, kb, heads, l1_heads=(), seed=None):
+    return (N, ka, kb, heads, l1_heads, N + ka + kb if seed is None else seed)
+
+
+@pytest.mark.parametrize("N,ka,kb,heads,l1_heads,seed", [
+    _case(1000, 128, 4, [(True, 1, 3), (True, 1, 1), (True, 1, 48), (False, 2, 3)]),          # the coarse level of the reference configuration
+    _case(1000, 0, 4, [(True, 1, 3), (True, 1, 1), (True, 1, 48), (False, 2, 3)]),            # its fine level (no HexPlane features)
+    _case(37, 128, 8, [(True, 1, 4), (False, 1, 64), (True, 2, 33)]),                          # ragged tile, other widths
+    _case(96, 16, 4, [(True, 1, 3), (True, 1, 3), (True, 1, 4), (True, 1, 1), (True, 1, 48), (False, 2, 3)]),   # the goldens' network: 16 HexPlane features, six heads
+    _case(500, 72, 5, [(True, 1, 7)]),                                                         # xa ends inside its third tile, odd embedding width
+    _case(70001, 128, 4, [(True, 1, 3), (True, 1, 48)]),                                       # many tiles per wave
     # levels without HexPlane features whose heads all have one hidden layer: no trunk launch, every head forms h from the embedding (EmdMlpBranch.xb)
-    (1000, 0, 4, [(True, 1, 3), (True, 1, 1), (True, 1, 48)]),                            # the fine level of the run script without the feature head
-    (37, 0, 8, [(True, 1, 4), (False, 1, 64)]),                                           # ragged tile, the widest embedding, an un-rectified input
-    (70001, 0, 5, [(True, 1, 3), (True, 1, 48)]),                                         # many tiles per wave, odd embedding width
+    _case(1000, 0, 4, [(True, 1, 3), (True, 1, 1), (True, 1, 48)]),                            # the fine level of the run script without the feature head
+    _case(37, 0, 8, [(True, 1, 4), (False, 1, 64)]),                                           # ragged tile, the widest embedding, an un-rectified input
+    _case(70001, 0, 5, [(True, 1, 3), (True, 1, 48)]),                                         # many tiles per wave, odd embedding width
     # every way dL/dout reaches the backward kernels: one output tile of 8 / 16 / 32 floats (16-byte pieces, partial tile), odd widths (guarded path), with h read ...
-    (333, 16, 4, [(True, 1, 16), (True, 1, 32), (True, 1, 8), (True, 1, 7), (True, 1, 33)]),
-    (333, 0, 4, [(True, 1, 16), (True, 1, 7), (True, 1, 33), (False, 1, 12)]),            # ... and with h recomputed from the embedding
-], ids=["coarse", "fine", "ragged", "golden-shape", "ka72", "70k", "fine-recomputed", "ragged-recomputed", "70k-recomputed", "dout-forms", "dout-forms-recomputed"])
-def test_level_mlp_matches_float64(N, ka, kb, heads):
+    _case(333, 16, 4, [(True, 1, 16), (True, 1, 32), (True, 1, 8), (True, 1, 7), (True, 1, 33)]),
+    _case(333, 0, 4, [(True, 1, 16), (True, 1, 7), (True, 1, 33), (False, 1, 12)]),            # ... and with h recomputed from the embedding
+    # The host dispatch of csrc/mlp.hip, arm by arm, at N = 70 (two full 32-row tiles and a ragged one): every form first and later, h read (ka 16 / 64: one and
+    # two input tiles) and recomputed (ka 0), plain and with the L1 regulariser of every head.  The seeds are chosen on the float64 reference alone: no ReLU of
+    # these levels comes within 3e-5 of its kink.
+    _case(70, 16, 4, _ORDER_3, seed=90), _case(70, 64, 5, _ORDER_8, seed=143), _case(70, 64, 4, _ORDER_64, seed=142),
+    _case(70, 64, 5, _ORDER_3, _ALL, seed=142), _case(70, 16, 4, _ORDER_8, _ALL, seed=96), _case(70, 16, 5, _ORDER_64, _ALL, seed=98),
+    _case(70, 0, 4, _ORDER_3, seed=99), _case(70, 0, 5, _ORDER_8, seed=89), _case(70, 0, 4, _ORDER_64, seed=74),
+    _case(70, 0, 5, _ORDER_3, _ALL, seed=92), _case(70, 0, 4, _ORDER_8, _ALL, seed=87), _case(70, 0, 5, _ORDER_64, _ALL, seed=86),
+    # two hidden layers: the embedding alone at an odd width, two input tiles, and an xa that ends inside its third tile (regulariser on some heads)
+    _case(70, 0, 5, _DEEP, seed=312), _case(70, 64, 4, _DEEP, _ALL, seed=141), _case(70, 72, 5, _DEEP[:3], (0, 2), seed=148),
+], ids=["coarse", "fine", "ragged", "golden-shape", "ka72", "70k", "fine-recomputed", "ragged-recomputed", "70k-recomputed", "dout-forms", "dout-forms-recomputed",
+        "first3", "first8", "first64", "first3-l1", "first8-l1", "first64-l1", "first3-recomputed", "first8-recomputed", "first64-recomputed",
+        "first3-recomputed-l1", "first8-recomputed-l1", "first64-recomputed-l1", "deep-embedding", "deep-l1", "deep-ka72-l1"])
+def test_level_mlp_matches_float64(N, ka, kb, heads, l1_heads, seed):
     from emd_amd.mlp import level_mlp
-    g = torch.Generator().manual_seed(N + ka + kb)
+    g = torch.Generator().manual_seed(seed)
     net = _net(g, ka, kb, heads)
     xa = torch.randn(N, ka, generator=g, dtype=torch.float64).requires_grad_(True) if ka else None
     xb = torch.randn(N, kb, generator=g, dtype=torch.float64).requires_grad_(True)
     gouts = [torch.randn(N, o, generator=g, dtype=torch.float64) for _, _, o in heads]
+    lam = [0.5 + 0.25 * j for j in range(len(l1_heads))]          # weight of the regulariser mean |out| of head l1_heads[j]
     kink = []
-    ref = _reference(net, xa, xb, kink)
+    ref = _reference(net, xa, xb, kink, l1_heads)
+    ref, ref_l1 = ref[:len(heads)], ref[len(heads):]
     near = torch.stack(kink).min(dim=0).values < 1e-5          # rows with a ReLU at its kink: no gradient is sent into them
     assert int(near.sum()) <= max(8, N // 20)
+    assert not l1_heads or int(near.sum()) == 0                # (the regulariser reaches every row: such a level needs a seed without one)
     for go in gouts:
         go[near] = 0.0
-    sum((r * go).sum() for r, go in zip(ref, gouts)).backward()
+    (sum((r * go).sum() for r, go in zip(ref, gouts)) + sum(w * r for w, r in zip(lam, ref_l1))).backward()          # lam * out.abs().mean() per regularised head
     # the HIP path on float32 copies
     c = lambda t: None if t is None else t.detach().to(DEV, torch.float32).requires_grad_(True)
     hx, hb = c(xa), c(xb)
     hnet = dict(w0=c(net["w0"]), b=c(net["b"]), col_a=net["col_a"], col_b=net["col_b"],
                 branches=[(ri, [(c(w), c(b)) for w, b in hid], (c(wo), c(bo))) for ri, hid, (wo, bo) in net["branches"]])
-    outs = level_mlp(hx, hb, hnet["w0"], hnet["b"], hnet["col_a"], hnet["col_b"], hnet["branches"])
-    for k, (o, r) in enumerate(zip(outs, ref)):
+    outs = level_mlp(hx, hb, hnet["w0"], hnet["b"], hnet["col_a"], hnet["col_b"], hnet["branches"], l1_heads=l1_heads)
+    assert len(outs) == len(heads) + len(l1_heads)
+    outs, l1s = outs[:len(heads)], outs[len(heads):]
+    for k, (o, r) in enumerate(zip(outs + l1s, ref + ref_l1)):
         err = float((o.detach().double().cpu() - r.detach()).abs().max())
         assert err <= 2e-5 * max(1.0, float(r.abs().max())), ("output", k, err)
-    sum((o * go.to(DEV, torch.float32)).sum() for o, go in zip(outs, gouts)).backward()
+    (sum((o * go.to(DEV, torch.float32)).sum() for o, go in zip(outs, gouts)) + sum(w * o for w, o in zip(lam, l1s))).backward()
 
     def check(name, got, want):
         scale = max(float(want.abs().max()), 1e-12)
