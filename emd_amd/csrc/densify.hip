@@ -14,10 +14,12 @@
 //                       of 3 M elements, i.e. three workgroups: 7.3 ms of the event's 8.2 at 3 M Gaussians, profiles/r06_density_event.txt]
 //   k_densify_index    for every OUTPUT row its source row and kind (position = block offset + ballot prefix), in the reference's order:
 //                      survivors (in order), clones (in order), split samples replica 0 (in order), replica 1 (in order)
-//   k_densify_gather   one launch for ALL tensors (7 parameters + 14 Adam moments + statistics): output row <- source row;
-//                      the moments and statistics of new rows are zero; split samples get xyz = R(q) (std * n) + xyz with
-//                      n ~ N(0, 1) from Philox4x32-10 keyed by (seed, SOURCE Gaussian index, replica) -- identical on every
-//                      rank without communication -- and scaling = log(exp(s) / (0.8 * 2)).
+//   k_densify_gather   one launch for ALL tensors (7 parameters + 14 Adam moments + statistics) and ONE rule for both projects' events:
+//                      output row <- source row; the moments and statistics of new rows are zero (a densification zeroes the statistics
+//                      of every row); split samples get xyz = R(q) (std * n) + xyz with n ~ N(0, 1) from Philox4x32-10 keyed by
+//                      (seed, SOURCE Gaussian index, replica) -- identical on every rank without communication; a reduced row gets
+//                      scaling = log(exp(s) / 1.6)  (= 0.8 * 2 in float).  OmniRe's refinement (EMD_DENSIFY_MODE_REFINE) differs only in
+//                      WHICH rows are reduced: every copy of a split source (kind + 16), the original included.
 // HBM-bound: every surviving byte is read and written once.
 #include <string.h>
 
@@ -169,61 +171,42 @@ __device__ __forceinline__ void normal3(uint64_t seed, uint32_t index, uint32_t 
     n[2] = rb * cosf(6.28318530717958648f * u3);
 }
 
-// One launch for all tensors: blockIdx.y = tensor, grid-stride over its output elements.
+// One coordinate of a split sample: new_xyz = R(q) (std * n) + xyz with q normalised as build_rotation does (general_utils.py:245-266;
+// vanilla.py:328-343), std = exp() of the source row's scale BEFORE the reduction, n the recorded draw or Philox of (seed, source row, replica)
+__device__ __forceinline__ float split_sample_coord(const EmdDensifyGather& g, int i, int rep, int j, int c, float v) {
+    float n[3];
+    if (g.samples) { const float* s = g.samples + ((size_t)rep * g.num_split + g.split_rank[j]) * 3; n[0] = s[0]; n[1] = s[1]; n[2] = s[2]; }
+    else normal3(g.seed, (uint32_t)i, (uint32_t)rep, n);
+    const float* sc = g.scaling + 3 * (size_t)i;
+    const float* qq = g.rotation + 4 * (size_t)i;
+    const float e0 = expf(sc[0]) * n[0], e1 = expf(sc[1]) * n[1], e2 = expf(sc[2]) * n[2];
+    const float qn = sqrtf(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
+    const float r = qq[0] / qn, x = qq[1] / qn, y = qq[2] / qn, z = qq[3] / qn;
+    float R0, R1, R2;
+    if (c == 0) { R0 = 1.f - 2.f * (y * y + z * z); R1 = 2.f * (x * y - r * z); R2 = 2.f * (x * z + r * y); }
+    else if (c == 1) { R0 = 2.f * (x * y + r * z); R1 = 1.f - 2.f * (x * x + z * z); R2 = 2.f * (y * z - r * x); }
+    else { R0 = 2.f * (x * z - r * y); R1 = 2.f * (y * z + r * x); R2 = 1.f - 2.f * (x * x + y * y); }
+    return ((R0 * e0 + R1 * e1) + R2 * e2) + v;
+}
+
+// One launch for all tensors: blockIdx.y = tensor, grid-stride over its output elements.  kind & 15: 0 a surviving source row, 1 its copy (clone /
+// duplicate), 2 + r split sample of replica r.  A row's scale is reduced where kind carries + 16 (REFINE: the source was split -- original,
+// samples and duplicate alike, vanilla.py:337-345) and, in the other two modes, on the samples (the split original is not an output row).
 __global__ void __launch_bounds__(EMD_BLOCK) k_densify_gather(EmdDensifyGather g) {
     const EmdDensifyTensor t = g.tensors[blockIdx.y];
     const size_t total = (size_t)g.num_out * t.width;
     for (size_t idx = (size_t)blockIdx.x * EMD_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * EMD_BLOCK) {
         const int j = (int)(idx / t.width), c = (int)(idx % t.width);
-        const int i = g.src[j], kd = g.kind[j];
-        float v;
-        if (g.mode == EMD_DENSIFY_MODE_REFINE) {
-            // OmniRe (vanilla.py:256-263,328-349; basics.py:219-242): kind 0 original, 1 duplicate, 2 + r sample of replica r, + 16 = the source was split
-            const int base = kd & 15;
-            v = t.src[(size_t)i * t.width + c];
-            if (t.role == EMD_DENSIFY_ROLE_STATE || t.role == EMD_DENSIFY_ROLE_ZERO) { if (base != 0) v = 0.f; }
-            else if (t.role == EMD_DENSIFY_ROLE_SCALING) { if (kd & 16) v = logf(expf(v) / 1.6f); }      // original, samples and duplicate of a split source alike
-            else if (t.role == EMD_DENSIFY_ROLE_XYZ && base >= 2) {
-                float n[3];
-                if (g.samples) { const float* s_ = g.samples + ((size_t)(base - 2) * g.num_split + g.split_rank[j]) * 3; n[0] = s_[0]; n[1] = s_[1]; n[2] = s_[2]; }
-                else normal3(g.seed, (uint32_t)i, (uint32_t)(base - 2), n);
-                const float* sc = g.scaling + 3 * (size_t)i;          // the scale BEFORE the reduction (vanilla.py:337-340)
-                const float* qq = g.rotation + 4 * (size_t)i;
-                const float e0 = expf(sc[0]) * n[0], e1 = expf(sc[1]) * n[1], e2 = expf(sc[2]) * n[2];
-                const float qn = sqrtf(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
-                const float r = qq[0] / qn, x = qq[1] / qn, y = qq[2] / qn, z = qq[3] / qn;
-                float R0, R1, R2;
-                if (c == 0) { R0 = 1.f - 2.f * (y * y + z * z); R1 = 2.f * (x * y - r * z); R2 = 2.f * (x * z + r * y); }
-                else if (c == 1) { R0 = 2.f * (x * y + r * z); R1 = 1.f - 2.f * (x * x + z * z); R2 = 2.f * (y * z - r * x); }
-                else { R0 = 2.f * (x * z - r * y); R1 = 2.f * (y * z + r * x); R2 = 1.f - 2.f * (x * x + y * y); }
-                v = ((R0 * e0 + R1 * e1) + R2 * e2) + v;
-            }
-            t.dst[idx] = v;
-            continue;
-        }
-        if (t.role == EMD_DENSIFY_ROLE_STATE) v = kd == 0 ? t.src[(size_t)i * t.width + c] : 0.f;             // Adam moments of new rows: zero
-        else if (t.role == EMD_DENSIFY_ROLE_ZERO) v = (g.mode == EMD_DENSIFY_MODE_DENSIFY) ? 0.f : t.src[(size_t)i * t.width + c];   // statistics: reset by a densification
-        else {
-            v = t.src[(size_t)i * t.width + c];
-            if (kd >= 2) {
-                if (t.role == EMD_DENSIFY_ROLE_SCALING) v = logf(expf(v) / (0.8f * 2.f));
-                else if (t.role == EMD_DENSIFY_ROLE_XYZ) {
-                    // new_xyz = R(q) (std * n) + xyz, q normalised as build_rotation does (general_utils.py:245-266)
-                    float n[3];
-                    if (g.samples) { const float* s = g.samples + ((size_t)(kd - 2) * g.num_split + g.split_rank[j]) * 3; n[0] = s[0]; n[1] = s[1]; n[2] = s[2]; }
-                    else normal3(g.seed, (uint32_t)i, (uint32_t)(kd - 2), n);
-                    const float* sc = g.scaling + 3 * (size_t)i;
-                    const float* qq = g.rotation + 4 * (size_t)i;
-                    const float e0 = expf(sc[0]) * n[0], e1 = expf(sc[1]) * n[1], e2 = expf(sc[2]) * n[2];
-                    const float qn = sqrtf(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
-                    const float r = qq[0] / qn, x = qq[1] / qn, y = qq[2] / qn, z = qq[3] / qn;
-                    float R0, R1, R2;
-                    if (c == 0) { R0 = 1.f - 2.f * (y * y + z * z); R1 = 2.f * (x * y - r * z); R2 = 2.f * (x * z + r * y); }
-                    else if (c == 1) { R0 = 2.f * (x * y + r * z); R1 = 1.f - 2.f * (x * x + z * z); R2 = 2.f * (y * z - r * x); }
-                    else { R0 = 2.f * (x * z - r * y); R1 = 2.f * (y * z + r * x); R2 = 1.f - 2.f * (x * x + y * y); }
-                    v = ((R0 * e0 + R1 * e1) + R2 * e2) + v;
-                }
-            }
+        const int i = g.src[j], kd = g.kind[j], base = kd & 15;
+        const bool fresh = base != 0, sample = base >= 2, reduced = (kd & 16) || (g.mode != EMD_DENSIFY_MODE_REFINE && sample);
+        const auto source = [&] { return t.src[(size_t)i * t.width + c]; };
+        float v = 0.f;
+        switch (t.role) {          // the same for every thread of the block: a scalar branch, and a copied row's load does not depend on its kind
+        case EMD_DENSIFY_ROLE_STATE: if (!fresh) v = source(); break;                                              // Adam moments of new rows: zero
+        case EMD_DENSIFY_ROLE_ZERO: if (!fresh && g.mode != EMD_DENSIFY_MODE_DENSIFY) v = source(); break;         // statistics: also reset by a densification
+        case EMD_DENSIFY_ROLE_SCALING: v = source(); if (reduced) v = logf(expf(v) / 1.6f); break;
+        case EMD_DENSIFY_ROLE_XYZ: v = source(); if (sample) v = split_sample_coord(g, i, base - 2, j, c, v); break;
+        default: v = source();                                                                                     // COPY
         }
         t.dst[idx] = v;
     }

@@ -1,0 +1,103 @@
+"""The one driver of a density-control event and the one optimiser handoff behind it (csrc/densify.hip).
+
+`restructure_rows` runs decide -> scan -> ONE host read of the totals -> index -> ONE gather over an arbitrary set of per-point tensors, for
+S3Gaussian's densify / prune (EmdDensifyArgs) and for OmniRe's refinement (EmdRefineArgs) alike; `hand_over` points an optimiser group at the
+leaf that replaces its parameter and attaches the Adam moments that travelled with the rows.  The three stores (GaussianModel,
+VanillaGaussians, model.density_control) build their jobs, install the outputs on their own attributes and keep their own bookkeeping."""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, scaling=None, rotation=None, num_samples=2):
+    """One density-control event on `N` rows of an arbitrary set of per-point tensors: decide -> scan -> index -> ONE gather (csrc/densify.hip).
+    `args`: an EmdDensifyArgs (`mode` DENSIFY / PRUNE) or an EmdRefineArgs (`mode` REFINE) with the decision inputs filled (pointers to the N
+    rows); `jobs`: [(tensor [N, ...], role)] -- one that is not float32 or not contiguous is converted, and only when rows move; `scaling` [N,3] / `rotation` [N,4]: the
+    source log-scales and quaternions a split sample's position is drawn from (float32 contiguous; not needed by a prune); `samples`
+    [num_samples, n_split, 3]: standard normals to use instead of the Philox draw keyed by `seed` (`num_samples` is 2 outside REFINE);
+    `front_rows`: every output tensor gets that many extra rows in FRONT of the gathered ones, left for the caller to fill (rows of a store
+    that do not take part: the actors of emd_amd.model.density_control).
+    -> (outs or None when nothing changes, totals): (n_keep, n_clone, n_split), in REFINE mode (n_keep, n_dup, n_samp, n_split) -- originals,
+    duplicates and split sources whose samples are kept, split sources.  The event's single host read is the totals."""
+    lib = L.load()
+    refine = isinstance(args, L.EmdRefineArgs)
+    assert refine == (mode == L.DENSIFY_MODE_REFINE)
+    cols = 4 if refine else 3
+    if N == 0:
+        return None, (0,) * cols
+    dev = jobs[0][0].device
+    code = torch.empty(N, dtype=torch.int32, device=dev)
+    inc = torch.empty(cols, (N + 255) // 256, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
+    totals = torch.empty(cols, dtype=torch.int32, device=dev)
+    args.num_points = N
+    if refine:
+        L.check(lib.emd_refine_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_refine_decide")
+    else:
+        args.mode = mode
+        L.check(lib.emd_densify_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_densify_decide")
+    L.check(lib.emd_densify_scan(N, cols, inc.data_ptr(), totals.data_ptr(), _stream()), "emd_densify_scan")
+    counts = tuple(int(v) for v in totals.tolist())
+    if refine:
+        n_keep, n_dup, n_samp, n_split = counts
+        M = n_keep + num_samples * n_samp + n_dup
+        nothing = M == N and n_keep == N and n_split == 0
+    else:
+        n_keep, n_clone, n_split = counts
+        M, num_samples = n_keep + n_clone + 2 * n_split, 2
+        nothing = (n_clone == 0 and n_split == 0) if mode == L.DENSIFY_MODE_DENSIFY else n_keep == N
+    if nothing:
+        return None, counts
+    src = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    kind = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    rank = torch.empty(max(M, 1), dtype=torch.int32, device=dev) if samples is not None else None      # the row of a recorded draw
+    if refine:
+        L.check(lib.emd_refine_index(N, M, num_samples, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), L.ptr(rank),
+                                     _stream()), "emd_refine_index")
+    else:
+        L.check(lib.emd_densify_index(N, M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), _stream()), "emd_densify_index")
+        if rank is not None:
+            L.check(lib.emd_densify_split_rank(M, n_keep, n_clone, n_split, rank.data_ptr(), _stream()), "emd_densify_split_rank")
+    g = L.EmdDensifyGather()
+    g.num_out, g.mode, g.num_split = M, mode, n_split
+    g.src, g.kind = src.data_ptr(), kind.data_ptr()
+    g.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    g.scaling, g.rotation = L.ptr(scaling), L.ptr(rotation)
+    keep_alive = [src, kind, code, inc, totals, scaling, rotation, rank]
+    if samples is not None:
+        samples = samples.to(dev).float().contiguous()
+        assert samples.shape == (num_samples, n_split, 3), (tuple(samples.shape), num_samples, n_split)
+        g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
+        keep_alive.append(samples)
+    assert len(jobs) <= L.DENSIFY_MAX_TENSORS
+    outs = []
+    for k, (t, role) in enumerate(jobs):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.detach().float().contiguous()
+        assert t.shape[0] == N
+        width = t.numel() // N
+        out = torch.empty((front_rows + M,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+        g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width = t.data_ptr(), out.data_ptr() + 4 * width * front_rows, width
+        g.tensors[k].role = role
+        keep_alive.append(t)
+        outs.append(out)
+    g.num_tensors = len(jobs)
+    L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
+    del keep_alive
+    return outs, counts
+
+
+def hand_over(optimizer, group, param, moments=None):
+    """Point the single-parameter `group` of `optimizer` at the leaf `param` that replaces its parameter.  The old parameter's state (step count
+    included) moves to the new one with `moments` = (exp_avg, exp_avg_sq), or with zero moments when `moments` is None (an opacity reset, or a
+    state that held no moments to carry); a parameter that has no state yet gets none."""
+    st = optimizer.state.pop(group["params"][0], None)
+    group["params"] = [param]
+    if st:
+        st["exp_avg"], st["exp_avg_sq"] = moments if moments is not None else (torch.zeros_like(param), torch.zeros_like(param))
+        optimizer.state[param] = st

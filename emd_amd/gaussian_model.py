@@ -14,7 +14,7 @@ Mirrors, with the same attribute / method names and argument meaning (behaviour 
 What differs from the reference is WHERE the work runs.  The reference edits every parameter and both Adam moments with
 boolean-mask indexing and `torch.cat` / `repeat` (a device-to-host sync per mask, ~60 launches and as many temporaries per
 event) and draws the split samples from the global CUDA generator.  Here one event is four launches (`emd_densify_*`,
-csrc/densify.hip): decide -> prefix sums -> output index -> ONE gather that writes all 7 parameters, 14 Adam moments and the
+csrc/densify.hip, driven by density.restructure_rows): decide -> prefix sums -> output index -> ONE gather that writes all 7 parameters, 14 Adam moments and the
 statistics, with a single host read (the new point count, needed to size the new tensors).  The split samples come from
 Philox4x32-10 keyed by (seed, source Gaussian index, replica): every rank of a data-parallel job draws the same samples without
 communication, so replicas stay identical ("DP semantic change").  The ORDER of the resulting points is the
@@ -27,7 +27,6 @@ raises inside numpy whenever `gaussian_embedding_dim > 0` -- gaussian_model.py:2
 and load in the reference unchanged.)  `capture` / `restore` use the reference's 16-tuple, so `torch.save((gaussians.capture(),
 iteration), path)` checkpoints are interchangeable.
 """
-import ctypes as C
 import os
 import struct
 
@@ -36,6 +35,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .density import hand_over, restructure_rows
 from .optim import Adam, expon_lr
 
 SH_C0 = 0.28209479177387814
@@ -43,10 +43,6 @@ SH_C0 = 0.28209479177387814
 
 def inverse_sigmoid(x):
     return torch.log(x / (1 - x))
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---- PLY (binary_little_endian 1.0, one `vertex` element of float properties) ---------------------------------------------------
@@ -101,58 +97,6 @@ def read_ply(path):
         dt = np.dtype([(n, end + t) for n, t in props])
         arr = np.frombuffer(f.read(dt.itemsize * count), dtype=dt, count=count)
         return {n: np.asarray(arr[n]) for n, _ in props}
-
-
-def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, scaling=None, rotation=None):
-    """One density-control event on `N` rows of an arbitrary set of per-point tensors: decide -> scan -> index -> ONE gather (csrc/densify.hip).
-    `args`: an EmdDensifyArgs with the decision inputs filled (pointers to the N rows); `jobs`: [(tensor [N, ...] float32 contiguous, role)];
-    `scaling` [N,3] / `rotation` [N,4]: the source log-scales and quaternions a split sample's position is drawn from (needed in DENSIFY mode);
-    `front_rows`: every output tensor gets that many extra rows in FRONT of the gathered ones, left for the caller to fill (rows of a store
-    that do not take part: the actors of emd_amd.model.density_control).  -> (outs or None when nothing changes, (n_keep, n_clone, n_split)).
-    The event's single host read is the three totals."""
-    lib = L.load()
-    if N == 0:
-        return None, (0, 0, 0)
-    dev = jobs[0][0].device
-    code = torch.empty(N, dtype=torch.int32, device=dev)
-    inc = torch.empty(3, (N + 255) // 256, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
-    totals = torch.empty(3, dtype=torch.int32, device=dev)
-    args.num_points, args.mode = N, mode
-    L.check(lib.emd_densify_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_densify_decide")
-    L.check(lib.emd_densify_scan(N, 3, inc.data_ptr(), totals.data_ptr(), _stream()), "emd_densify_scan")
-    n_keep, n_clone, n_split = (int(v) for v in totals.tolist())
-    if (mode == L.DENSIFY_MODE_DENSIFY and n_clone == 0 and n_split == 0) or (mode == L.DENSIFY_MODE_PRUNE and n_keep == N):
-        return None, (n_keep, n_clone, n_split)
-    M = n_keep + n_clone + 2 * n_split
-    src = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    kind = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    L.check(lib.emd_densify_index(N, M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), _stream()), "emd_densify_index")
-    g = L.EmdDensifyGather()
-    g.num_out, g.mode, g.num_split = M, mode, n_split
-    g.src, g.kind = src.data_ptr(), kind.data_ptr()
-    g.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    keep_alive = [src, kind, code, inc, totals, scaling, rotation]
-    g.scaling, g.rotation = L.ptr(scaling), L.ptr(rotation)
-    if samples is not None:
-        samples = samples.to(dev).float().contiguous()
-        assert samples.shape == (2, n_split, 3), (tuple(samples.shape), n_split)
-        rank = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        L.check(lib.emd_densify_split_rank(M, n_keep, n_clone, n_split, rank.data_ptr(), _stream()), "emd_densify_split_rank")
-        g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
-        keep_alive += [samples, rank]
-    assert len(jobs) <= L.DENSIFY_MAX_TENSORS
-    outs = []
-    for k, (t, role) in enumerate(jobs):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == N
-        width = t.numel() // N
-        out = torch.empty((front_rows + M,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-        g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width = t.data_ptr(), out.data_ptr() + 4 * width * front_rows, width
-        g.tensors[k].role = role
-        outs.append(out)
-    g.num_tensors = len(jobs)
-    L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
-    del keep_alive
-    return outs, (n_keep, n_clone, n_split)
 
 
 class GaussianModel:
@@ -364,97 +308,51 @@ class GaussianModel:
         return {g["name"]: g for g in self.optimizer.param_groups if g["name"] in self.GROUPS and len(g["params"]) == 1}
 
     def _restructure(self, mode, args, samples=None):
-        """One event: decide -> scan -> index -> gather (see the module docstring).  Returns (n_keep, n_clone, n_split)."""
-        lib, dev = L.load(), self.device
+        """One event through density.restructure_rows (see the module docstring).  Returns (n_keep, n_clone, n_split)."""
         N = self._xyz.shape[0]
         if N == 0:
             return 0, 0, 0
-        code = torch.empty(N, dtype=torch.int32, device=dev)
-        nblocks = (N + 255) // 256
-        inc = torch.empty(3, nblocks, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
-        totals = torch.empty(3, dtype=torch.int32, device=dev)
-        args.num_points, args.mode = N, mode
-        L.check(lib.emd_densify_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_densify_decide")
-        L.check(lib.emd_densify_scan(N, 3, inc.data_ptr(), totals.data_ptr(), _stream()), "emd_densify_scan")
-        n_keep, n_clone, n_split = (int(v) for v in totals.tolist())          # the event's single host read
-        if mode == L.DENSIFY_MODE_DENSIFY and n_clone == 0 and n_split == 0:
-            # nothing selected: the reference's densify_and_clone still runs densification_postfix, which clears the three statistics
-            # (gaussian_model.py:526-530) -- stale ones would leak into the next interval and into prune()'s max_radii2D test
-            for t in (getattr(self, "xyz_gradient_accum", None), getattr(self, "denom", None), getattr(self, "max_radii2D", None)):
-                if t is not None:
-                    t.zero_()
-            return n_keep, 0, 0
-        if mode == L.DENSIFY_MODE_PRUNE and n_keep == N:
-            return n_keep, 0, 0
-        M = n_keep + n_clone + 2 * n_split
-        src = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        kind = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        L.check(lib.emd_densify_index(N, M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), _stream()), "emd_densify_index")
-        g = L.EmdDensifyGather()
-        g.num_out, g.mode, g.num_split = M, mode, n_split
-        g.src, g.kind = src.data_ptr(), kind.data_ptr()
-        g.scaling, g.rotation = self._scaling.data_ptr(), self._rotation.data_ptr()
-        g.seed = (self.densify_seed * 0x9E3779B97F4A7C15 + self.densify_events) & 0xFFFFFFFFFFFFFFFF
-        keep_alive = [src, kind, code, inc, totals]
-        if samples is not None:
-            samples = samples.to(dev).float().contiguous()
-            assert samples.shape == (2, n_split, 3), (tuple(samples.shape), n_split)
-            rank = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-            L.check(lib.emd_densify_split_rank(M, n_keep, n_clone, n_split, rank.data_ptr(), _stream()), "emd_densify_split_rank")
-            g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
-            keep_alive += [samples, rank]
-        jobs = []          # (source tensor, role, setter)
+        jobs, keys = [], []          # (source tensor, role), what the output becomes
         roles = {"xyz": L.DENSIFY_ROLE_XYZ, "scaling": L.DENSIFY_ROLE_SCALING}
         groups = self._point_groups()
         for name in self.GROUPS:
-            attr = self._ATTR[name]
-            p = getattr(self, attr)
-            jobs.append((p, roles.get(name, L.DENSIFY_ROLE_COPY), ("param", name)))
+            jobs.append((getattr(self, self._ATTR[name]), roles.get(name, L.DENSIFY_ROLE_COPY)))
+            keys.append(("param", name))
             st = self._state(groups[name]) if name in groups else None
             if st is not None:
-                jobs.append((st["exp_avg"], L.DENSIFY_ROLE_STATE, ("exp_avg", name)))
-                jobs.append((st["exp_avg_sq"], L.DENSIFY_ROLE_STATE, ("exp_avg_sq", name)))
+                jobs += [(st["exp_avg"], L.DENSIFY_ROLE_STATE), (st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)]
+                keys += [("moment", name)] * 2
         for attr in ("xyz_gradient_accum", "denom", "max_radii2D"):
             t = getattr(self, attr)
             if t.dim() >= 1 and t.shape[0] == N:
-                jobs.append((t, L.DENSIFY_ROLE_ZERO, ("stat", attr)))
-        table_f = self._deformation_table.to(torch.float32)
-        jobs.append((table_f, L.DENSIFY_ROLE_COPY, ("table", None)))
-        assert len(jobs) <= L.DENSIFY_MAX_TENSORS
-        outs = []
-        for k, (t, role, _) in enumerate(jobs):
-            t = t.detach()
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.float().contiguous()
-            width = t.numel() // N
-            out = torch.empty((M,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-            g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width, g.tensors[k].role = t.data_ptr(), out.data_ptr(), width, role
-            keep_alive.append(t)
-            outs.append(out)
-        g.num_tensors = len(jobs)
-        L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
+                jobs.append((t, L.DENSIFY_ROLE_ZERO))
+                keys.append(("stat", attr))
+        jobs.append((self._deformation_table, L.DENSIFY_ROLE_COPY))          # travels as float (the driver converts it once rows do move)
+        keys.append(("table", None))
+        seed = self.densify_seed * 0x9E3779B97F4A7C15 + self.densify_events
+        outs, (n_keep, n_clone, n_split) = restructure_rows(mode, args, jobs, N, seed=seed, samples=samples, scaling=self._scaling.detach(),
+                                                            rotation=self._rotation.detach())
+        if outs is None:
+            if mode == L.DENSIFY_MODE_DENSIFY:
+                # nothing selected: the reference's densify_and_clone still runs densification_postfix, which clears the three statistics
+                # (gaussian_model.py:526-530) -- stale ones would leak into the next interval and into prune()'s max_radii2D test
+                for t in (getattr(self, "xyz_gradient_accum", None), getattr(self, "denom", None), getattr(self, "max_radii2D", None)):
+                    if t is not None:
+                        t.zero_()
+            return n_keep, 0, 0
         # install the new tensors: parameters become fresh leaves, the optimiser keeps its groups and per-parameter state
-        new_params, new_state = {}, {}
-        for (t, role, (what, name)), out in zip(jobs, outs):
+        moments = {}          # group name -> [exp_avg, exp_avg_sq]
+        for (what, name), out in zip(keys, outs):
             if what == "param":
-                new_params[name] = nn.Parameter(out.requires_grad_(True))
-            elif what in ("exp_avg", "exp_avg_sq"):
-                new_state.setdefault(name, {})[what] = out
+                setattr(self, self._ATTR[name], nn.Parameter(out.requires_grad_(True)))
+            elif what == "moment":
+                moments.setdefault(name, []).append(out)
             elif what == "stat":
                 setattr(self, name, out)
             else:
                 self._deformation_table = out > 0.5
-        for name in self.GROUPS:
-            old = getattr(self, self._ATTR[name])
-            if name in groups:
-                grp = groups[name]
-                st = self.optimizer.state.pop(grp["params"][0], None)
-                grp["params"][0] = new_params[name]
-                if st:
-                    st["exp_avg"], st["exp_avg_sq"] = new_state[name]["exp_avg"], new_state[name]["exp_avg_sq"]
-                    self.optimizer.state[new_params[name]] = st
-            setattr(self, self._ATTR[name], new_params[name])
-            del old
+        for name, grp in groups.items():
+            hand_over(self.optimizer, grp, getattr(self, self._ATTR[name]), moments.get(name))
         if mode == L.DENSIFY_MODE_DENSIFY:
             self.densify_events += 1
         self._knn_table = None                     # the rows moved: the cached neighbour table describes another point set
@@ -498,9 +396,5 @@ class GaussianModel:
         p = nn.Parameter(new.requires_grad_(True))
         grp = self._point_groups().get("opacity")
         if grp is not None:
-            st = self.optimizer.state.pop(grp["params"][0], None)
-            grp["params"][0] = p
-            if st:
-                st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(new), torch.zeros_like(new)
-                self.optimizer.state[p] = st
+            hand_over(self.optimizer, grp, p)
         self._opacity = p

@@ -78,7 +78,7 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
 
     The BACKGROUND Gaussians (actor id -1) take part; an actor's points stay as they are -- the reference holds every tracked actor at a
     fixed budget (<= 5000 Gaussians, OmniRe/configs/paper_legacy/omnire.yaml:93; the bench scene's actors sit at that cap) and stores an
-    actor's points contiguously, which the per-actor kernels rely on.  The engine is emd_amd.gaussian_model.restructure_rows -- the device-side
+    actor's points contiguously, which the per-actor kernels rely on.  The engine is emd_amd.density.restructure_rows -- the device-side
     decide -> scan -> index -> gather of GaussianModel (csrc/densify.hip), here applied to the background rows of the store's own tensors IN
     PLACE of a copy (round 6: no slice / cat passes around the gather; `_features` travels as one 48-float row): two events (densify, prune),
     two host reads.  The split samples are a Philox draw keyed by (seed, event, source row, replica), so every rank of a view-parallel run that
@@ -92,7 +92,7 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
     `cat_tensors_to_optimizer` / `_prune_optimizer` do (gaussian_model.py:454-500); the actors' rows keep theirs.  WITHOUT it a caller's optimizer
     still points at the old tensors and must be rebuilt (its state for these five parameters is lost)."""
     from . import _lib as L
-    from .gaussian_model import restructure_rows
+    from .density import hand_over, restructure_rows
     dev, N = model._xyz.device, model._xyz.shape[0]
     if dev.type != "cuda":
         raise L.EmdError("density_control needs the store on a ROCm device; there is no CPU path")
@@ -164,12 +164,7 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
             old = getattr(model, nm)
             new = torch.nn.Parameter(full[nm]) if full[nm] is not cur[nm] else old
             if nm in groups and new is not old:
-                st = optimizer.state.pop(old, None)
-                groups[nm]["params"] = [new]
-                if st:
-                    if (nm, "exp_avg") in mom:
-                        st["exp_avg"], st["exp_avg_sq"] = mom[(nm, "exp_avg")], mom[(nm, "exp_avg_sq")]
-                    optimizer.state[new] = st
+                hand_over(optimizer, groups[nm], new, (mom[(nm, "exp_avg")], mom[(nm, "exp_avg_sq")]) if (nm, "exp_avg") in mom else None)
             setattr(model, nm, new)
         if model.has_actors:
             model.actor_id = torch.cat([model.actor_id[:n_dyn], torch.full((n_new,), -1, dtype=model.actor_id.dtype, device=dev)])

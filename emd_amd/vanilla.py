@@ -24,6 +24,7 @@ import torch
 from torch.nn import Parameter
 
 from . import _lib as L
+from .density import hand_over, restructure_rows
 
 SH_C0 = 0.28209479177387814
 
@@ -158,7 +159,7 @@ class VanillaGaussians(torch.nn.Module):
         return info
 
     def _refine(self, optimizer, do_densify, do_cull, samples):
-        lib, dev, c = L.load(), self._means.device, self.ctrl_cfg
+        dev, c = self._means.device, self.ctrl_cfg
         if dev.type != "cuda":
             raise L.EmdError("VanillaGaussians.refinement_after needs tensors on a ROCm device; there is no CPU path")
         N, ns = self.num_points, int(_get(c, "n_split_samples", 2))
@@ -178,72 +179,35 @@ class VanillaGaussians(torch.nn.Module):
         a.grad_threshold, a.size_threshold = float(_get(c, "densify_grad_thresh")), float(_get(c, "densify_size_thresh") * self.scene_scale)
         a.split_screen, a.cull_alpha = float(_get(c, "split_screen_size")), float(_get(c, "cull_alpha_thresh"))
         a.cull_size, a.cull_screen = float(_get(c, "cull_scale_thresh") * self.scene_scale), float(_get(c, "cull_screen_size"))
-        code = torch.empty(N, dtype=torch.int32, device=dev)
-        inc = torch.empty(4, (N + 255) // 256, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
-        totals = torch.empty(4, dtype=torch.int32, device=dev)
-        L.check(lib.emd_refine_decide(C.byref(a), code.data_ptr(), inc.data_ptr(), _stream()), "emd_refine_decide")
-        L.check(lib.emd_densify_scan(N, 4, inc.data_ptr(), totals.data_ptr(), _stream()), "emd_densify_scan")
-        n_keep, n_dup, n_samp, n_split = (int(v) for v in totals.tolist())          # the event's single host read
-        M = n_keep + ns * n_samp + n_dup
-        info = {"n_before": N, "n_after": M, "split": n_split, "originals_kept": n_keep, "samples_kept": ns * n_samp, "dups_kept": n_dup}
-        if M == N and n_keep == N and n_split == 0:
-            return info                                             # nothing split, duplicated or culled: every tensor stays as it is
-        src = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        kind = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        rank = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-        L.check(lib.emd_refine_index(N, M, ns, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), rank.data_ptr(), _stream()),
-                "emd_refine_index")
-        g = L.EmdDensifyGather()
-        g.num_out, g.mode, g.num_split = M, L.DENSIFY_MODE_REFINE, n_split
-        g.src, g.kind, g.split_rank = src.data_ptr(), kind.data_ptr(), rank.data_ptr()
-        keep.append(self._quats.detach().contiguous())
-        g.scaling, g.rotation = keep[0].data_ptr(), keep[-1].data_ptr()
-        g.seed = (self.refine_seed * 0x9E3779B97F4A7C15 + self.refine_events) & 0xFFFFFFFFFFFFFFFF
-        if samples is not None:
-            samples = samples.to(dev).float().contiguous()
-            assert samples.shape == (ns, n_split, 3), (tuple(samples.shape), ns, n_split)
-            g.samples = samples.data_ptr()
-            keep.append(samples)
         attrs = {"xyz": ("_means", L.DENSIFY_ROLE_XYZ), "sh_dc": ("_features_dc", L.DENSIFY_ROLE_COPY), "sh_rest": ("_features_rest", L.DENSIFY_ROLE_COPY),
                  "opacity": ("_opacities", L.DENSIFY_ROLE_COPY), "scaling": ("_scales", L.DENSIFY_ROLE_SCALING), "rotation": ("_quats", L.DENSIFY_ROLE_COPY)}
         groups = {grp["name"]: grp for grp in (optimizer.param_groups if optimizer is not None else [])
                   if grp["name"].startswith(self.class_prefix) and grp["name"][len(self.class_prefix):] in attrs}
-        jobs = []
+        jobs, keys = [], []          # (source tensor, role), what the output becomes
         for short, (attr, role) in attrs.items():
-            p = getattr(self, attr)
-            jobs.append((p, role, ("param", short)))
+            jobs.append((getattr(self, attr), role))
+            keys.append(("param", short))
             grp = groups.get(self.class_prefix + short)
             st = optimizer.state.get(grp["params"][0]) if grp is not None else None
             if st:
-                jobs.append((st["exp_avg"], L.DENSIFY_ROLE_STATE, ("exp_avg", short)))
-                jobs.append((st["exp_avg_sq"], L.DENSIFY_ROLE_STATE, ("exp_avg_sq", short)))
-        assert len(jobs) <= L.DENSIFY_MAX_TENSORS
-        outs = []
-        for k, (t, role, _) in enumerate(jobs):
-            t = t.detach()
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.float().contiguous()
-            out = torch.empty((M,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-            g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width, g.tensors[k].role = t.data_ptr(), out.data_ptr(), t.numel() // N, role
-            keep.append(t)
-            outs.append(out)
-        g.num_tensors = len(jobs)
-        L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
-        new_params, new_state = {}, {}
-        for (t, role, (what, short)), out in zip(jobs, outs):
+                jobs += [(st["exp_avg"], L.DENSIFY_ROLE_STATE), (st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)]
+                keys += [("moment", short)] * 2
+        seed = self.refine_seed * 0x9E3779B97F4A7C15 + self.refine_events
+        outs, (n_keep, n_dup, n_samp, n_split) = restructure_rows(L.DENSIFY_MODE_REFINE, a, jobs, N, seed=seed, samples=samples, scaling=keep[0],
+                                                                  rotation=self._quats.detach().contiguous(), num_samples=ns)
+        info = {"n_before": N, "n_after": n_keep + ns * n_samp + n_dup, "split": n_split, "originals_kept": n_keep, "samples_kept": ns * n_samp,
+                "dups_kept": n_dup}
+        if outs is None:
+            return info                                             # nothing split, duplicated or culled: every tensor stays as it is
+        moments = {}          # short name -> [exp_avg, exp_avg_sq]
+        for (what, short), out in zip(keys, outs):
             if what == "param":
-                new_params[short] = Parameter(out)
+                setattr(self, attrs[short][0], Parameter(out))
             else:
-                new_state.setdefault(short, {})[what] = out
-        for short, (attr, _) in attrs.items():
-            grp = groups.get(self.class_prefix + short)
-            if grp is not None:
-                st = optimizer.state.pop(grp["params"][0], None)
-                grp["params"] = [new_params[short]]
-                if st:
-                    st["exp_avg"], st["exp_avg_sq"] = new_state[short]["exp_avg"], new_state[short]["exp_avg_sq"]
-                    optimizer.state[new_params[short]] = st
-            setattr(self, attr, new_params[short])
+                moments.setdefault(short, []).append(out)
+        for name, grp in groups.items():
+            short = name[len(self.class_prefix):]
+            hand_over(optimizer, grp, getattr(self, attrs[short][0]), moments.get(short))
         if do_densify:
             self.refine_events += 1
         return info
