@@ -250,7 +250,9 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward",
                     "emd_radix_sort", "emd_camera_grad_workspace_size", "emd_raster_backward_camera",
                     "emd_raster_det_workspace_size", "emd_raster_det_layout", "emd_segmented_row_sum_workspace", "emd_segmented_row_sum",
-                    "emd_hexplane_det_workspace_size", "emd_hexplane_det_workspace_offsets")
+                    "emd_hexplane_det_workspace_size", "emd_hexplane_det_workspace_offsets",
+                    "emd_sky_det_workspace_size", "emd_sky_det_workspace_offsets", "emd_sky_backward_det",
+                    "emd_motion_det_workspace_size", "emd_motion_det_workspace_offsets", "emd_motion_backward_det")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -291,6 +293,11 @@ def load():
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emd_motion_backward.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EmdMotion)] + \
         [C.c_void_p] * 10
+    lib.emd_motion_det_workspace_size.argtypes = [C.c_int32]
+    lib.emd_motion_det_workspace_size.restype = C.c_size_t
+    lib.emd_motion_det_workspace_offsets.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.emd_motion_backward_det.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EmdMotion)] + \
+        [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_sh_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emd_sh_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.emd_activations_forward.argtypes = [C.c_int32] + [C.c_void_p] * 7
@@ -341,6 +348,10 @@ def load():
     lib.emd_tracked_pose_backward.argtypes = [C.POINTER(EmdTrackedPoseArgs), C.POINTER(EmdTrackedPoseGrads), C.c_void_p]
     lib.emd_sky_forward.argtypes = [C.POINTER(EmdSkyArgs), C.c_void_p]
     lib.emd_sky_backward.argtypes = [C.POINTER(EmdSkyBwdArgs), C.c_void_p]
+    lib.emd_sky_det_workspace_size.argtypes = [C.c_int64]
+    lib.emd_sky_det_workspace_size.restype = C.c_size_t
+    lib.emd_sky_det_workspace_offsets.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.emd_sky_backward_det.argtypes = [C.POINTER(EmdSkyBwdArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_knn_workspace.argtypes = [C.c_int32, C.c_int32]
     lib.emd_knn_workspace.restype = C.c_size_t
     lib.emd_knn.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -432,3 +443,38 @@ def hex_det_layout(args, plane):
     check(load().emd_hexplane_det_workspace_offsets(C.byref(args), int(plane), out), "emd_hexplane_det_workspace_offsets")
     o = [int(x) for x in out]
     return dict(rows=o[0], keys=o[1], slots=o[2], time_column=o[3], raw_keys=o[4], counts=o[5], passes=o[6], bytes=o[7])
+
+
+def _det_offsets(o):
+    return dict(rows=o[0], raw_keys=o[1], keys=o[2], slots=o[3], counts=o[4], bytes=o[5])
+
+
+def sky_det_workspace_size(num_pixels):
+    """Bytes of the workspace of emd_sky_backward_det for a call of `num_pixels` pixels (or directions)."""
+    n = int(load().emd_sky_det_workspace_size(int(num_pixels)))
+    if n == 0:
+        raise EmdError(f"the deterministic sky backward does not serve {num_pixels} pixels (4 P slots are numbered in 32 bits)")
+    return n
+
+
+def sky_det_layout(num_pixels, resolution):
+    """Byte offsets inside that workspace (emd_sky_det_workspace_offsets): a dict."""
+    out = (C.c_size_t * 6)()
+    check(load().emd_sky_det_workspace_offsets(int(num_pixels), int(resolution), out), "emd_sky_det_workspace_offsets")
+    return _det_offsets([int(x) for x in out])
+
+
+def motion_det_workspace_size(n):
+    """Bytes of the workspace of emd_motion_backward_det for `n` points."""
+    b = int(load().emd_motion_det_workspace_size(int(n)))
+    if b == 0:
+        raise EmdError(f"the deterministic motion backward does not serve {n} points")
+    return b
+
+
+def motion_det_layout(n, num_actors):
+    """Byte offsets inside that workspace (emd_motion_det_workspace_offsets): a dict."""
+    out = (C.c_size_t * 6)()
+    check(load().emd_motion_det_workspace_offsets(int(n), int(num_actors), out), "emd_motion_det_workspace_offsets")
+    return _det_offsets([int(x) for x in out])
+

@@ -547,6 +547,57 @@ int emd_motion_backward(int32_t n, const float* means, const float* quats, const
                                       dL_dresidual_dx, dL_dresidual_dq, st);
 }
 
+// the points are numbered in 32 bits, and the sort rounds its launch up to whole tiles
+static bool motion_det_fits(int64_t n) { return n >= 0 && 4 * n <= (int64_t)0xFFFFFFFFu - EMD_SORT_TILE; }
+
+size_t emd_motion_det_workspace_size(int32_t n) {
+    if (!motion_det_fits(n)) return 0;
+    MotionDetWs w;
+    emd_carve_motion_det(nullptr, n, &w);
+    return w.bytes;
+}
+
+int emd_motion_det_workspace_offsets(int32_t n, int32_t num_actors, size_t out[6]) {
+    if (!out || !motion_det_fits(n) || num_actors < 1) { emd_set_error("motion_det_workspace_offsets: bad argument (n = %d, num_actors = %d)", n, num_actors); return EMD_ERR_INVALID; }
+    MotionDetWs w;
+    emd_carve_motion_det(nullptr, n, &w);
+    const int buf = emd_radix_result_buf(true, emd_det_sort_passes(num_actors));
+    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
+    out[0] = off(w.pose_rows); out[1] = off(w.p.keys_in); out[2] = off(w.p.keys[buf]); out[3] = off(w.p.vals[buf]); out[4] = off(w.counts); out[5] = w.bytes;
+    return EMD_OK;
+}
+
+// emd_motion_backward with the pose gradient summed in a pinned order: rows, a stable compacting sort by actor, the segmented
+// row sum.  The per-point outputs are the default entry's.
+int emd_motion_backward_det(int32_t n, const float* means, const float* quats, const float* opacities,
+                            const EmdMotion* motion, const float* dL_dworld_means, const float* dL_dworld_quats,
+                            const float* dL_dopacities_out, float* dL_dmeans, float* dL_dquats, float* dL_dopacities,
+                            float* dL_dactor_pose, float* dL_dresidual_dx, float* dL_dresidual_dq, void* det_ws, size_t det_bytes,
+                            void* hip_stream) {
+    if (n < 0 || !means || !motion) { emd_set_error("motion_backward_det: bad argument"); return EMD_ERR_INVALID; }
+    if (motion->actor_id && (!motion->actor_pose || motion->num_actors <= 0)) { emd_set_error("motion_backward_det: actor_id without actor_pose"); return EMD_ERR_INVALID; }
+    if (!motion_det_fits(n)) { emd_set_error("motion_backward_det: the deterministic mode serves 4 n <= 2^32 - 1 - %d (n = %d)", EMD_SORT_TILE, n); return EMD_ERR_INVALID; }
+    // everything is decided here, before the first launch
+    const bool pose = dL_dactor_pose && motion->num_actors > 0;
+    MotionDetWs w;
+    memset(&w, 0, sizeof(w));
+    if (pose) {
+        emd_carve_motion_det(nullptr, n, &w);
+        if (!det_ws || det_bytes < w.bytes || ((uintptr_t)det_ws & 255)) {
+            emd_set_error("motion_backward_det: needs a 256-byte aligned det_ws of %zu bytes (emd_motion_det_workspace_size), got %zu at %p", w.bytes, det_ws ? det_bytes : (size_t)0, det_ws);
+            return EMD_ERR_WORKSPACE;
+        }
+        emd_carve_motion_det(det_ws, n, &w);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (pose) { int zrc = emd_zero_async(dL_dactor_pose, (size_t)motion->num_actors * EMD_ACTOR_STRIDE * sizeof(float), st); if (zrc) return zrc; }
+    int rc = emd_launch_motion_backward_det(n, means, quats, opacities, *motion, dL_dworld_means, dL_dworld_quats, dL_dopacities_out, dL_dmeans, dL_dquats,
+                                            dL_dopacities, dL_dresidual_dx, dL_dresidual_dq, w.pose_rows, w.p.keys_in, st);
+    if (rc || !pose || n == 0) return rc;
+    return emd_det_sort_and_sum(w.p, (size_t)n, motion->num_actors, nullptr, w.counts, w.pose_rows, EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, dL_dactor_pose,
+                                EMD_ACTOR_STRIDE, st);
+}
+
 int emd_sh_forward(int32_t n, int32_t degree, int32_t sh_coeffs, const float* dirs, const float* coeffs, float* rgb,
                    void* hip_stream) {
     if (n < 0 || degree < 0 || degree > 3 || sh_coeffs < (degree + 1) * (degree + 1) || !dirs || !coeffs || !rgb) {

@@ -266,6 +266,10 @@ int emd_launch_motion_forward(int n, const float* means, const float* quats, con
 int emd_launch_motion_backward(int n, const float* means, const float* quats, const float* opac, const EmdMotion& mo,
                                const float* g_wm, const float* g_wq, const float* g_wo, float* d_means, float* d_quats,
                                float* d_opac, float* d_pose, float* d_rdx, float* d_rdq, hipStream_t st);
+// the deterministic form: the pose rows of the bound points and their actors as keys instead of atomics on d_pose (pose_rows == NULL: none asked for)
+int emd_launch_motion_backward_det(int n, const float* means, const float* quats, const float* opac, const EmdMotion& mo,
+                                   const float* g_wm, const float* g_wq, const float* g_wo, float* d_means, float* d_quats,
+                                   float* d_opac, float* d_rdx, float* d_rdq, float* pose_rows, uint32_t* keys_in, hipStream_t st);
 int emd_launch_sh_forward(int n, int deg, int M, const float* dirs, const float* coeffs, float* rgb, hipStream_t st);
 int emd_launch_sh_backward(int n, int deg, int M, const float* dirs, const float* coeffs, const float* g_rgb,
                            float* d_coeffs, float* d_dirs, hipStream_t st);

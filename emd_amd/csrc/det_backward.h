@@ -1,6 +1,7 @@
 // det_backward.h -- workspace of the deterministic backward (EMD_FLAG_DETERMINISTIC, EmdBwdArgs.det_ws): the contribution rows
 // of the render backward and the pose rows of K8, each with the buffers of the reduction (det_reduce.h) that lists the rows per destination and adds
-// each list.  Included by api.hip alone; include/emd_raster.h states the size formula.
+// each list; and the workspace of the stand-alone motion backward's deterministic form (emd_motion_backward_det, section 8.10), which is the pose half
+// alone.  Included by api.hip alone; include/emd_raster.h states the size formulas.
 #pragma once
 #include "det_reduce.h"
 
@@ -21,5 +22,21 @@ static inline void emd_carve_det(void* base, int N, int64_t capacity, int num_ex
     w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
     w->pose_rows = (float*)(p + off); off = emd_align_up(off + n * EMD_ACTOR_STRIDE * sizeof(float), 256);
     emd_carve_det_sort(p, off, n, EMD_ACTOR_STRIDE, &w->p);
+    w->bytes = off + 256;
+}
+
+struct MotionDetWs {
+    float* pose_rows;        // [n][EMD_ACTOR_STRIDE] pose gradient of every actor-bound point (k_motion_backward_det)
+    DetSortWs p;             // n points -> actor ids
+    uint32_t* counts;        // [16] device-side counts: [0] points the sort kept
+    size_t bytes;
+};
+static inline void emd_carve_motion_det(void* base, int64_t n_points, MotionDetWs* w) {
+    char* p = (char*)base;
+    size_t off = 0;
+    const size_t n = (size_t)(n_points > 0 ? n_points : 1);
+    w->pose_rows = (float*)(p + off); off = emd_align_up(off + n * EMD_ACTOR_STRIDE * sizeof(float), 256);
+    emd_carve_det_sort(p, off, n, EMD_ACTOR_STRIDE, &w->p);
+    w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
     w->bytes = off + 256;
 }

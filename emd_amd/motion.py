@@ -381,8 +381,9 @@ def actor_pose_table(instances_quats, instances_trans, instances_fv, frame, trac
 
 class _MotionTransform(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means, quats, opacities, actor_pose, residual_dx, residual_dq, actor_ids):
+    def forward(ctx, means, quats, opacities, actor_pose, residual_dx, residual_dq, actor_ids, deterministic=False):
         lib = L.load()
+        ctx.deterministic = bool(deterministic)
         if means.device.type != "cuda":
             raise L.EmdError("transform_gaussians needs tensors on a ROCm device; there is no CPU path")
         N = means.shape[0]
@@ -409,18 +410,29 @@ class _MotionTransform(torch.autograd.Function):
         d_rdx = torch.empty_like(residual_dx) if residual_dx is not None else None
         d_rdq = torch.empty_like(residual_dq) if residual_dq is not None else None
         m = L.EmdMotion(L.ptr(actor_ids), L.ptr(actor_pose), int(actor_pose.shape[0]), L.ptr(residual_dx), L.ptr(residual_dq))
-        L.check(lib.emd_motion_backward(N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
-                                        L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
-                                        d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq), _stream()), "emd_motion_backward")
-        return d_means, d_quats, d_opac, d_pose, d_rdx, d_rdq, None
+        if ctx.deterministic:
+            # the pose gradient summed per actor in a pinned order (emd_motion_backward_det); the workspace comes from torch's
+            # allocator (512-byte aligned; under capture from the graph's pool), no host synchronisation
+            ws = torch.empty(L.motion_det_workspace_size(N), device=means.device, dtype=torch.uint8)
+            L.check(lib.emd_motion_backward_det(N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
+                                                L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
+                                                d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq), ws.data_ptr(), ws.numel(), _stream()),
+                    "emd_motion_backward_det")
+        else:
+            L.check(lib.emd_motion_backward(N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
+                                            L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
+                                            d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq), _stream()), "emd_motion_backward")
+        return d_means, d_quats, d_opac, d_pose, d_rdx, d_rdq, None, None
 
 
-def transform_gaussians(means, quats, opacities, actor_ids, actor_pose, residual_dx=None, residual_dq=None):
+def transform_gaussians(means, quats, opacities, actor_ids, actor_pose, residual_dx=None, residual_dq=None, deterministic=False):
     """world_means, world_quats (already `quat_act`-ed), opacities * valid -- one HIP kernel, differentiable.
 
     Equivalent of RigidNodes.transform_means + transform_quats + the validity mask of get_gaussians
     (rigid.py:575-576,589-591); points with actor_id < 0 pass through unchanged (static background).
+    deterministic: the gradient of `actor_pose` is summed per actor in ascending point index without float atomics -- bit-identical from run to
+    run, across streams and under hipGraph replay; every other gradient is per point and the same either way.
     """
     f = lambda t: None if t is None else t.contiguous().float()
     return _MotionTransform.apply(f(means), f(quats), None if opacities is None else f(opacities).reshape(-1),
-                                  f(actor_pose), f(residual_dx), f(residual_dq), actor_ids.to(torch.int32).contiguous())
+                                  f(actor_pose), f(residual_dx), f(residual_dq), actor_ids.to(torch.int32).contiguous(), bool(deterministic))

@@ -35,11 +35,12 @@ def _colors(world_means, features_dc, features_rest, camera_center, sh_degree, s
 
 
 def rigid_gaussians(means, quats, opacity_logits, log_scales, features_dc, features_rest, point_ids, actor_pose, camera_center,
-                    sh_degree=3, step=0, sh_degree_interval=1000, check_finite=True):
+                    sh_degree=3, step=0, sh_degree_interval=1000, check_finite=True, deterministic=False):
     """-> dict(_means, _opacities [N,1], _rgbs, _scales, _quats).  actor_pose: the [A,12] table of motion.build_actor_pose /
-    actor_pose_table for the current frame (pose, learned track offsets, validity)."""
+    actor_pose_table for the current frame (pose, learned track offsets, validity).  deterministic: as transform_gaussians."""
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
-    world_means, world_quats, opac = transform_gaussians(means, quats, torch.sigmoid(opacity_logits), ids, actor_pose)
+    world_means, world_quats, opac = transform_gaussians(means, quats, torch.sigmoid(opacity_logits), ids, actor_pose,
+                                                         deterministic=deterministic)
     gs = dict(_means=world_means, _opacities=opac.reshape(-1, 1),
               _rgbs=_colors(world_means, features_dc, features_rest, camera_center, sh_degree, step, sh_degree_interval),
               _scales=torch.exp(log_scales), _quats=world_quats)
@@ -50,9 +51,10 @@ def rigid_gaussians(means, quats, opacity_logits, log_scales, features_dc, featu
 
 def deformable_gaussians(network, means, quats, opacity_logits, log_scales, features_dc, features_rest, point_ids, actor_pose,
                          camera_center, instances_size, instances_embedding, t, sh_degree=3, step=0, sh_degree_interval=1000,
-                         use_deformation=True, stop_optimizing_canonical_xyz=True, check_finite=True):
+                         use_deformation=True, stop_optimizing_canonical_xyz=True, check_finite=True, deterministic=False):
     """DeformableNodes.get_gaussians: delta_xyz on the canonical means (detached when `stop_optimizing_canonical_xyz`), delta_quat on
-    the normalised quaternions, delta_scale (when the network has that head) on the activated scales; then as rigid_gaussians."""
+    the normalised quaternions, delta_scale (when the network has that head) on the activated scales; then as rigid_gaussians
+    (`deterministic` included: it covers the motion transform, not the network)."""
     from .deformation import nonrigid_deformation
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
     dx = dq = ds = None
@@ -63,7 +65,7 @@ def deformable_gaussians(network, means, quats, opacity_logits, log_scales, feat
     # delta_quat to get_quats = q / |q| (deformable.py:69), so the quaternions are normalised first when a residual is present
     q_in = quats / quats.norm(dim=-1, keepdim=True) if dq is not None else quats
     world_means, world_quats, opac = transform_gaussians(base, q_in, torch.sigmoid(opacity_logits), ids, actor_pose,
-                                                         residual_dx=dx, residual_dq=dq)
+                                                         residual_dx=dx, residual_dq=dq, deterministic=deterministic)
     scales = torch.exp(log_scales)
     if ds is not None:
         scales = scales + ds

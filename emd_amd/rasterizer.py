@@ -82,8 +82,10 @@ class RasterOptions:
     deterministic: bool = False     # bit-reproducible backward (EMD_FLAG_DETERMINISTIC): every gradient of a call is a fixed function of its inputs --
                                     # the render backward stores one row per (quadrant, survivor) and a stable sort + a segmented sum with a pinned
                                     # association replace its float atomics, the actor-pose gradient likewise.  The forward is untouched.  Costs a
-                                    # workspace of 64 B x 4 x capacity and five more launches; emd_amd.nodes' stand-alone motion
-                                    # op and the sky backward keep their atomics; the HexPlane backward has its own switch (HexPlaneField.deterministic)
+                                    # workspace of 64 B x 4 x capacity and five more launches.  The ops around the rasterizer have
+                                    # switches of their own: the sky backward (SkyCubeMap.deterministic / EnvLight.deterministic) and emd_amd.nodes'
+                                    # stand-alone motion op (transform_gaussians(..., deterministic=True)); the HexPlane backward
+                                    # (HexPlaneField.deterministic), section 8.9
 
     def replace(self, **kw):
         return dataclasses.replace(self, **{k: v for k, v in kw.items() if v is not None})

@@ -36,7 +36,7 @@ class _SkyOp(torch.autograd.Function):
     """sky colour (and optionally the blended image) from the cube map; gradients to cube, fg and acc (blend only)."""
 
     @staticmethod
-    def forward(ctx, cube, fg, acc, dirs, cam, jitter, H, W, flags, threshold, fill, want_blend):
+    def forward(ctx, cube, fg, acc, dirs, cam, jitter, H, W, flags, threshold, fill, want_blend, deterministic=False):
         _need_gpu(cube, "sky lookup")
         lib = L.load()
         cube = cube.contiguous().float()
@@ -79,7 +79,7 @@ class _SkyOp(torch.autograd.Function):
             out = torch.empty(shape, device=dev, dtype=torch.float32)
             a.out = out.data_ptr()
         L.check(lib.emd_sky_forward(C.byref(a), _stream()), "emd_sky_forward")
-        ctx.args, ctx.keep, ctx.want_blend = a, keep, want_blend
+        ctx.args, ctx.keep, ctx.want_blend, ctx.deterministic = a, keep, want_blend, bool(deterministic)
         ctx.save_for_backward(cube, fg if want_blend else None, acc)
         return (sky, out) if want_blend else (sky, sky.new_empty(0))
 
@@ -97,13 +97,21 @@ class _SkyOp(torch.autograd.Function):
         if ctx.want_blend and g_out is not None:
             g_out = g_out.contiguous().float(); keep.append(g_out); b.dL_dout = g_out.data_ptr()
         if b.dL_dsky is None and b.dL_dout is None:
-            return (None,) * 12
+            return (None,) * 13
         d_cube = torch.empty_like(cube) if ctx.needs_input_grad[0] else None
         d_fg = torch.empty_like(fg) if (ctx.want_blend and ctx.needs_input_grad[1]) else None
         d_acc = torch.empty_like(acc) if (ctx.want_blend and acc is not None and ctx.needs_input_grad[2]) else None
         b.dL_dcube, b.dL_dfg, b.dL_dacc = L.ptr(d_cube), L.ptr(d_fg), L.ptr(d_acc)
-        L.check(lib.emd_sky_backward(C.byref(b), _stream()), "emd_sky_backward")
-        return (d_cube, d_fg, d_acc) + (None,) * 9
+        if ctx.deterministic:
+            # the cube-map gradient summed in a pinned order (emd_sky_backward_det).  The workspace comes from torch's
+            # allocator -- under capture from the graph's pool --, which aligns to 512 bytes; no host synchronisation
+            ws = None
+            if d_cube is not None:
+                ws = torch.empty(L.sky_det_workspace_size(b.f.height * b.f.width), device=cube.device, dtype=torch.uint8)
+            L.check(lib.emd_sky_backward_det(C.byref(b), L.ptr(ws), 0 if ws is None else ws.numel(), _stream()), "emd_sky_backward_det")
+        else:
+            L.check(lib.emd_sky_backward(C.byref(b), _stream()), "emd_sky_backward")
+        return (d_cube, d_fg, d_acc) + (None,) * 10
 
 
 def _camera_rays_params(camera):
@@ -134,10 +142,17 @@ def sky_ray_constants(K, world_view_transform):
 
 
 class SkyCubeMap(torch.nn.Module):
-    """S3Gaussian/scene/sky_cubemap.py:13-87.  `cfg` needs sky_resolution, sky_white_background, white_background."""
+    """S3Gaussian/scene/sky_cubemap.py:13-87.  `cfg` needs sky_resolution, sky_white_background, white_background.
 
-    def __init__(self, cfg, device="cuda"):
+    `deterministic` (class attribute, constructor keyword, or set on an instance): the cube map's gradient is summed in a pinned order without float
+    atomics -- bit-identical from run to run, across streams and under hipGraph replay.  Off by default."""
+
+    deterministic = False
+
+    def __init__(self, cfg, device="cuda", deterministic=None):
         super().__init__()
+        if deterministic is not None:
+            self.deterministic = bool(deterministic)
         self.cfg = cfg
         self.sky_resolution = cfg.sky_resolution
         eps = 1e-3
@@ -164,7 +179,7 @@ class SkyCubeMap(torch.nn.Module):
             a, threshold = acc[0].detach(), 1e-3
         fill = 1.0 if self.cfg.sky_white_background else 0.0
         sky, _ = _SkyOp.apply(self.sky_cube_map, None, a, None, _camera_rays_params(camera), jitter, H, W, L.SKY_CLAMP01, threshold,
-                              fill, False)
+                              fill, False, self.deterministic)
         return sky
 
 
@@ -180,15 +195,20 @@ def composite_s3g(sky_model: SkyCubeMap, camera, render, weight, is_train=False,
         return render * weight + sky * (1 - weight), sky
     fill = 1.0 if sky_model.cfg.sky_white_background else 0.0
     sky, out = _SkyOp.apply(sky_model.sky_cube_map, render, weight.reshape(H, W), None, _camera_rays_params(camera), jitter, H, W,
-                            L.SKY_CLAMP01 | L.SKY_BLEND_S3G, 1e-3, fill, True)
+                            L.SKY_CLAMP01 | L.SKY_BLEND_S3G, 1e-3, fill, True, sky_model.deterministic)
     return out, sky
 
 
 class EnvLight(torch.nn.Module):
-    """OmniRe/models/modules.py:174-208: cube map looked up along `image_infos["viewdirs"]` (rotated to OpenGL axes)."""
+    """OmniRe/models/modules.py:174-208: cube map looked up along `image_infos["viewdirs"]` (rotated to OpenGL axes).
+    `deterministic`: as for SkyCubeMap."""
 
-    def __init__(self, class_name="Sky", resolution=1024, device="cuda", **kwargs):
+    deterministic = False
+
+    def __init__(self, class_name="Sky", resolution=1024, device="cuda", deterministic=None, **kwargs):
         super().__init__()
+        if deterministic is not None:
+            self.deterministic = bool(deterministic)
         self.class_prefix = class_name + "#"
         self.to_opengl = torch.tensor([[1, 0, 0], [0, 0, 1], [0, -1, 0]], dtype=torch.float32, device=device)
         self.base = torch.nn.Parameter(0.5 * torch.ones(6, resolution, resolution, 3, device=device))
@@ -197,7 +217,7 @@ class EnvLight(torch.nn.Module):
         l = image_infos["viewdirs"]
         prefix = l.shape[:-1]
         d = (l.reshape(-1, 3) @ self.to_opengl.T).contiguous()
-        sky, _ = _SkyOp.apply(self.base, None, None, d, None, None, 1, d.shape[0], L.SKY_INTERLEAVED, -1.0, 0.0, False)
+        sky, _ = _SkyOp.apply(self.base, None, None, d, None, None, 1, d.shape[0], L.SKY_INTERLEAVED, -1.0, 0.0, False, self.deterministic)
         return sky.view(*prefix, -1)
 
     def get_param_groups(self):
@@ -212,5 +232,5 @@ def composite_add(env: EnvLight, image_infos, rgb_gaussians, opacity):
     d = (l.reshape(-1, 3) @ env.to_opengl.T).contiguous()
     P = d.shape[0]
     sky, out = _SkyOp.apply(env.base, rgb_gaussians.reshape(P, 3), opacity.reshape(P), d, None, None, 1, P,
-                            L.SKY_INTERLEAVED | L.SKY_BLEND_ADD, -1.0, 0.0, True)
+                            L.SKY_INTERLEAVED | L.SKY_BLEND_ADD, -1.0, 0.0, True, env.deterministic)
     return out.view(*prefix, 3), sky.view(*prefix, 3)

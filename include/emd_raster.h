@@ -11,7 +11,7 @@
  *   emd_raster_forward   <- GaussianRasterizer.forward(...)   S3Gaussian/gaussian_renderer/__init__.py:145-155
  *                           rasterization(...)                OmniRe/models/trainers/base.py:393-408
  *   emd_raster_backward  <- autograd of the same call         S3Gaussian/train.py:366
- *   emd_motion_forward / emd_motion_backward
+ *   emd_motion_forward / emd_motion_backward / emd_motion_backward_det
  *                        <- RigidNodes.transform_means/quats  OmniRe/models/nodes/rigid.py:478-568
  *                           DeformableNodes residual add      OmniRe/models/nodes/deformable.py:57-69
  *                           (when EMD_FLAG_MOTION is set the same transform is fused
@@ -398,6 +398,31 @@ int emd_motion_backward(int32_t n, const float* means, const float* quats, const
                         float* dL_dactor_pose /*[A,12] zeroed here*/, float* dL_dresidual_dx, float* dL_dresidual_dq,
                         void* hip_stream);
 
+/* ---- ABI 30 extension: the deterministic motion backward (opt-in; an entry point of its own, so that emd_motion_backward and its kernel are unchanged) ----
+ * emd_motion_backward with one difference: dL_dactor_pose is not accumulated with float atomics.  Every actor-bound point (actor_id >= 0) stores its
+ * twelve floats as row i of an [n, 12] buffer, a stable compacting sort lists the points per actor, and the lists are added with the association of
+ * emd_segmented_row_sum.  Contract: an actor's pose gradient is the sum of its points' rows in ASCENDING POINT INDEX -- chunks of EMD_SEG_CHUNK = 512,
+ * each summed in fp64 in ascending order from 0.0, the chunk sums added in ascending order in fp64 from 0.0, one rounding to fp32.  Actors without a
+ * point get zeros (dL_dactor_pose is zeroed here).  Nothing of it depends on workgroup order, the stream, other work on the device, or eager execution
+ * against hipGraph replay; no kernel of the mode uses an atomic or a device-scope fence.  The per-point outputs are those of emd_motion_backward, bit for
+ * bit.  Every argument check of emd_motion_backward applies; in addition 4 n <= 2^32 - 1 - 2048 (EMD_ERR_INVALID otherwise).
+ * det_ws: caller-owned, 256-byte aligned, never cleared; missing, misaligned or shorter than emd_motion_det_workspace_size(n) is EMD_ERR_WORKSPACE,
+ * decided before anything is launched.  When dL_dactor_pose is NULL no workspace is needed (det_ws may be NULL).
+ * Bytes of det_ws, m = max(n, 1), up(b) = b rounded up to 256, sort(m, g) as for emd_raster_det_workspace_size:
+ *     bytes = up(48 m) + sort(m, 16) + up(64) + 256
+ *             the [n, 12] pose rows, the sort by actor with the chunk sums, the count words
+ * emd_motion_det_workspace_size is host-only and returns 0 for an n outside the limit.  emd_motion_det_workspace_offsets gives the byte offsets inside
+ * det_ws of what a call with num_actors actors leaves there, for tests and profiles: out[0] the pose rows, [1] the raw keys (actor id of every point,
+ * 0xFFFFFFFF = static), [2] the sorted keys and [3] the sorted point indices -- the ping-pong pair that holds the result for this num_actors --,
+ * [4] the count words (uint32 [0] = points the sort kept), out[5] = the total, as emd_motion_det_workspace_size reports it. */
+size_t emd_motion_det_workspace_size(int32_t n);
+int emd_motion_det_workspace_offsets(int32_t n, int32_t num_actors, size_t out[6]);
+int emd_motion_backward_det(int32_t n, const float* means, const float* quats, const float* opacities,
+                            const EmdMotion* motion, const float* dL_dworld_means, const float* dL_dworld_quats,
+                            const float* dL_dopacities_out, float* dL_dmeans, float* dL_dquats, float* dL_dopacities,
+                            float* dL_dactor_pose /*[A,12] zeroed here*/, float* dL_dresidual_dx, float* dL_dresidual_dq,
+                            void* det_ws, size_t det_bytes, void* hip_stream);
+
 /* Spherical harmonics colour (no +0.5, no clamp): rgb = SH_deg(dirs / |dirs|) . coeffs */
 int emd_sh_forward(int32_t n, int32_t degree, int32_t sh_coeffs, const float* dirs /*[N,3]*/,
                    const float* coeffs /*[N,K,3]*/, float* rgb /*[N,3]*/, void* hip_stream);
@@ -524,6 +549,31 @@ typedef struct EmdSkyBwdArgs {
 
 int emd_sky_forward(const EmdSkyArgs* args, void* hip_stream);
 int emd_sky_backward(const EmdSkyBwdArgs* args, void* hip_stream);
+
+/* ---- ABI 30 extension: the deterministic sky backward (opt-in; an entry point of its own, so that EmdSkyBwdArgs, emd_sky_backward and its kernel are
+ * unchanged).  emd_sky_backward with one difference: dL_dcube is not accumulated through LDS windows and float atomics.  Tap k (0..3, the order of the
+ * bilinear footprint: (u0,v0), (u1,v0), (u0,v1), (u1,v1)) of pixel p stores the three floats w_k * dL/d(sky colour) as a row at slot e = k P + p, with
+ * P = height * width and p the row-major pixel index (for a direction list: the list index); a stable compacting sort lists the slots per texel and the
+ * lists are added with the association of emd_segmented_row_sum.  A tap contributes when its pixel is sampled (mask / threshold) and its weight is not
+ * zero (a cube corner's missing fourth tap has weight zero); a row of zeros is still a contribution.
+ * Contract: a texel's gradient is the sum of its contributions in ASCENDING (k, p) ORDER -- chunks of EMD_SEG_CHUNK = 512, each summed in fp64 in
+ * ascending order from 0.0, the chunk sums added in ascending order in fp64 from 0.0, one rounding to fp32.  Texels without a contribution are +0.0
+ * (dL_dcube is zeroed here).  Nothing of it depends on workgroup order, the stream, other work on the device, or eager execution against hipGraph
+ * replay; no kernel of the mode uses an atomic or a device-scope fence.  dL_dfg and dL_dacc are those of emd_sky_backward, bit for bit.  Both call
+ * shapes are served: the pinhole image (planar or interleaved, with or without jitter and camera_dev) and the direction list (height 1).
+ * Every argument check of emd_sky_backward applies; in addition 4 P <= 2^32 - 1 - 2048 and 6 resolution^2 <= 2^30 (EMD_ERR_INVALID otherwise).
+ * det_ws: caller-owned, 256-byte aligned, never cleared; missing, misaligned or shorter than emd_sky_det_workspace_size(P) is EMD_ERR_WORKSPACE,
+ * decided before anything is launched.  When dL_dcube is NULL no workspace is needed (det_ws may be NULL).
+ * Bytes of det_ws, m = 4 max(P, 1) slots, up(b) = b rounded up to 256, sort(m, g) as for emd_raster_det_workspace_size:
+ *     bytes = up(16 m) + sort(m, 16) + up(64) + 256
+ *             the rows at a pitch of 4 floats (three channels and a pad: one 16-byte store), the sort by texel with the chunk sums, the count words
+ * emd_sky_det_workspace_size is host-only and returns 0 for a P outside the limit.  emd_sky_det_workspace_offsets gives the byte offsets inside det_ws
+ * of what a call leaves there, for tests and profiles: out[0] the rows, [1] the raw keys (flat texel index of every slot, 0xFFFFFFFF = no contribution),
+ * [2] the sorted keys and [3] the sorted slots -- the ping-pong pair that holds the result for this resolution --, [4] the count words (uint32 [0] =
+ * slots the sort kept), out[5] = the total, as emd_sky_det_workspace_size reports it. */
+size_t emd_sky_det_workspace_size(int64_t num_pixels);
+int emd_sky_det_workspace_offsets(int64_t num_pixels, int32_t resolution, size_t out[6]);
+int emd_sky_backward_det(const EmdSkyBwdArgs* args, void* det_ws, size_t det_bytes, void* hip_stream);
 
 /* ---- image-loss tail -----------------------------------------------------------------
  * loss = L1 + lambda_depth * depth L2 + lambda_dssim * (1 - SSIM 11x11) + lambda_sky * sky BCE, with the gradients with
