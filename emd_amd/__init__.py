@@ -8,4 +8,7 @@ from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, Raste
 
 from .graphs import StepGraphs, StepInputs  # noqa: F401
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "RasterCall", "RasterConfig", "RasterOptions", "StepGraphs", "StepInputs"]
+from .smpl import SMPL_PARENTS, SkinLayout, joint_transforms, posed_skin_gaussians, skin_gaussians  # noqa: F401
+
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "RasterCall", "RasterConfig", "RasterOptions", "StepGraphs", "StepInputs",
+           "SMPL_PARENTS", "SkinLayout", "joint_transforms", "posed_skin_gaussians", "skin_gaussians"]

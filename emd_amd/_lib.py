@@ -16,6 +16,9 @@ SETTINGS_DEV_FLOATS = 38
 TILE = 16
 ACTOR_STRIDE = 12
 BWD_PAYLOAD = 12
+SKIN_JOINTS = 24         # EMD_SKIN_JOINTS
+SKIN_CHUNK = 256         # EMD_SKIN_CHUNK: most points of one chunk of the skinning point layout (csrc/skinning.hip)
+SKIN_PARTIAL_FLOATS = 291  # EMD_SKIN_PARTIAL_FLOATS: one chunk's slab of the skinning backward, 24 x 12 sums of dL/dA + 3 of dL/dtrans
 SEG_CHUNK = 512          # EMD_SEG_CHUNK: chunk length of the pinned association of the segmented row sum (csrc/segsum.h)
 
 
@@ -234,6 +237,21 @@ class EmdSegSumArgs(C.Structure):
                 ("out", _f), ("out_pitch", C.c_int32), ("reserved", C.c_int32), ("partials", _f), ("partial_bytes", C.c_size_t)]
 
 
+class EmdJointChainArgs(C.Structure):
+    _fields_ = [("num_instances", C.c_int32), ("reserved", C.c_int32), ("theta", _f), ("joints", _f), ("parents", _f), ("canon_inv", _f), ("A", _f)]
+
+
+class EmdSkinArgs(C.Structure):
+    _fields_ = [("num_points", C.c_int32), ("num_instances", C.c_int32), ("num_chunks", C.c_int32), ("reserved", C.c_int32), ("means", _f),
+                ("quats", _f), ("opacities", _f), ("ids", _f), ("weights", _f), ("A", _f), ("trans", _f), ("valid", _f), ("order", _f),
+                ("chunks", _f), ("world_means", _f), ("world_quats", _f), ("opacities_out", _f)]
+
+
+class EmdSkinGrads(C.Structure):
+    _fields_ = [("g_world_means", _f), ("g_world_quats", _f), ("g_opacities_out", _f), ("d_means", _f), ("d_quats", _f), ("d_opacities", _f),
+                ("d_weights", _f), ("partials", _f)]
+
+
 # every symbol include/emd_raster.h declares
 EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_size", "emd_raster_forward",
                     "emd_raster_backward", "emd_raster_export_binning", "emd_raster_export_geometry",
@@ -252,7 +270,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_raster_det_workspace_size", "emd_raster_det_layout", "emd_segmented_row_sum_workspace", "emd_segmented_row_sum",
                     "emd_hexplane_det_workspace_size", "emd_hexplane_det_workspace_offsets",
                     "emd_sky_det_workspace_size", "emd_sky_det_workspace_offsets", "emd_sky_backward_det",
-                    "emd_motion_det_workspace_size", "emd_motion_det_workspace_offsets", "emd_motion_backward_det")
+                    "emd_motion_det_workspace_size", "emd_motion_det_workspace_offsets", "emd_motion_backward_det",
+                    "emd_joint_chain_forward", "emd_joint_chain_backward", "emd_skin_forward", "emd_skin_backward")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -368,6 +387,10 @@ def load():
     lib.emd_segmented_row_sum_workspace.argtypes = [C.c_int64, C.c_int32]
     lib.emd_segmented_row_sum_workspace.restype = C.c_size_t
     lib.emd_segmented_row_sum.argtypes = [C.POINTER(EmdSegSumArgs), C.c_void_p]
+    lib.emd_joint_chain_forward.argtypes = [C.POINTER(EmdJointChainArgs), C.c_void_p]
+    lib.emd_joint_chain_backward.argtypes = [C.POINTER(EmdJointChainArgs)] + [C.c_void_p] * 7
+    lib.emd_skin_forward.argtypes = [C.POINTER(EmdSkinArgs), C.c_void_p]
+    lib.emd_skin_backward.argtypes = [C.POINTER(EmdSkinArgs), C.POINTER(EmdSkinGrads), C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p

@@ -5,6 +5,7 @@ per-actor rigid transform, opacity x validity of (frame, actor), SH colour on DE
 exp scales -- the dictionary `collect_gaussians` (models/trainers/base.py:342-383) concatenates over classes before the
 `rasterization` call.  `deformable_gaussians` is DeformableNodes.get_gaussians (models/nodes/deformable.py:49-114): the learned
 residual of `ConditionalDeformNetwork` is added to the (detached) canonical means and to the normalised quaternions first.
+`smpl_gaussians` is SMPLNodes.get_gaussians (models/nodes/smpl.py): the per-point blend of 24 joint transforms of `emd_amd.smpl`.
 Two HIP launches per class (`emd_motion_forward`, `emd_sh_forward`) instead of the reference's Python loop over actors; the
 NaN / Inf guard of the reference (ten `.any()` host syncs per class and step) is one reduction and one sync, and can be
 switched off.  (When the caller uses this repository's GaussianRasterizer directly, the same transform and SH evaluation are
@@ -41,6 +42,23 @@ def rigid_gaussians(means, quats, opacity_logits, log_scales, features_dc, featu
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
     world_means, world_quats, opac = transform_gaussians(means, quats, torch.sigmoid(opacity_logits), ids, actor_pose,
                                                          deterministic=deterministic)
+    gs = dict(_means=world_means, _opacities=opac.reshape(-1, 1),
+              _rgbs=_colors(world_means, features_dc, features_rest, camera_center, sh_degree, step, sh_degree_interval),
+              _scales=torch.exp(log_scales), _quats=world_quats)
+    if check_finite:
+        _check_finite(gs, step)
+    return gs
+
+
+def smpl_gaussians(means, quats, opacity_logits, log_scales, features_dc, features_rest, point_ids, weights, theta, joints, trans, valid,
+                   camera_center, canon_inv=None, sh_degree=3, step=0, sh_degree_interval=1000, check_finite=True, layout=None):
+    """SMPLNodes.get_gaussians (models/nodes/smpl.py): as rigid_gaussians, with the per-point blend of 24 joint transforms in place of one
+    actor pose.  theta [P,24,4]: the frame's joint quaternions, row 0 the global orientation; joints [P,24,3]: rest joints; trans [P,3] and
+    valid [P]: the frame's instance translations and validity; weights [N,24]: the points' skinning weights; layout: a `smpl.SkinLayout`
+    kept between steps.  Two HIP launches each way for the pose and the skinning (`smpl.posed_skin_gaussians`), then `emd_sh_forward`."""
+    from .smpl import posed_skin_gaussians
+    world_means, world_quats, opac = posed_skin_gaussians(means, quats, torch.sigmoid(opacity_logits), point_ids, weights, theta, joints, trans,
+                                                          valid=valid, canon_inv=canon_inv, layout=layout)
     gs = dict(_means=world_means, _opacities=opac.reshape(-1, 1),
               _rgbs=_colors(world_means, features_dc, features_rest, camera_center, sh_degree, step, sh_degree_interval),
               _scales=torch.exp(log_scales), _quats=world_quats)

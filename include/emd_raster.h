@@ -31,6 +31,9 @@
  *   emd_adam_step                       <- optimizer.step()              S3Gaussian/scene/gaussian_model.py:188-201, train.py:428
  *   emd_knn / emd_knn_reverse           <- simple_knn distCUDA2, o3d_knn S3Gaussian/scene/gaussian_model.py:152-181 (create_from_pcd), train.py:326-337
  *   emd_embed_reg_forward / backward    <- weighted_l2_loss_v2 over the neighbour table   S3Gaussian/train.py:326-337
+ *   emd_joint_chain_forward / backward, emd_skin_forward / backward
+ *                                       <- SMPLTemplate.forward          OmniRe/models/human_body.py:158-181
+ *                                          SMPLNodes.transform_means_and_quats  OmniRe/models/nodes/smpl.py:438-532
  *   emd_sh_grad_from_factors            (multi-GPU: rebuilds the SH gradient from all-gathered rank-one factors; no reference counterpart)
  *   emd_compact_rows / emd_scatter_rows (multi-GPU: visibility-compacted gradient rows for 2 / 4 ranks; no reference counterpart)
  *
@@ -58,7 +61,8 @@ extern "C" {
 #endif
 
 /* (the deterministic backward extends ABI 30 compatibly -- a new flag bit, two fields at the END of EmdBwdArgs that are read only when the flag
- * is set, new entry points -- so a caller built against the earlier ABI 30 header keeps working and the number stays) */
+ * is set, new entry points -- so a caller built against the earlier ABI 30 header keeps working and the number stays; the skinning entry points
+ * at the end of this header are the same kind of extension: new functions and structs only) */
 #define EMD_ABI_VERSION 30
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
@@ -1100,6 +1104,81 @@ typedef struct EmdSegSumArgs {
 } EmdSegSumArgs;
 size_t emd_segmented_row_sum_workspace(int64_t n_cap, int32_t width);
 int emd_segmented_row_sum(const EmdSegSumArgs* args, void* hip_stream);
+
+/* ---- ABI 30 extension (new entry points and structs only, so the number stays): linear-blend skinning of SMPL pedestrian nodes (csrc/skinning.hip) ----
+ * OmniRe's fourth Gaussian class: a pedestrian point moves by a per-point blend of J = 24 joint transforms.  Two launches each way, no atomics:
+ * every gradient is a fixed function of the call's inputs (bit-reproducible from run to run, across streams and under hipGraph replay); there is
+ * no other mode.  Quaternions are (w, x, y, z); R(q) is the rotation of q / |q|; 3x4 transforms are row-major [r00 r01 r02 t0 | r10 ... | r20 ...].
+ *
+ * Joint chain (SMPLTemplate.forward, human_body.py:158-181), P instances, `parents` a DEVICE int32[24] with parents[0] = -1, parents[j] < j (an
+ * entry outside [-1, j - 1] is held to that range; -1 makes joint j a root):
+ *     L_j = [R(theta_j) | joints_j - joints_parent(j)]   (a root: joints_j),   G_root = L_root,   G_j = G_parent(j) L_j,
+ *     A_j = [G_j.R | G_j.t - G_j.R joints_j],   and A_j <- A_j o canon_inv_j (affine composition) when canon_inv != NULL.
+ * theta [P,24,4] is unnormalised (row 0: the global orientation) and receives the gradient, through the normalisation; joints [P,24,3] and
+ * canon_inv [P,24,12] are constants. */
+#define EMD_SKIN_JOINTS 24
+#define EMD_SKIN_CHUNK 256                 /* most points of a chunk of the point layout */
+#define EMD_SKIN_PARTIAL_FLOATS 291        /* one chunk's slab: 24 x 12 sums of dL/dA and 3 of dL/dtrans */
+typedef struct EmdJointChainArgs {
+    int32_t num_instances, reserved;
+    const float* theta;
+    const float* joints;
+    const int32_t* parents;
+    const float* canon_inv;                /* or NULL */
+    float* A;                              /* [P,24,12]: written by the forward, not read by the backward */
+} EmdJointChainArgs;
+int emd_joint_chain_forward(const EmdJointChainArgs* args, void* hip_stream);
+/* dL/dA reaches the backward in one of two forms (exactly one is non-NULL): dL_dA [P,24,12] dense, or `partials`, the chunk slabs emd_skin_backward
+ * left, with instance_chunk_start int32[P+1] (instance p owns the chunks [start[p], start[p+1]) of the table): the slabs of an instance are added in
+ * ASCENDING CHUNK ORDER from 0.0 in fp32, and the sums are also stored to dL_dA_out [P,24,12] / dL_dtrans [P,3] when those are non-NULL.  Then the
+ * chain runs in reverse, joint s adding into its parent for s = 23 .. 1 (a parent receives its children in descending joint index), and
+ * dL_dtheta [P,24,4] is written in full.  dL_dtheta == NULL: only the sum of the slabs is wanted (theta / joints / parents are not read). */
+int emd_joint_chain_backward(const EmdJointChainArgs* args, const float* dL_dA, const float* partials, const int32_t* instance_chunk_start,
+                             float* dL_dA_out, float* dL_dtrans, float* dL_dtheta, void* hip_stream);
+
+/* Skinning (transform_means_and_quats, smpl.py:438-532).  For a point with ids[i] = p in [0, P):
+ *     T_i = sum_j weights[i,j] A[p,j]                 (fp32, ascending j, from 0.0)
+ *     world_mean = T_i.R mean + T_i.t + trans[p]
+ *     world_quat = quat_act(quat_mult(m2q(T_i.R), quat_act(quat)))
+ *     opacity_out = opacity * valid[p]                (valid: P floats, NULL = all 1)
+ * m2q is pytorch3d's matrix_to_quaternion on the blended (not orthogonal) block: q_abs = sqrt(max(0, .)) of 1+m00+m11+m22, 1+m00-m11-m22,
+ * 1-m00+m11-m22, 1-m00-m11+m22; the candidate of the largest q_abs (the lowest index on a tie) divided by 2 max(q_abs, 0.1); quat_act is
+ * F.normalize (eps 1e-12).  A point with ids[i] < 0 (or >= P) is returned as emd_motion_forward returns a static point: unchanged.
+ * The forward walks the points in index order and reads neither `order` nor `chunks`.  The backward is driven by the point layout: `chunks` is a
+ * DEVICE int32 [num_chunks, 3] table of (instance or -1, first, count <= EMD_SKIN_CHUNK): chunk c owns the points order[first .. first + count)
+ * (order == NULL: the identity), all of that instance; an instance's chunks are consecutive and follow its points in ascending position.  Per-point
+ * gradients are stored directly (d_weights only when non-NULL; rows of unbound points get pass-through gradients and zero d_weights); chunk c's
+ * sums of weights (x) dL/dT and of dL/dworld_mean, added in ASCENDING POSITION from 0.0 in fp32, are stored to partials[c * 291 ..] (chunks of
+ * instance -1 store nothing) for emd_joint_chain_backward.  Every point must lie in exactly one chunk; entries that point outside the call's
+ * arrays are skipped, never followed.  Checked on the host: ceil(N / 256) <= num_chunks <= N / 256 + P + 1.  No host synchronisation. */
+typedef struct EmdSkinArgs {
+    int32_t num_points, num_instances, num_chunks, reserved;
+    const float* means;
+    const float* quats;
+    const float* opacities;
+    const int32_t* ids;
+    const float* weights;                  /* [N,24] dense, 16-byte aligned */
+    const float* A;
+    const float* trans;
+    const float* valid;                    /* or NULL */
+    const int32_t* order;                  /* or NULL */
+    const int32_t* chunks;                 /* may be NULL for the forward */
+    float* world_means;
+    float* world_quats;
+    float* opacities_out;
+} EmdSkinArgs;
+typedef struct EmdSkinGrads {
+    const float* g_world_means;
+    const float* g_world_quats;
+    const float* g_opacities_out;
+    float* d_means;
+    float* d_quats;
+    float* d_opacities;
+    float* d_weights;                      /* or NULL */
+    float* partials;                       /* [num_chunks, EMD_SKIN_PARTIAL_FLOATS], needs no clearing */
+} EmdSkinGrads;
+int emd_skin_forward(const EmdSkinArgs* args, void* hip_stream);
+int emd_skin_backward(const EmdSkinArgs* args, const EmdSkinGrads* grads, void* hip_stream);
 
 #ifdef __cplusplus
 }
