@@ -127,6 +127,15 @@ class EmdHexGrads(C.Structure):
                 ("det_ws", C.c_void_p), ("det_bytes", C.c_size_t), ("det_keep_plane", C.c_uint32)]       # (read only with HEX_FLAG_DETERMINISTIC)
 
 
+PLANE_REG_SEG = 32       # EMD_PLANE_REG_SEG: rows of H one workgroup of the plane regularisers owns (csrc/plane_reg.hip)
+
+
+class EmdPlaneRegArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("num_scales", C.c_int32), ("res", (C.c_int32 * 4) * HEX_MAX_SCALES), ("planes", (_f * 6) * HEX_MAX_SCALES),
+                ("plane_tv_weight", C.c_float), ("time_smoothness_weight", C.c_float), ("l1_time_planes_weight", C.c_float), ("reserved", C.c_float),
+                ("out", _f), ("g", _f), ("dL_dplanes", (_f * 6) * HEX_MAX_SCALES)]
+
+
 class EmdDeformInArgs(C.Structure):
     _fields_ = [("num_points", C.c_int32), ("num_freqs_x", C.c_int32), ("num_freqs_t", C.c_int32), ("embed_dim", C.c_int32),
                 ("ld", C.c_int32), ("reserved", C.c_int32), ("means", _f), ("point_ids", _f), ("inst_size", _f), ("inst_embed", _f),
@@ -271,7 +280,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_hexplane_det_workspace_size", "emd_hexplane_det_workspace_offsets",
                     "emd_sky_det_workspace_size", "emd_sky_det_workspace_offsets", "emd_sky_backward_det",
                     "emd_motion_det_workspace_size", "emd_motion_det_workspace_offsets", "emd_motion_backward_det",
-                    "emd_joint_chain_forward", "emd_joint_chain_backward", "emd_skin_forward", "emd_skin_backward")
+                    "emd_joint_chain_forward", "emd_joint_chain_backward", "emd_skin_forward", "emd_skin_backward",
+                    "emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -391,6 +401,10 @@ def load():
     lib.emd_joint_chain_backward.argtypes = [C.POINTER(EmdJointChainArgs)] + [C.c_void_p] * 7
     lib.emd_skin_forward.argtypes = [C.POINTER(EmdSkinArgs), C.c_void_p]
     lib.emd_skin_backward.argtypes = [C.POINTER(EmdSkinArgs), C.POINTER(EmdSkinGrads), C.c_void_p]
+    lib.emd_plane_reg_workspace_size.argtypes = [C.POINTER(EmdPlaneRegArgs)]
+    lib.emd_plane_reg_workspace_size.restype = C.c_size_t
+    lib.emd_plane_reg_forward.argtypes = [C.POINTER(EmdPlaneRegArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_plane_reg_backward.argtypes = [C.POINTER(EmdPlaneRegArgs), C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p

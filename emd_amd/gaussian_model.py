@@ -180,6 +180,31 @@ class GaussianModel:
             t = self._knn_table = KnnTable(self._xyz, k=k, weight_fn=weight_fn)
         return t
 
+    # ---- HexPlane regularisers (gaussian_model.py:745-784) --------------------------------------------------------------------------
+    def _hexplane_field(self):
+        net = getattr(self._deformation, "deformation_net", None)
+        if net is None or getattr(net, "grid", None) is None:
+            raise RuntimeError("the plane regularisers read self._deformation.deformation_net.grid: this GaussianModel was built without a "
+                               "deformation network (pass deformation=deform_network(...))")
+        return net.grid
+
+    def _plane_regulation(self):
+        """Mean squared second difference of the spatial planes (0, 1, 3), summed over planes and scales."""
+        return self._hexplane_field().regulation(0.0, 0.0, 1.0)
+
+    def _time_regulation(self):
+        """The same on the time planes (2, 4, 5)."""
+        return self._hexplane_field().regulation(1.0, 0.0, 0.0)
+
+    def _l1_regulation(self):
+        """mean |1 - P| of the time planes, summed over planes and scales."""
+        return self._hexplane_field().regulation(0.0, 1.0, 0.0)
+
+    def compute_regulation(self, time_smoothness_weight, l1_time_planes_weight, plane_tv_weight):
+        """plane_tv_weight * _plane_regulation() + time_smoothness_weight * _time_regulation() + l1_time_planes_weight * _l1_regulation() as ONE
+        autograd node: two launches forward and one backward for all planes (emd_amd.hexplane.plane_regulation)."""
+        return self._hexplane_field().regulation(time_smoothness_weight, l1_time_planes_weight, plane_tv_weight)
+
     def training_setup(self, training_args):
         """The ten named groups of gaussian_model.py:188-201 (deformation / grid / sky only when those modules are attached); the
         optimiser is emd_amd.optim.Adam (one HIP launch per step), `lr=0.0, eps=1e-15` as in the reference."""

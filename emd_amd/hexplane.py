@@ -140,6 +140,75 @@ class _HexLookup(torch.autograd.Function):
         return (d_pts, d_times, None, None, None, *grads)
 
 
+class _PlaneReg(torch.autograd.Function):
+    """One autograd node over all planes of all scales: `emd_plane_reg_forward` (two launches) and `emd_plane_reg_backward` (one)."""
+
+    @staticmethod
+    def forward(ctx, weights, *planes):
+        if any(p.device.type != "cuda" for p in planes):
+            raise L.EmdError("HexPlane regularisers need planes on a ROCm device; there is no CPU path")
+        lib = L.load()
+        if not planes or len(planes) % 6 or any(p.dim() != 4 or p.shape[0] != 1 for p in planes):
+            raise L.EmdError(f"plane regularisers: {len(planes)} planes, expected six [1, C, H, W] planes per scale")
+        S, Cc, dev = len(planes) // 6, planes[0].shape[1], planes[0].device
+        if S > L.HEX_MAX_SCALES:
+            raise L.EmdError(f"plane regularisers: {S} scales, at most {L.HEX_MAX_SCALES}")
+        # [H][W][C] fp32 memory: the parameter's own when it is fp32 and channel-last (what init_grid_param creates), a copy of anything else (as the
+        # lookup copies)
+        cl = [q if (q.dtype == torch.float32 and q.is_contiguous(memory_format=torch.channels_last)) else q.float().contiguous(memory_format=torch.channels_last)
+              for q in (p.detach() for p in planes)]
+        a = L.EmdPlaneRegArgs()
+        a.channels, a.num_scales = Cc, S
+        a.time_smoothness_weight, a.l1_time_planes_weight, a.plane_tv_weight = weights
+        for s in range(S):
+            g = cl[s * 6:s * 6 + 6]
+            res = (g[0].shape[3], g[0].shape[2], g[1].shape[2], g[2].shape[2])
+            for k in range(4):
+                a.res[s][k] = res[k]
+            for p, (ca, cb) in enumerate(PAIRS):
+                if tuple(g[p].shape) != (1, Cc, res[cb], res[ca]):
+                    raise L.EmdError(f"plane regularisers: plane {p} of scale {s} is {tuple(g[p].shape)}, not [1, {Cc}, {res[cb]}, {res[ca]}]")
+                a.planes[s][p] = g[p].data_ptr()
+        out = torch.empty(4, device=dev, dtype=torch.float32)
+        # the workgroups' partial sums: caller-owned, never cleared (a captured step takes it from the graph's pool)
+        ws = torch.empty(max(int(lib.emd_plane_reg_workspace_size(C.byref(a))), 8), device=dev, dtype=torch.uint8)
+        a.out = out.data_ptr()
+        L.check(lib.emd_plane_reg_forward(C.byref(a), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                "emd_plane_reg_forward")
+        a.out = None
+        ctx.args, ctx.keep = a, cl
+        ctx.shapes = [tuple(p.shape) for p in planes]
+        loss, terms = out[0], out[1:]
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_terms):
+        a = ctx.args
+        g_loss = g_loss.contiguous().float()
+        # every element of every plane's gradient is written by the kernel: one uncleared buffer, the gradients its channel-last views
+        flat = torch.empty(sum(int(np.prod(s)) for s in ctx.shapes), device=g_loss.device, dtype=torch.float32)
+        grads, off, base = [], 0, flat.data_ptr()
+        for i, (_, c, h, w) in enumerate(ctx.shapes):
+            grads.append(flat.as_strided((1, c, h, w), (c * h * w, 1, w * c, c), off))       # [1, C, H, W] over [H][W][C] memory, like the planes
+            a.dL_dplanes[i // 6][i % 6] = base + 4 * off
+            off += c * h * w
+        a.g = g_loss.data_ptr()
+        L.check(L.load().emd_plane_reg_backward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_plane_reg_backward")
+        return (None, *grads)
+
+
+def plane_regulation(grids, time_smoothness_weight, l1_time_planes_weight, plane_tv_weight, return_terms=False):
+    """compute_regulation of S3Gaussian/scene/gaussian_model.py:745-784 over `grids` (a `HexPlaneField.grids`: per scale the six planes of PAIRS):
+        loss = plane_tv_weight * tv + time_smoothness_weight * ts + l1_time_planes_weight * l1
+    tv / ts: the mean squared second difference along H of the spatial planes (0, 1, 3) / the time planes (2, 4, 5), summed over planes and scales;
+    l1: mean |1 - P| of the time planes, likewise summed.  Returns the 0-dim loss, with `return_terms` also the detached [3] tensor (tv, ts, l1).
+    The weights are Python numbers.  Bit-reproducible, forward and backward (csrc/plane_reg.hip)."""
+    planes = [p for gp in grids for p in gp]
+    loss, terms = _PlaneReg.apply((float(time_smoothness_weight), float(l1_time_planes_weight), float(plane_tv_weight)), *planes)
+    return (loss, terms) if return_terms else loss
+
+
 def init_grid_param(grid_nd, in_dim, out_dim, reso, a=0.1, b=0.5):
     """S3Gaussian/scene/hexplane.py:48-70"""
     assert in_dim == len(reso) and grid_nd == 2 and in_dim == 4, "the HIP lookup implements the 4-D, plane (2-D) configuration"
@@ -319,3 +388,7 @@ class HexPlaneField(nn.Module):
 
     def forward(self, pts, timestamps=None):
         return self.get_density(pts, timestamps)
+
+    def regulation(self, time_smoothness_weight, l1_time_planes_weight, plane_tv_weight, return_terms=False):
+        """The plane regularisers of the fine stage over this field's planes (`plane_regulation`)."""
+        return plane_regulation(self.grids, time_smoothness_weight, l1_time_planes_weight, plane_tv_weight, return_terms)

@@ -34,6 +34,7 @@
  *   emd_joint_chain_forward / backward, emd_skin_forward / backward
  *                                       <- SMPLTemplate.forward          OmniRe/models/human_body.py:158-181
  *                                          SMPLNodes.transform_means_and_quats  OmniRe/models/nodes/smpl.py:438-532
+ *   emd_plane_reg_forward / backward    <- compute_regulation            S3Gaussian/scene/gaussian_model.py:745-784
  *   emd_sh_grad_from_factors            (multi-GPU: rebuilds the SH gradient from all-gathered rank-one factors; no reference counterpart)
  *   emd_compact_rows / emd_scatter_rows (multi-GPU: visibility-compacted gradient rows for 2 / 4 ranks; no reference counterpart)
  *
@@ -62,7 +63,7 @@ extern "C" {
 
 /* (the deterministic backward extends ABI 30 compatibly -- a new flag bit, two fields at the END of EmdBwdArgs that are read only when the flag
  * is set, new entry points -- so a caller built against the earlier ABI 30 header keeps working and the number stays; the skinning entry points
- * at the end of this header are the same kind of extension: new functions and structs only) */
+ * and the plane regularisers at the end of this header are the same kind of extension: new functions and structs only) */
 #define EMD_ABI_VERSION 30
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
@@ -1179,6 +1180,43 @@ typedef struct EmdSkinGrads {
 } EmdSkinGrads;
 int emd_skin_forward(const EmdSkinArgs* args, void* hip_stream);
 int emd_skin_backward(const EmdSkinArgs* args, const EmdSkinGrads* grads, void* hip_stream);
+
+/* ---- ABI 30 extension (new entry points and a struct only, so the number stays): the HexPlane regularisers (csrc/plane_reg.hip) ----
+ * compute_regulation of S3Gaussian/scene/gaussian_model.py:745-784 (the K-Planes / 4DGaussians formulation) over all planes of all scales: two
+ * launches forward, one backward, no float atomics.  A plane is [1, C, H, W] in channel-last memory, [H][W][C] floats, exactly as EmdHexArgs.planes:
+ * planes[s][p] belongs to the pair (a, b) = (0,1),(0,2),(0,3),(1,2),(1,3),(2,3) with W = res[s][a], H = res[s][b]; the spatial planes are p = 0, 1, 3,
+ * the time planes p = 2, 4, 5, on which H runs along time.
+ *     d1[c,h,w] = x[c,h+1,w] - x[c,h,w]            h in [0, H-2]
+ *     d2[c,h,w] = d1[c,h+1,w] - d1[c,h,w]          h in [0, H-3]          (along H only, as the reference)
+ *     smooth(P) = sum(d2^2) / (C (H-2) W)          l1(P) = sum(|1 - x|) / (C H W)
+ *     tv = sum over scales, p in {0,1,3} of smooth(P)    ts = sum over scales, p in {2,4,5} of smooth(P)    l1 = sum over scales, p in {2,4,5} of l1(P)
+ *     loss = plane_tv_weight * tv + time_smoothness_weight * ts + l1_time_planes_weight * l1
+ * Forward: out[0..3] = loss, tv, ts, l1 (the terms unweighted).  A lane adds at most EMD_PLANE_REG_SEG squares per accumulator in fp32; from there on
+ * every sum is fp64, in a fixed order (lanes in a fixed tree, a plane's workgroups in ascending order, the planes in ascending order), so the four
+ * floats are bit-identical from run to run, across streams and under hipGraph replay.  `workspace`: emd_plane_reg_workspace_size(args) bytes,
+ * 8-byte aligned, needs no clearing (the size is a function of channels, num_scales and res alone; 0 for arguments the forward would refuse).
+ * Backward, with g [1] = dL/dloss on the device and d2 = 0 outside [0, H-3]:
+ *     d smooth / d x[c,h,w] = 2 / (C (H-2) W) * ((d2[h] - d2[h-1]) - (d2[h-1] - d2[h-2]))
+ *     d l1     / d x[c,h,w] = sign(x - 1) / (C H W),   sign(0) = 0       (time planes start at exactly 1)
+ * Both stencils are formed as differences of differences, as written: values that sit within a few percent of 1 subtract exactly.  Every element
+ * of every dL_dplanes[s][p] (channel-last like the plane) is WRITTEN exactly once: no zero fill by the caller; spatial planes receive
+ * g * plane_tv_weight * d smooth, time planes g * (time_smoothness_weight * d smooth + l1_time_planes_weight * d l1).
+ * Neither W * C nor a pointer needs to be a multiple of 16 bytes (4-byte alignment suffices; 16-byte aligned planes with W * C % 4 == 0 take the
+ * wide loads).  1 <= channels, res >= 1, H < 3 on any plane (res[s][1], res[s][2] or res[s][3] below 3) is EMD_ERR_INVALID: the reference
+ * returns NaN there.  No host synchronisation. */
+#define EMD_PLANE_REG_SEG 32               /* rows of H one workgroup owns (it reads 2 more forward, 4 more backward) */
+typedef struct EmdPlaneRegArgs {
+    int32_t channels, num_scales;
+    int32_t res[EMD_HEX_MAX_SCALES][4];          /* per scale: resolution along x, y, z, t */
+    const float* planes[EMD_HEX_MAX_SCALES][6];
+    float plane_tv_weight, time_smoothness_weight, l1_time_planes_weight, reserved;
+    float* out;                                  /* forward: [4] loss, tv, ts, l1 */
+    const float* g;                              /* backward: [1] dL/dloss */
+    float* dL_dplanes[EMD_HEX_MAX_SCALES][6];    /* backward */
+} EmdPlaneRegArgs;
+size_t emd_plane_reg_workspace_size(const EmdPlaneRegArgs* args);
+int emd_plane_reg_forward(const EmdPlaneRegArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
+int emd_plane_reg_backward(const EmdPlaneRegArgs* args, void* hip_stream);
 
 #ifdef __cplusplus
 }
