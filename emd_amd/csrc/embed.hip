@@ -12,9 +12,14 @@
 //                       models/modules.py:318-366,430-437).  The reference builds it from 43 tensors and two concats.
 //  k_deform_input_bwd   gradient of that matrix back to the actor embedding table (positions and time are detached there).
 // Launch-latency / HBM-write bound; nothing here is reused.
+// The per-actor chain (embedding sums -> track heads -> pose row) has a one-launch form (k_tracked_pose) and a three-launch form
+// (k_track_embed_sum[_seg], k_track_heads, k_actor_pose_* of standalone_ops.hip) that must agree bit for bit.  Their arithmetic is one source text:
+// te_* (temporal sampling), segment_sum, heads_eval / heads_backward below, and pose_row_forward / pose_row_backward in quat_math.h.  Each kernel
+// keeps its own loads, stores, clears and launch shape.
 #include <string.h>
 
 #include "common.h"
+#include "quat_math.h"
 
 namespace {
 
@@ -48,12 +53,109 @@ __device__ __forceinline__ void resized_row(int r, int k, int rows, int* h0, int
     *l0 = 1.f - *l1;
 }
 
+// the sample of the k-row resize at time t: the two resized rows around it (each two source rows ha / hb with weights la / lb) and their weights
+struct TeSample { int ha[2], hb[2]; float la[2], lb[2], wy0, wy1; bool in1; };      // in1: the row past the end contributes nothing
+
+__device__ __forceinline__ TeSample te_rows(float t, int k, int rows) {
+#pragma clang fp contract(off)
+    TeSample s;
+    float my;
+    const float iy = reflect_coord((t - 0.5f) * 2.f, k, &my);
+    const float y0f = floorf(iy);
+    const int y0 = (int)y0f, y1 = y0 + 1;
+    s.wy1 = iy - y0f; s.wy0 = 1.f - s.wy1;
+    resized_row(min(y0, k - 1), k, rows, &s.ha[0], &s.hb[0], &s.la[0], &s.lb[0]);
+    resized_row(min(y1, k - 1), k, rows, &s.ha[1], &s.hb[1], &s.la[1], &s.lb[1]);
+    s.in1 = y1 <= k - 1;
+    return s;
+}
+
+// column j of a sample: the reference samples it at x = (j / (dim-1) - 0.5) * 2, which un-normalises to j up to rounding
+struct TeCol { int x0, x1; float wx0, wx1; bool inx1; };
+
+__device__ __forceinline__ TeCol te_col(int j, int dim) {
+#pragma clang fp contract(off)
+    TeCol c;
+    float mx;
+    const float gx = dim > 1 ? ((float)j / (float)(dim - 1) - 0.5f) * 2.f : -1.f;
+    const float ix = reflect_coord(gx, dim, &mx);
+    const float x0f = floorf(ix);
+    c.x0 = (int)x0f; c.x1 = c.x0 + 1;
+    c.wx1 = ix - x0f; c.wx0 = 1.f - c.wx1;
+    c.inx1 = c.x1 <= dim - 1;
+    return c;
+}
+
+// the eight taps of a sample, unconditionally (a tap the sample does not use -- the row past the table's end, the column past its width -- is read
+// from a valid neighbour and selected away): with the loads inside the row loop's branches each row waited for its own round trip
+__device__ __forceinline__ void te_taps(const float* __restrict__ weight, int dim, const TeSample& s, const TeCol& c, float (&wv)[2][4]) {
+    const int x1c = c.inx1 ? c.x1 : c.x0;
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        wv[r][0] = weight[s.ha[r] * dim + c.x0]; wv[r][1] = weight[s.hb[r] * dim + c.x0];
+        wv[r][2] = weight[s.ha[r] * dim + x1c]; wv[r][3] = weight[s.hb[r] * dim + x1c];
+    }
+}
+
+// the bilinear blend of a sample's eight taps.  ONE function without contraction for every caller: the one-launch actor chain (te_column2) and the
+// three-launch path (te_column) must produce the same bits (tests/test_motion_sh_gpu.py), and with contraction left to the compiler the two
+// inlined copies were fused differently.
+__device__ __forceinline__ float te_eval(const TeSample& s, const float (&wv)[2][4], const TeCol& c) {
+#pragma clang fp contract(off)
+    float out = 0.f;
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const float wy = r ? s.wy1 : s.wy0;
+        const float v0 = s.la[r] * wv[r][0] + s.lb[r] * wv[r][1];
+        const float v1 = c.inx1 ? s.la[r] * wv[r][2] + s.lb[r] * wv[r][3] : 0.f;
+        const float term = v0 * (c.wx0 * wy) + v1 * (c.wx1 * wy);
+        out = (r == 1 && !s.in1) ? out : out + term;
+    }
+    return out;
+}
+
+// column j of the sampled row
+__device__ __forceinline__ float te_column(const float* __restrict__ weight, int dim, const TeSample& s, int j) {
+    const TeCol c = te_col(j, dim);
+    float wv[2][4];
+    te_taps(weight, dim, s, c, wv);
+    return te_eval(s, wv, c);
+}
+
+// two samples of the same table column (the coarse and the fine level of an actor's table): all sixteen taps are requested before either is evaluated
+__device__ __forceinline__ void te_column2(const float* __restrict__ weight, int dim, const TeSample& sa, const TeSample& sb, int j, float* oa, float* ob) {
+    const TeCol c = te_col(j, dim);
+    float wa[2][4], wb[2][4];
+    te_taps(weight, dim, sa, c, wa);
+    te_taps(weight, dim, sb, c, wb);
+    *oa = te_eval(sa, wa, c);
+    *ob = te_eval(sb, wb, c);
+}
+
+// the gradient g of a sample's column into the table gradient G
+__device__ __forceinline__ void te_scatter(float* __restrict__ G, int dim, const TeSample& s, const TeCol& c, float g) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        if (r == 1 && !s.in1) continue;
+        const float wy = r ? s.wy1 : s.wy0;
+        atomicAdd(G + s.ha[r] * dim + c.x0, g * c.wx0 * wy * s.la[r]);
+        atomicAdd(G + s.hb[r] * dim + c.x0, g * c.wx0 * wy * s.lb[r]);
+        if (c.inx1) {
+            atomicAdd(G + s.ha[r] * dim + c.x1, g * c.wx1 * wy * s.la[r]);
+            atomicAdd(G + s.hb[r] * dim + c.x1, g * c.wx1 * wy * s.lb[r]);
+        }
+    }
+}
+
 template <bool BWD>
 __global__ void __launch_bounds__(EMD_WAVE) k_temporal_embed(const float* __restrict__ weight, int rows, int dim, int k,
                                                               const float* __restrict__ t_ptr, float* __restrict__ out,
                                                               const float* __restrict__ g_out, float* __restrict__ g_weight,
                                                               float* __restrict__ g_t) {
     // one wave per table (S3Gaussian has one; OmniRe keeps one per actor)
+    // (the row and column set-up and the table-gradient adds are te_rows / te_col / te_scatter written out: taken from them, both instantiations
+    //  came out with other registers, and this kernel is S3Gaussian's, pinned instruction for instruction across the tidy-up of the actor chain)
     weight += (size_t)blockIdx.x * rows * dim;
     if (out) out += (size_t)blockIdx.x * dim;
     if (g_out) g_out += (size_t)blockIdx.x * dim;
@@ -175,100 +277,6 @@ __global__ void __launch_bounds__(EMD_WAVE) k_deform_input_bwd(int n, int E, int
 // lane j < dim holds column j of both temporal rows, lanes dim .. dim+E-1 the mean embedding; the eight head outputs are
 // eight DPP wave sums.
 // ---------------------------------------------------------------------------------------------------------------------------
-struct TeSample { int ha[2], hb[2]; float la[2], lb[2], wy0, wy1; bool in1; };
-
-__device__ __forceinline__ TeSample te_rows(float t, int k, int rows) {
-#pragma clang fp contract(off)
-    TeSample s;
-    float my;
-    const float iy = reflect_coord((t - 0.5f) * 2.f, k, &my);
-    const float y0f = floorf(iy);
-    const int y0 = (int)y0f, y1 = y0 + 1;
-    s.wy1 = iy - y0f; s.wy0 = 1.f - s.wy1;
-    resized_row(min(y0, k - 1), k, rows, &s.ha[0], &s.hb[0], &s.la[0], &s.lb[0]);
-    resized_row(min(y1, k - 1), k, rows, &s.ha[1], &s.hb[1], &s.la[1], &s.lb[1]);
-    s.in1 = y1 <= k - 1;
-    return s;
-}
-
-// the eight taps of a sample, unconditionally (x1c: the column neighbour, clamped onto x0 where the sample has none)
-__device__ __forceinline__ void te_taps(const float* __restrict__ weight, int dim, const TeSample& s, int x0, int x1c, float (&wv)[2][4]) {
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        wv[r][0] = weight[s.ha[r] * dim + x0]; wv[r][1] = weight[s.hb[r] * dim + x0];
-        wv[r][2] = weight[s.ha[r] * dim + x1c]; wv[r][3] = weight[s.hb[r] * dim + x1c];
-    }
-}
-
-// the bilinear blend of a sample's eight taps.  ONE function without contraction for every caller: the one-launch actor chain (te_column2) and the
-// three-launch path (te_column) must produce the same bits (tests/test_motion_sh_gpu.py), and with contraction left to the compiler the two
-// inlined copies were fused differently.
-__device__ __forceinline__ float te_eval(const TeSample& s, const float (&wv)[2][4], float wx0, float wx1, bool inx1) {
-#pragma clang fp contract(off)
-    float out = 0.f;
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const float wy = r ? s.wy1 : s.wy0;
-        const float v0 = s.la[r] * wv[r][0] + s.lb[r] * wv[r][1];
-        const float v1 = inx1 ? s.la[r] * wv[r][2] + s.lb[r] * wv[r][3] : 0.f;
-        const float term = v0 * (wx0 * wy) + v1 * (wx1 * wy);
-        out = (r == 1 && !s.in1) ? out : out + term;
-    }
-    return out;
-}
-
-// column j of the sampled row (same arithmetic as k_temporal_embed); with G != nullptr scatters g into the table gradient instead
-__device__ __forceinline__ float te_column(const float* __restrict__ weight, int dim, const TeSample& s, int j, float g, float* __restrict__ G) {
-#pragma clang fp contract(off)
-    float mx;
-    const float gx = dim > 1 ? ((float)j / (float)(dim - 1) - 0.5f) * 2.f : -1.f;
-    const float ix = reflect_coord(gx, dim, &mx);
-    const float x0f = floorf(ix);
-    const int x0 = (int)x0f, x1 = x0 + 1;
-    const float wx1 = ix - x0f, wx0 = 1.f - wx1;
-    const bool inx1 = x1 <= dim - 1;
-    float out = 0.f;
-    if (!G) {
-        // all eight taps first, unconditionally (a tap the sample does not use -- the row past the table's end, the column past its width -- is read
-        // from a valid neighbour and selected away): with the loads inside the row loop's branches each row waited for its own round trip
-        float wv[2][4];
-        te_taps(weight, dim, s, x0, inx1 ? x1 : x0, wv);
-        return te_eval(s, wv, wx0, wx1, inx1);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        if (r == 1 && !s.in1) continue;
-        const float wy = r ? s.wy1 : s.wy0;
-        if (!G) {
-        } else {
-            atomicAdd(G + s.ha[r] * dim + x0, g * wx0 * wy * s.la[r]);
-            atomicAdd(G + s.hb[r] * dim + x0, g * wx0 * wy * s.lb[r]);
-            if (inx1) {
-                atomicAdd(G + s.ha[r] * dim + x1, g * wx1 * wy * s.la[r]);
-                atomicAdd(G + s.hb[r] * dim + x1, g * wx1 * wy * s.lb[r]);
-            }
-        }
-    }
-    return out;
-}
-
-// two samples of the same table column (the coarse and the fine level of an actor's table): all sixteen taps are requested before either is evaluated
-__device__ __forceinline__ void te_column2(const float* __restrict__ weight, int dim, const TeSample& sa, const TeSample& sb, int j, float* oa, float* ob) {
-#pragma clang fp contract(off)
-    float mx;
-    const float gx = dim > 1 ? ((float)j / (float)(dim - 1) - 0.5f) * 2.f : -1.f;
-    const float ix = reflect_coord(gx, dim, &mx);
-    const float x0f = floorf(ix);
-    const int x0 = (int)x0f, x1 = x0 + 1;
-    const float wx1 = ix - x0f, wx0 = 1.f - wx1;
-    const bool inx1 = x1 <= dim - 1;
-    float wa[2][4], wb[2][4];
-    te_taps(weight, dim, sa, x0, inx1 ? x1 : x0, wa);
-    te_taps(weight, dim, sb, x0, inx1 ? x1 : x0, wb);
-    *oa = te_eval(sa, wa, wx0, wx1, inx1);
-    *ob = te_eval(sb, wb, wx0, wx1, inx1);
-}
-
 __device__ __forceinline__ float wave_sum_all(float v) {
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
     return v;
@@ -279,157 +287,17 @@ __device__ __forceinline__ float wave_sum_all(float v) {
 // result -- no atomics, no zero fill.  Without them: a wave owns 64 consecutive points, one DPP sum + E atomics per uniform wave
 // (10 k atomics onto 128 addresses at the bench size: 53 us against 5 us for the segmented form).
 #define SEG_THREADS 1024
-__global__ void __launch_bounds__(SEG_THREADS) k_track_embed_sum_seg(int E, const float* __restrict__ emb, const int32_t* __restrict__ seg,
-                                                                     float* __restrict__ sums) {
-    // 1024 threads per actor: the 5000 points of a bench actor are 5 independent loads per thread (20 dependent trips with 256 threads:
-    // the kernel is pure latency, 19 us -> 7 us); E == 4 rows are read as one float4
-    __shared__ float s_part[SEG_THREADS / 64][8];
-    const int a = blockIdx.x, lo = seg[a], hi = seg[a + 1];
+// the sum of the embeddings of the points [lo, hi) by the whole 1024-thread workgroup -> s_sum[0..8) (E <= 8; entries from E on are zero).
+// 1024 threads per actor: the 5000 points of a bench actor are 5 independent loads per thread (20 dependent trips with 256 threads:
+// the kernel is pure latency, 19 us -> 7 us); E == 4 rows are read as one float4
+__device__ __forceinline__ void segment_sum(int E, const float* __restrict__ emb, int lo, int hi, float (*s_part)[8], float* s_sum) {
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) acc[e] = 0.f;
     if (E == 4 && ((uintptr_t)emb & 15) == 0) {
-        const float4* e4 = (const float4*)emb;
-        for (int i = lo + threadIdx.x; i < hi; i += SEG_THREADS) {
-            const float4 v = e4[i];
-            acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
-        }
-    } else {
-        for (int i = lo + threadIdx.x; i < hi; i += SEG_THREADS)
-#pragma unroll
-            for (int e = 0; e < 8; e++) if (e < E) acc[e] += emb[(size_t)i * E + e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-        const float w = wave_sum_all(acc[e]);
-        if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6][e] = w;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < E) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < SEG_THREADS / 64; w++) t += s_part[w][threadIdx.x];
-        sums[(size_t)a * E + threadIdx.x] = t;
-    }
-}
-
-__global__ void __launch_bounds__(EMD_BLOCK) k_track_embed_sum(int n, int E, const float* __restrict__ emb, const int32_t* __restrict__ ids,
-                                                               float* __restrict__ sums) {
-    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
-    const int id = i < n ? ids[i] : -1;
-    const unsigned long long has = __ballot(id >= 0);
-    if (!has) return;
-    const int a0 = __builtin_amdgcn_readlane(id, __ffsll((long long)has) - 1);
-    const bool uniform = __ballot(id >= 0 && id != a0) == 0ull;
-    for (int e = 0; e < E; e++) {
-        const float v = id >= 0 ? emb[(size_t)i * E + e] : 0.f;
-        if (uniform) {
-            const float sum = wave_sum_all(v);
-            if ((threadIdx.x & 63) == 0) atomicAdd(sums + (size_t)a0 * E + e, sum);
-        } else if (id >= 0) atomicAdd(sums + (size_t)id * E + e, v);
-    }
-}
-
-__global__ void __launch_bounds__(EMD_BLOCK) k_track_embed_bwd(int n, int E, const int32_t* __restrict__ ids, const float* __restrict__ count,
-                                                               const float* __restrict__ d_mean, float* __restrict__ d_emb) {
-    const size_t idx = (size_t)blockIdx.x * EMD_BLOCK + threadIdx.x;
-    if (idx >= (size_t)n * E) return;
-    const int i = (int)(idx / E), e = (int)(idx % E), id = ids[i];
-    d_emb[idx] = id >= 0 ? d_mean[(size_t)id * E + e] / count[id] : 0.f;
-}
-
-template <bool BWD>
-__global__ void __launch_bounds__(EMD_WAVE) k_track_heads(EmdTrackArgs a, EmdTrackGrads g) {
-    const int act = blockIdx.x, lane = threadIdx.x, dim = a.dim, E = a.embed_dim, width = dim + E;
-    const float* w = a.weight + (size_t)act * a.rows * dim;
-    const float t = a.t_dev ? a.t_dev[0] : a.t;
-    const int k_fine = a.k_fine_dev ? min(max(a.k_fine_dev[0], 1), a.rows) : a.k_fine;      // (a device-side level is clamped into the table)
-    const TeSample sc = te_rows(t, a.k_coarse, a.rows), sf = te_rows(t, k_fine, a.rows);
-    float hc = 0.f, hf = 0.f;
-    if (lane < dim) { hc = te_column(w, dim, sc, lane, 0.f, nullptr); hf = te_column(w, dim, sf, lane, 0.f, nullptr); }
-    else if (lane < width) hc = hf = a.emb_sum[(size_t)act * E + (lane - dim)] / a.count[act];
-    // head rows: 0-2 trans_c, 3-5 trans_f, 6 rot_c, 7 rot_f
-    float out[8], wrow[8];
-#pragma unroll
-    for (int o = 0; o < 8; o++) {
-        const int hd = o < 3 ? 0 : o < 6 ? 1 : o - 4, r = o < 3 ? o : o < 6 ? o - 3 : 0;
-        wrow[o] = lane < width ? a.head_w[hd][r * width + lane] : 0.f;
-        out[o] = wave_sum_all(wrow[o] * ((o < 3 || o == 6) ? hc : hf)) + a.head_b[hd][r];
-    }
-    const float cc = cosf(out[6]), scn = sinf(out[6]), cf = cosf(out[7]), sfn = sinf(out[7]);
-    const float ow = cc * cf - scn * sfn, oz = cc * sfn + scn * cf;          // quaternion_raw_multiply of two rotations about z
-    if (!BWD) {
-        if (lane == 0) {
-            a.trans[3 * act] = out[0] + out[3]; a.trans[3 * act + 1] = out[1] + out[4]; a.trans[3 * act + 2] = out[2] + out[5];
-            a.rot[4 * act] = ow; a.rot[4 * act + 1] = 0.f; a.rot[4 * act + 2] = 0.f; a.rot[4 * act + 3] = oz;
-        }
-        return;
-    }
-    // NaN gradients of an actor that is skipped in the pose table arrive as zeros from the pose kernel
-    const float gt0 = g.g_trans[3 * act], gt1 = g.g_trans[3 * act + 1], gt2 = g.g_trans[3 * act + 2];
-    const float gw = g.g_rot[4 * act], gz = g.g_rot[4 * act + 3];
-    const float dth = gw * (-oz) + gz * ow;                                  // d / d theta_c = d / d theta_f (the product depends on theta_c + theta_f)
-    const float go[8] = {gt0, gt1, gt2, gt0, gt1, gt2, dth, dth};
-    float dhc = 0.f, dhf = 0.f;
-#pragma unroll
-    for (int o = 0; o < 8; o++) {
-        const int hd = o < 3 ? 0 : o < 6 ? 1 : o - 4, r = o < 3 ? o : o < 6 ? o - 3 : 0;
-        const bool coarse = o < 3 || o == 6;
-        if (lane < width) atomicAdd(g.d_head_w[hd] + r * width + lane, go[o] * (coarse ? hc : hf));
-        if (lane == 0) atomicAdd(g.d_head_b[hd] + r, go[o]);
-        if (coarse) dhc += go[o] * wrow[o]; else dhf += go[o] * wrow[o];
-    }
-    if (lane < dim) {
-        float* G = g.d_weight + (size_t)act * a.rows * dim;
-        te_column(w, dim, sc, lane, dhc, G);
-        te_column(w, dim, sf, lane, dhf, G);
-    } else if (lane < width) g.d_mean[(size_t)act * E + (lane - dim)] = dhc + dhf;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The whole per-actor chain in ONE launch each way (round 3): embedding sums -> track heads -> pose row, and pose row gradient ->
-// heads -> temporal table / embeddings / per-frame pose tables.  Every step of the chain is per actor, so one 1024-thread
-// workgroup per actor runs it front to back: the forward replaces three launch-bound kernels (k_track_embed_sum_seg,
-// k_track_heads, k_actor_pose_forward: ~21 us of a 1.5 ms step), the backward replaces three more plus the two zero fills of
-// their dense outputs -- each workgroup clears what it owns (its actor's temporal table gradient and its column of the
-// [F, A, .] pose gradients) before accumulating.  Only the head parameters are shared between actors: their gradients are
-// float atomics into a 296-float accumulator that the FORWARD launch of the same step cleared (EmdTrackedPoseArgs.head_acc; a
-// last-workgroup reduction with release / acquire fences was measured first: 28 us for the backward launch against 9), so no
-// output needs a fill launch.  The pose arithmetic is the one of k_actor_pose_*
-// (standalone_ops.hip), evaluated without contraction so that both produce the same bits.
-// ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tp_quat_mul(const float a[4], const float b[4], float o[4]) {
-#pragma clang fp contract(off)
-    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-}
-__device__ __forceinline__ float tp_quat_norm(const float q[4]) {
-#pragma clang fp contract(off)
-    return sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-}
-__device__ __forceinline__ void tp_dnormalize4(const float vu[4], float n, const float g[4], float out[4]) {
-#pragma clang fp contract(off)
-    float dot = ((vu[0] * g[0] + vu[1] * g[1]) + vu[2] * g[2]) + vu[3] * g[3];
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = (g[k] - vu[k] * dot) / n;
-}
-__device__ __forceinline__ bool tp_any_nan(const float* v, int n) {
-    bool b = false;
-    for (int k = 0; k < n; k++) b |= !(v[k] == v[k]);
-    return b;
-}
-
-// per-actor sum of the embeddings of its points [lo, hi) by the whole workgroup -> s_sum[0..E) (E <= 8)
-__device__ __forceinline__ void tp_segment_sum(int E, const float* __restrict__ emb, int lo, int hi, float (*s_part)[8], float* s_sum) {
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) acc[e] = 0.f;
-    if (E == 4 && ((uintptr_t)emb & 15) == 0) {
-        // eight rows per thread in flight at once, unconditionally (a row past the segment's end reads its last row and counts as zero): the
+        // eight rows per thread in flight at once, unconditionally (a row past the segment's end reads its last row and counts as zero): a
         // plain loop waited for every row before asking for the next -- five dependent trips to memory for a bench actor's 5 000 points.
-        // (The adds run in the same order, row i before row i + 1 024: the same sums.)
+        // (The adds run in the plain loop's order, row i before row i + 1 024: the same sums.)
         const float4* e4 = (const float4*)emb;
         if (hi > lo) {
             for (int base = lo + (int)threadIdx.x; base < hi; base += 8 * SEG_THREADS) {
@@ -461,6 +329,124 @@ __device__ __forceinline__ void tp_segment_sum(int E, const float* __restrict__ 
     __syncthreads();
 }
 
+__global__ void __launch_bounds__(SEG_THREADS) k_track_embed_sum_seg(int E, const float* __restrict__ emb, const int32_t* __restrict__ seg,
+                                                                     float* __restrict__ sums) {
+    __shared__ float s_part[SEG_THREADS / 64][8], s_sum[8];
+    const int a = blockIdx.x;
+    segment_sum(E, emb, seg[a], seg[a + 1], s_part, s_sum);
+    if ((int)threadIdx.x < E) sums[(size_t)a * E + threadIdx.x] = s_sum[threadIdx.x];
+}
+
+__global__ void __launch_bounds__(EMD_BLOCK) k_track_embed_sum(int n, int E, const float* __restrict__ emb, const int32_t* __restrict__ ids,
+                                                               float* __restrict__ sums) {
+    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
+    const int id = i < n ? ids[i] : -1;
+    const unsigned long long has = __ballot(id >= 0);
+    if (!has) return;
+    const int a0 = __builtin_amdgcn_readlane(id, __ffsll((long long)has) - 1);
+    const bool uniform = __ballot(id >= 0 && id != a0) == 0ull;
+    for (int e = 0; e < E; e++) {
+        const float v = id >= 0 ? emb[(size_t)i * E + e] : 0.f;
+        if (uniform) {
+            const float sum = wave_sum_all(v);
+            if ((threadIdx.x & 63) == 0) atomicAdd(sums + (size_t)a0 * E + e, sum);
+        } else if (id >= 0) atomicAdd(sums + (size_t)id * E + e, v);
+    }
+}
+
+__global__ void __launch_bounds__(EMD_BLOCK) k_track_embed_bwd(int n, int E, const int32_t* __restrict__ ids, const float* __restrict__ count,
+                                                               const float* __restrict__ d_mean, float* __restrict__ d_emb) {
+    const size_t idx = (size_t)blockIdx.x * EMD_BLOCK + threadIdx.x;
+    if (idx >= (size_t)n * E) return;
+    const int i = (int)(idx / E), e = (int)(idx % E), id = ids[i];
+    d_emb[idx] = id >= 0 ? d_mean[(size_t)id * E + e] / count[id] : 0.f;
+}
+
+// the eight head rows: o = 0-2 trans_c, 3-5 trans_f, 6 rot_c, 7 rot_f -> head tensor, its row, and whether it reads h_c or h_f
+__device__ __forceinline__ constexpr int head_of(int o) { return o < 3 ? 0 : o < 6 ? 1 : o - 4; }
+__device__ __forceinline__ constexpr int head_row(int o) { return o < 3 ? o : o < 6 ? o - 3 : 0; }
+__device__ __forceinline__ constexpr bool head_coarse(int o) { return o < 3 || o == 6; }
+
+// The heads of one actor by one wave, for k_track_heads and k_tracked_pose alike (contraction is the unit's default in both).  Every lane holds its
+// column of the eight head rows (wrow: zero past the width) and of h_c / h_f; out[] and the rotation (ow, 0, 0, oz) come out wave-uniform.
+__device__ __forceinline__ void heads_eval(const float (&wrow)[8], const float (&hbias)[8], float hc, float hf, float (&out)[8], float* ow, float* oz) {
+#pragma unroll
+    for (int o = 0; o < 8; o++) out[o] = wave_sum_all(wrow[o] * (head_coarse(o) ? hc : hf)) + hbias[o];
+    const float cc = cosf(out[6]), scn = sinf(out[6]), cf = cosf(out[7]), sfn = sinf(out[7]);
+    // quaternion_raw_multiply of two rotations about z: ow = cc cf - scn sfn, oz = cc sfn + scn cf.  Which product of each pair is fused is written
+    // out: left to the compiler, the copy inlined into k_tracked_pose was packed with the quaternion product behind it and fused the other product
+    // of oz than k_track_heads' copy (one ulp in the pose table).  This is the form both kernels had before they shared this function.
+    *ow = fmaf(cc, cf, -(scn * sfn)); *oz = fmaf(scn, cf, cc * sfn);
+}
+
+// gt = d L / d track_trans, (gw, gz) = the w and z components of d L / d track_rot (gradients of a skipped, NaN, offset arrive as zeros).
+// Adds this actor's share into d_head_w / d_head_b and returns the lane's d L / d h_c, d L / d h_f.  An add of go[o] == 0 is skipped: the
+// accumulators of every caller start as +0, adding +-0 never changes a value and -0 cannot arise, so skipping is bit-neutral.
+__device__ __forceinline__ void heads_backward(const float (&wrow)[8], float hc, float hf, int lane, int width, const float (&gt)[3], float gw, float gz,
+                                               float ow, float oz, float* const (&d_head_w)[4], float* const (&d_head_b)[4], float* dhc_out,
+                                               float* dhf_out) {
+    const float dth = gw * (-oz) + gz * ow;                                  // d / d theta_c = d / d theta_f (the product depends on theta_c + theta_f)
+    const float go[8] = {gt[0], gt[1], gt[2], gt[0], gt[1], gt[2], dth, dth};
+    float dhc = 0.f, dhf = 0.f;
+#pragma unroll
+    for (int o = 0; o < 8; o++) {
+        if (go[o] != 0.f) {
+            if (lane < width) atomicAdd(d_head_w[head_of(o)] + head_row(o) * width + lane, go[o] * (head_coarse(o) ? hc : hf));
+            if (lane == 0) atomicAdd(d_head_b[head_of(o)] + head_row(o), go[o]);
+        }
+        if (head_coarse(o)) dhc += go[o] * wrow[o]; else dhf += go[o] * wrow[o];
+    }
+    *dhc_out = dhc; *dhf_out = dhf;
+}
+
+template <bool BWD>
+__global__ void __launch_bounds__(EMD_WAVE) k_track_heads(EmdTrackArgs a, EmdTrackGrads g) {
+    const int act = blockIdx.x, lane = threadIdx.x, dim = a.dim, E = a.embed_dim, width = dim + E;
+    const float* w = a.weight + (size_t)act * a.rows * dim;
+    const float t = a.t_dev ? a.t_dev[0] : a.t;
+    const int k_fine = a.k_fine_dev ? min(max(a.k_fine_dev[0], 1), a.rows) : a.k_fine;      // (a device-side level is clamped into the table)
+    const TeSample sc = te_rows(t, a.k_coarse, a.rows), sf = te_rows(t, k_fine, a.rows);
+    float hc = 0.f, hf = 0.f;
+    if (lane < dim) { hc = te_column(w, dim, sc, lane); hf = te_column(w, dim, sf, lane); }
+    else if (lane < width) hc = hf = a.emb_sum[(size_t)act * E + (lane - dim)] / a.count[act];
+    float out[8], wrow[8], hbias[8], ow, oz;
+#pragma unroll
+    for (int o = 0; o < 8; o++) {
+        wrow[o] = lane < width ? a.head_w[head_of(o)][head_row(o) * width + lane] : 0.f;
+        hbias[o] = a.head_b[head_of(o)][head_row(o)];
+    }
+    heads_eval(wrow, hbias, hc, hf, out, &ow, &oz);
+    if (!BWD) {
+        if (lane == 0) {
+            a.trans[3 * act] = out[0] + out[3]; a.trans[3 * act + 1] = out[1] + out[4]; a.trans[3 * act + 2] = out[2] + out[5];
+            a.rot[4 * act] = ow; a.rot[4 * act + 1] = 0.f; a.rot[4 * act + 2] = 0.f; a.rot[4 * act + 3] = oz;
+        }
+        return;
+    }
+    // NaN gradients of an actor that is skipped in the pose table arrive as zeros from the pose kernel
+    const float gt[3] = {g.g_trans[3 * act], g.g_trans[3 * act + 1], g.g_trans[3 * act + 2]};
+    float dhc, dhf;
+    heads_backward(wrow, hc, hf, lane, width, gt, g.g_rot[4 * act], g.g_rot[4 * act + 3], ow, oz, g.d_head_w, g.d_head_b, &dhc, &dhf);
+    if (lane < dim) {
+        float* G = g.d_weight + (size_t)act * a.rows * dim;
+        const TeCol c = te_col(lane, dim);
+        te_scatter(G, dim, sc, c, dhc);
+        te_scatter(G, dim, sf, c, dhf);
+    } else if (lane < width) g.d_mean[(size_t)act * E + (lane - dim)] = dhc + dhf;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The whole per-actor chain in ONE launch each way (round 3): embedding sums -> track heads -> pose row, and pose row gradient ->
+// heads -> temporal table / embeddings / per-frame pose tables.  Every step of the chain is per actor, so one 1024-thread
+// workgroup per actor runs it front to back: the forward replaces three launch-bound kernels (k_track_embed_sum_seg,
+// k_track_heads, k_actor_pose_forward: ~21 us of a 1.5 ms step), the backward replaces three more plus the two zero fills of
+// their dense outputs -- each workgroup clears what it owns (its actor's temporal table gradient and its column of the
+// [F, A, .] pose gradients) before accumulating.  Only the head parameters are shared between actors: their gradients are
+// float atomics into a 296-float accumulator that the FORWARD launch of the same step cleared (EmdTrackedPoseArgs.head_acc; a
+// last-workgroup reduction with release / acquire fences was measured first: 28 us for the backward launch against 9), so no
+// output needs a fill launch.  The arithmetic is the three-launch form's: segment_sum, te_*, heads_eval / heads_backward above and the pose row of
+// k_actor_pose_* (pose_row_forward / pose_row_backward, quat_math.h: no contraction), so both forms produce the same bits.
+// ---------------------------------------------------------------------------------------------------------------------------
 template <bool BWD>
 __global__ void __launch_bounds__(SEG_THREADS) k_tracked_pose(EmdTrackedPoseArgs p, EmdTrackedPoseGrads g) {
     __shared__ float s_part[SEG_THREADS / 64][8];
@@ -506,10 +492,7 @@ __global__ void __launch_bounds__(SEG_THREADS) k_tracked_pose(EmdTrackedPoseArgs
             if (p.valid_all && lane == 28) valid_in = p.valid_all[(size_t)frame * A + act];
         }
 #pragma unroll
-        for (int o = 0; o < 8; o++) {
-            const int hd = o < 3 ? 0 : o < 6 ? 1 : o - 4, r = o < 3 ? o : o < 6 ? o - 3 : 0;
-            wrow[o] = a.head_w[hd][r * width + (lane < width ? lane : 0)];          // (unconditional; lanes past the width are zeroed below)
-        }
+        for (int o = 0; o < 8; o++) wrow[o] = a.head_w[head_of(o)][head_row(o) * width + (lane < width ? lane : 0)];   // (unconditional; lanes past the width are zeroed below)
         if (lane < dim) te_column2(w, dim, sc, sf, lane, &hc_t, &hf_t);
 #pragma unroll
         for (int o = 0; o < 8; o++) wrow[o] = lane < width ? wrow[o] : 0.f;
@@ -528,14 +511,13 @@ __global__ void __launch_bounds__(SEG_THREADS) k_tracked_pose(EmdTrackedPoseArgs
     if (!BWD) {
         // the accumulator the backward launch of this step adds the shared head gradients into (no fill launch, no ticket)
         if (blockIdx.x == 0 && p.head_acc) for (int i = threadIdx.x; i < p.head_acc_floats; i += SEG_THREADS) p.head_acc[i] = 0.f;
-        if (E > 0) tp_segment_sum(E, a.embeddings, lo, hi, s_part, s_sum);
+        if (E > 0) segment_sum(E, a.embeddings, lo, hi, s_part, s_sum);
         if ((int)threadIdx.x < E) a.emb_sum[(size_t)act * E + threadIdx.x] = s_sum[threadIdx.x];      // kept for the backward
     } else {
         if ((int)threadIdx.x < E) s_sum[threadIdx.x] = a.emb_sum[(size_t)act * E + threadIdx.x];
         __syncthreads();                                                                           // (also: the clears above are done)
     }
     if (wave == 0) {
-        const float* w = a.weight + (size_t)act * a.rows * dim;
         {   // the uniform inputs, from the lanes that loaded them
             auto rl = [&](int k) -> float { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lane_in), k)); };
 #pragma unroll
@@ -553,84 +535,41 @@ __global__ void __launch_bounds__(SEG_THREADS) k_tracked_pose(EmdTrackedPoseArgs
         }
         float hc = hc_t, hf = hf_t;
         if (lane >= dim && lane < width) hc = hf = s_sum[lane - dim] / cnt;
-        float out[8];
-#pragma unroll
-        for (int o = 0; o < 8; o++) out[o] = wave_sum_all(wrow[o] * ((o < 3 || o == 6) ? hc : hf)) + hbias[o];
-        const float cc = cosf(out[6]), scn = sinf(out[6]), cf = cosf(out[7]), sfn = sinf(out[7]);
-        const float ow = cc * cf - scn * sfn, oz = cc * sfn + scn * cf;
+        float out[8], ow, oz;
+        heads_eval(wrow, hbias, hc, hf, out, &ow, &oz);
         const float dtv[3] = {out[0] + out[3], out[1] + out[4], out[2] + out[5]};
         const float dqv[4] = {ow, 0.f, 0.f, oz};
-        // ---- pose row of this actor (k_actor_pose_forward / _backward, every lane computes the same values) ----
-        const float q[4] = {qf[0], qf[1], qf[2], qf[3]};
-        const float* t_f = tf;
-        const float n = fmaxf(tp_quat_norm(q), 1e-12f);
-        const bool ok_t = !tp_any_nan(dtv, 3), ok_r = !tp_any_nan(dqv, 4);
-        float pq[4] = {q[0], q[1], q[2], q[3]};
-        if (ok_r) tp_quat_mul(q, dqv, pq);
-        const float n2 = fmaxf(tp_quat_norm(pq), 1e-12f);
+        // ---- pose row of this actor (every lane computes the same values) ----
         if (!BWD) {
+            float row[12];
+            pose_row_forward(qf, tf, true, dtv, true, dqv, vflag, row);
             if (lane == 0) {
                 if (a.trans) { a.trans[3 * act] = dtv[0]; a.trans[3 * act + 1] = dtv[1]; a.trans[3 * act + 2] = dtv[2]; }
                 if (a.rot) { a.rot[4 * act] = ow; a.rot[4 * act + 1] = 0.f; a.rot[4 * act + 2] = 0.f; a.rot[4 * act + 3] = oz; }
                 float* P = p.pose + (size_t)act * EMD_ACTOR_STRIDE;
 #pragma unroll
-                for (int k = 0; k < 4; k++) P[k] = q[k] / n;
-#pragma unroll
-                for (int k = 0; k < 3; k++) P[4 + k] = ok_t ? t_f[k] + dtv[k] : t_f[k];
-                P[7] = vflag;
-#pragma unroll
-                for (int k = 0; k < 4; k++) P[8 + k] = pq[k] / n2;
+                for (int k = 0; k < 12; k++) P[k] = row[k];
             }
         } else {
-            const float* Gp = gp_in;                      // (the pose row's gradient: loaded with the other uniform inputs)
-            const float qu[4] = {q[0] / n, q[1] / n, q[2] / n, q[3] / n};
-            const float gm[4] = {Gp[0], Gp[1], Gp[2], Gp[3]};
-            float dqf[4];
-            tp_dnormalize4(qu, n, gm, dqf);
-            const float pu[4] = {pq[0] / n2, pq[1] / n2, pq[2] / n2, pq[3] / n2};
-            const float gr[4] = {Gp[8], Gp[9], Gp[10], Gp[11]};
-            float dp[4], dr[4] = {0.f, 0.f, 0.f, 0.f};
-            tp_dnormalize4(pu, n2, gr, dp);
-            if (ok_r) {
-                const float rc[4] = {dqv[0], -dqv[1], -dqv[2], -dqv[3]}, qc[4] = {q[0], -q[1], -q[2], -q[3]};
-                float t1[4];
-                tp_quat_mul(dp, rc, t1);
-                tp_quat_mul(qc, dp, dr);
-#pragma unroll
-                for (int k = 0; k < 4; k++) dqf[k] += t1[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; k++) dqf[k] += dp[k];
-            }
+            float dqf[4], ddt[3], dr[4];
+            pose_row_backward(qf, true, dtv, true, dqv, gp_in, dqf, ddt, dr);       // (gp_in, the pose row's gradient: loaded with the other uniform inputs)
             if (lane == 0) {
                 float* dq = g.d_q_all + ((size_t)frame * A + act) * 4;
                 float* dt = g.d_t_all + ((size_t)frame * A + act) * 3;
 #pragma unroll
                 for (int k = 0; k < 4; k++) dq[k] = dqf[k];
 #pragma unroll
-                for (int k = 0; k < 3; k++) dt[k] = Gp[4 + k];
+                for (int k = 0; k < 3; k++) dt[k] = gp_in[4 + k];
             }
-            // ---- heads ----
-            const float gt0 = ok_t ? Gp[4] : 0.f, gt1 = ok_t ? Gp[5] : 0.f, gt2 = ok_t ? Gp[6] : 0.f;
-            const float dth = dr[0] * (-oz) + dr[3] * ow;
-            const float go[8] = {gt0, gt1, gt2, gt0, gt1, gt2, dth, dth};
-            float dhc = 0.f, dhf = 0.f;
-            // head parameters are shared by the actors: float atomics into `head_acc`, which the FORWARD launch of this step cleared
-            // (layout = the eight head tensors back to back: w_tc, b_tc, w_tf, b_tf, w_rc, b_rc, w_rf, b_rf)
-#pragma unroll
-            for (int o = 0; o < 8; o++) {
-                const int hd = o < 3 ? 0 : o < 6 ? 1 : o - 4, r = o < 3 ? o : o < 6 ? o - 3 : 0;
-                const bool coarse = o < 3 || o == 6;
-                if (go[o] != 0.f) {
-                    if (lane < width) atomicAdd(g.d_head_w[hd] + r * width + lane, go[o] * (coarse ? hc : hf));
-                    if (lane == 0) atomicAdd(g.d_head_b[hd] + r, go[o]);
-                }
-                if (coarse) dhc += go[o] * wrow[o]; else dhf += go[o] * wrow[o];
-            }
+            // ---- heads ----  their parameters are shared by the actors: float atomics into `head_acc`, which the FORWARD launch of this step
+            // cleared (layout = the eight head tensors back to back: w_tc, b_tc, w_tf, b_tf, w_rc, b_rc, w_rf, b_rf)
+            float dhc, dhf;
+            heads_backward(wrow, hc, hf, lane, width, ddt, dr[0], dr[3], ow, oz, g.d_head_w, g.d_head_b, &dhc, &dhf);
             if (lane < dim) {
                 float* G = g.d_weight + (size_t)act * a.rows * dim;
-                te_column(w, dim, sc, lane, dhc, G);
-                te_column(w, dim, sf, lane, dhf, G);
+                const TeCol c = te_col(lane, dim);
+                te_scatter(G, dim, sc, c, dhc);
+                te_scatter(G, dim, sf, c, dhf);
             } else if (lane < width) s_dmean[lane - dim] = (dhc + dhf) / cnt;
         }
     }

@@ -6,9 +6,11 @@
 // EVERY includer is built with -ffp-contract=off (csrc/Makefile): this arithmetic is a bit-exact contract with oracle/raster_oracle.c --
 // the view depth (sort key), radius and tile rectangle derive from it --, so every operation here is an individually rounded fp32 op in
 // the documented order ("pinned evaluation order").  The pragma below says the same to a compiler that was not given the flag.
+// quat_mul / quat_norm / dnormalize4 / any_nan and the actor pose row live in quat_math.h, which embed.hip includes too.
 #pragma once
 #include "common.h"
 #include "device_utils.h"
+#include "quat_math.h"
 
 #pragma clang fp contract(off)
 
@@ -33,17 +35,6 @@ __device__ __forceinline__ void quat_to_R(const float q[4], float R[9]) {
     R[6] = 2.f * (x * z - r * y);
     R[7] = 2.f * (y * z + r * x);
     R[8] = 1.f - 2.f * (x * x + y * y);
-}
-
-__device__ __forceinline__ void quat_mul(const float a[4], const float b[4], float o[4]) {
-    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-}
-
-__device__ __forceinline__ float quat_norm(const float q[4]) {
-    return sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
 }
 
 // World-space mean / quaternion / opacity of Gaussian i under the explicit-motion model.
@@ -197,12 +188,6 @@ __device__ __forceinline__ void dR_to_dq(const float q[4], const float dR[9], fl
     dq[3] = 2.f * (-2.f * z * dR[0] - r * dR[1] + x * dR[2] + r * dR[3] - 2.f * z * dR[4] + y * dR[5] + x * dR[6] + y * dR[7]);
 }
 
-__device__ __forceinline__ void dnormalize4(const float vu[4], float n, const float g[4], float out[4]) {
-    float dot = ((vu[0] * g[0] + vu[1] * g[1]) + vu[2] * g[2]) + vu[3] * g[3];
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = (g[k] - vu[k] * dot) / n;
-}
-
 // Backward of motion_point for an actor point (a_id >= 0): world-space gradients (dm, dq, dop) -> local-space
 // gradients (dl, dql, dopl) and this point's contribution to its actor's pose row (pose_g[12]).
 // (the arithmetic on values in registers; motion_point_backward below loads them)
@@ -294,12 +279,6 @@ __device__ __forceinline__ void reduce_pose_grad(int a_id, const float pose_g[12
 #pragma unroll
         for (int k = 0; k < 12; k++) atomicAdd(dL_dpose + (size_t)a_id * EMD_ACTOR_STRIDE + k, pose_g[k]);
     }
-}
-
-__device__ __forceinline__ bool any_nan(const float* v, int n) {
-    bool b = false;
-    for (int k = 0; k < n; k++) b |= !(v[k] == v[k]);
-    return b;
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 // densification statistics, and the L1 losses with their backward passes.  gfx950, one element per lane.
 //
 // Built with the flags of preprocess.hip (-ffp-contract=off -fno-slp-vectorize): the motion and SH kernels share gaussian_math.h with K1 / K8
-// and must produce the same bits as they do.
+// and must produce the same bits as they do.  The actor pose row is shared with embed.hip's one-launch actor chain the same way, through
+// quat_math.h (no contraction there whatever the unit's flags).
 //
 // Reference behaviour this replaces (file:line):
 //   activations                           S3Gaussian/gaussian_renderer/__init__.py:99-101
@@ -236,7 +237,8 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_activations(int n, const float* l
 //   q_mean = normalize(q_f)                       rotation applied to local means          (rigid.py:499-503)
 //   trans  = t_f + dt      (dt skipped when NaN)                                            (rigid.py:519-532)
 //   q_rot  = normalize(q_f (x) dq)  (dq skipped when NaN) composed onto local quaternions   (rigid.py:547-566)
-// Replaces ~25 launch-bound torch kernels (normalize / cat / index and their backward) per step.
+// Replaces ~25 launch-bound torch kernels (normalize / cat / index and their backward) per step.  The row's arithmetic is
+// pose_row_forward / pose_row_backward (quat_math.h), which k_tracked_pose (embed.hip) calls too: the kernels here load and store.
 // ---------------------------------------------------------------------------------------------------
 __global__ void k_actor_pose_forward(int A, const float* __restrict__ q_f, const float* __restrict__ t_f,
                                      const uint8_t* __restrict__ valid, const float* __restrict__ dt,
@@ -248,18 +250,13 @@ __global__ void k_actor_pose_forward(int A, const float* __restrict__ q_f, const
     }
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= A) return;
-    const float q[4] = {q_f[4 * a], q_f[4 * a + 1], q_f[4 * a + 2], q_f[4 * a + 3]};
-    const float n = fmaxf(quat_norm(q), 1e-12f);
+    const float q[4] = {q_f[4 * a], q_f[4 * a + 1], q_f[4 * a + 2], q_f[4 * a + 3]}, t[3] = {t_f[3 * a], t_f[3 * a + 1], t_f[3 * a + 2]};
+    float dtv[3] = {0.f, 0.f, 0.f}, dqv[4] = {1.f, 0.f, 0.f, 0.f}, row[12];
+    if (dt) for (int k = 0; k < 3; k++) dtv[k] = dt[3 * a + k];
+    if (dq) for (int k = 0; k < 4; k++) dqv[k] = dq[4 * a + k];
+    pose_row_forward(q, t, dt != nullptr, dtv, dq != nullptr, dqv, valid ? (valid[a] ? 1.f : 0.f) : 1.f, row);
     float* P = pose + (size_t)a * EMD_ACTOR_STRIDE;
-    for (int k = 0; k < 4; k++) P[k] = q[k] / n;
-    float t[3] = {t_f[3 * a], t_f[3 * a + 1], t_f[3 * a + 2]};
-    if (dt && !any_nan(dt + 3 * a, 3)) { t[0] += dt[3 * a]; t[1] += dt[3 * a + 1]; t[2] += dt[3 * a + 2]; }
-    P[4] = t[0]; P[5] = t[1]; P[6] = t[2];
-    P[7] = valid ? (valid[a] ? 1.f : 0.f) : 1.f;
-    float p[4] = {q[0], q[1], q[2], q[3]};
-    if (dq && !any_nan(dq + 4 * a, 4)) { const float r[4] = {dq[4 * a], dq[4 * a + 1], dq[4 * a + 2], dq[4 * a + 3]}; quat_mul(q, r, p); }
-    const float n2 = fmaxf(quat_norm(p), 1e-12f);
-    for (int k = 0; k < 4; k++) P[8 + k] = p[k] / n2;
+    for (int k = 0; k < 12; k++) P[k] = row[k];
 }
 
 __global__ void k_actor_pose_backward(int A, const float* __restrict__ q_f, const float* __restrict__ dt,
@@ -269,34 +266,15 @@ __global__ void k_actor_pose_backward(int A, const float* __restrict__ q_f, cons
     if (frame_dev) { const size_t f = (size_t)frame_dev[0]; q_f += f * A * 4; d_q_f += f * A * 4; d_t_f += f * A * 3; }
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= A) return;
-    const float* G = g_pose + (size_t)a * EMD_ACTOR_STRIDE;
     const float q[4] = {q_f[4 * a], q_f[4 * a + 1], q_f[4 * a + 2], q_f[4 * a + 3]};
-    const float n = fmaxf(quat_norm(q), 1e-12f);
-    const float qu[4] = {q[0] / n, q[1] / n, q[2] / n, q[3] / n};
-    const float gm[4] = {G[0], G[1], G[2], G[3]};
-    float dqf[4];
-    dnormalize4(qu, n, gm, dqf);
-    const bool use_r = dq && !any_nan(dq + 4 * a, 4);
-    float p[4] = {q[0], q[1], q[2], q[3]}, r[4] = {1.f, 0.f, 0.f, 0.f};
-    if (use_r) { r[0] = dq[4 * a]; r[1] = dq[4 * a + 1]; r[2] = dq[4 * a + 2]; r[3] = dq[4 * a + 3]; quat_mul(q, r, p); }
-    const float n2 = fmaxf(quat_norm(p), 1e-12f);
-    const float pu[4] = {p[0] / n2, p[1] / n2, p[2] / n2, p[3] / n2};
-    const float gr[4] = {G[8], G[9], G[10], G[11]};
-    float dp[4];
-    dnormalize4(pu, n2, gr, dp);
-    float dr[4] = {0.f, 0.f, 0.f, 0.f};
-    if (use_r) {   // p = q (x) r : dL/dq = dp (x) conj(r), dL/dr = conj(q) (x) dp
-        const float rc[4] = {r[0], -r[1], -r[2], -r[3]}, qc[4] = {q[0], -q[1], -q[2], -q[3]};
-        float t1[4];
-        quat_mul(dp, rc, t1);
-        quat_mul(qc, dp, dr);
-        for (int k = 0; k < 4; k++) dqf[k] += t1[k];
-    } else {
-        for (int k = 0; k < 4; k++) dqf[k] += dp[k];
-    }
+    float dtv[3] = {0.f, 0.f, 0.f}, dqv[4] = {1.f, 0.f, 0.f, 0.f}, G[12], dqf[4], ddt[3], dr[4];
+    if (dt) for (int k = 0; k < 3; k++) dtv[k] = dt[3 * a + k];
+    if (dq) for (int k = 0; k < 4; k++) dqv[k] = dq[4 * a + k];
+    for (int k = 0; k < 12; k++) G[k] = g_pose[(size_t)a * EMD_ACTOR_STRIDE + k];
+    pose_row_backward(q, dt != nullptr, dtv, dq != nullptr, dqv, G, dqf, ddt, dr);
     for (int k = 0; k < 4; k++) d_q_f[4 * a + k] = dqf[k];
     for (int k = 0; k < 3; k++) d_t_f[3 * a + k] = G[4 + k];
-    if (d_dt) { const bool ok = dt && !any_nan(dt + 3 * a, 3); for (int k = 0; k < 3; k++) d_dt[3 * a + k] = ok ? G[4 + k] : 0.f; }
+    if (d_dt) for (int k = 0; k < 3; k++) d_dt[3 * a + k] = ddt[k];
     if (d_dq) for (int k = 0; k < 4; k++) d_dq[4 * a + k] = dr[k];
 }
 

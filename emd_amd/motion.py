@@ -22,6 +22,28 @@ import torch.nn.functional as F
 from . import _lib as L
 
 
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _track_inputs(weight, emb, head_params):
+    """The ten tensors of the track heads as the kernels read them (detached, contiguous, fp32), after the width check."""
+    c = lambda x: x.detach().contiguous().float()
+    weight_c, emb_c, heads = c(weight), c(emb), [c(x) for x in head_params]
+    width = weight_c.shape[2] + emb_c.shape[1]
+    if width > 64 or any(h.shape[-1] != width for h in heads[0::2]):
+        raise ValueError("track heads: temporal dim + embedding dim must be <= 64 and match the head widths")
+    return weight_c, emb_c, heads
+
+
+def _frame_on_device(frame, dev):
+    """Whether `frame` is a device frame index (then it must be an int32 tensor on `dev`)."""
+    on_dev = isinstance(frame, torch.Tensor)
+    if on_dev and (frame.dtype != torch.int32 or frame.device != dev):
+        raise ValueError("a device frame index must be an int32 tensor on the tables' device")
+    return on_dev
+
+
 def quat_act(q):
     return F.normalize(q, dim=-1)
 
@@ -160,10 +182,6 @@ class TrackOffsetHeads(torch.nn.Module):
                                   self.min_embeddings, k_f, frame)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class _TrackHeads(torch.autograd.Function):
     @staticmethod
     def _args(weight, emb, heads, ids32, cnt, seg, t, k_c, k_f, emb_sum, trans, rot):
@@ -188,12 +206,8 @@ class _TrackHeads(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, emb, wtc, btc, wtf, btf, wrc, brc, wrf, brf, ids32, cnt, seg, t, k_c, k_f):
         dev = weight.device
-        c = lambda x: x.detach().contiguous().float()
-        weight_c, emb_c = c(weight), c(emb)
-        heads = [c(x) for x in (wtc, btc, wtf, btf, wrc, brc, wrf, brf)]
+        weight_c, emb_c, heads = _track_inputs(weight, emb, (wtc, btc, wtf, btf, wrc, brc, wrf, brf))
         A, E = weight_c.shape[0], emb_c.shape[1]
-        if weight_c.shape[2] + E > 64 or any(h.shape[-1] != weight_c.shape[2] + E for h in heads[0::2]):
-            raise ValueError("track heads: temporal dim + embedding dim must be <= 64 and match the head widths")
         emb_sum = (torch.empty if seg is not None else torch.zeros)(A, max(E, 1), device=dev)
         trans, rot = torch.empty(A, 3, device=dev), torch.empty(A, 4, device=dev)
         a = _TrackHeads._args(weight_c, emb_c, heads, ids32, cnt, seg, t, k_c, k_f, emb_sum, trans, rot)
@@ -231,17 +245,12 @@ class _TrackedPose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, emb, wtc, btc, wtf, btf, wrc, brc, wrf, brf, q_all, t_all, fv, ids32, cnt, seg, t, k_c, k_f, frame):
         dev = weight.device
-        c = lambda x: x.detach().contiguous().float()
-        weight_c, emb_c, q_c, t_c = c(weight), c(emb), c(q_all), c(t_all)
-        heads = [c(x) for x in (wtc, btc, wtf, btf, wrc, brc, wrf, brf)]
+        weight_c, emb_c, heads = _track_inputs(weight, emb, (wtc, btc, wtf, btf, wrc, brc, wrf, brf))
+        q_c, t_c = q_all.detach().contiguous().float(), t_all.detach().contiguous().float()
         A, E = weight_c.shape[0], emb_c.shape[1]
-        if weight_c.shape[2] + E > 64 or any(h.shape[-1] != weight_c.shape[2] + E for h in heads[0::2]):
-            raise ValueError("track heads: temporal dim + embedding dim must be <= 64 and match the head widths")
         if q_c.shape[1] != A or t_c.shape[:2] != q_c.shape[:2]:
             raise ValueError("pose tables must be [F, A, 4] / [F, A, 3] with A = number of temporal tables")
-        on_dev = isinstance(frame, torch.Tensor)
-        if on_dev and (frame.dtype != torch.int32 or frame.device != dev):
-            raise ValueError("a device frame index must be an int32 tensor on the tables' device")
+        _frame_on_device(frame, dev)
         valid = None if fv is None else fv.contiguous().view(torch.uint8)
         emb_sum = torch.empty(A, max(E, 1), device=dev)
         pose = torch.empty(A, L.ACTOR_STRIDE, device=dev, dtype=torch.float32)
@@ -335,10 +344,8 @@ class _ActorPose(torch.autograd.Function):
         lib = L.load()
         if instances_quats.device.type != "cuda":
             raise L.EmdError("actor_pose_table needs tensors on a ROCm device; there is no CPU path")
-        on_dev = isinstance(frame, torch.Tensor)
+        on_dev = _frame_on_device(frame, instances_quats.device)
         if on_dev:
-            if frame.dtype != torch.int32 or frame.device != instances_quats.device:
-                raise ValueError("a device frame index must be an int32 tensor on the tables' device")
             q_f, t_f = instances_quats.detach().contiguous(), instances_trans.detach().contiguous()
             valid = None if instances_fv is None else instances_fv.contiguous().view(torch.uint8)
             A = q_f.shape[1]

@@ -258,7 +258,7 @@ def track_offsets(weight, heads, frame, num_frames, embeddings, point_ids, step,
 
     t = (frame - 0) / (num_frames - 1 - 0)
     ids = point_ids.long()
-    cnt = torch.zeros(A).index_add_(0, ids, torch.ones_like(ids, dtype=embeddings.dtype))
+    cnt = torch.zeros(A, dtype=embeddings.dtype).index_add_(0, ids, torch.ones_like(ids, dtype=embeddings.dtype))
     mean_emb = torch.zeros(A, embeddings.shape[1], dtype=embeddings.dtype).index_add_(0, ids, embeddings) / cnt[:, None]
     k_f = int(min_embeddings + (max_embeddings - min_embeddings) * min(max(step, 0), c2f_temporal_iter) / c2f_temporal_iter)
     h_c = torch.cat([temporal_embed(t, min_embeddings), mean_emb], -1)

@@ -291,3 +291,89 @@ def test_one_launch_actor_chain_equals_the_three_launch_path(frame, step, on_dev
             a, b = a.cpu().numpy(), b.cpu().numpy()
             assert a.shape == b.shape
             assert np.abs(a - b).max() <= 2e-5 * np.abs(b).max() + 1e-7, (rep, np.abs(a - b).max(), np.abs(b).max())
+
+
+# points per actor of the generated case: one and two points, 1025 (a second row for one thread of the 1024-thread segment sum) and 8193 (a second
+# trip of its eight-deep load loop for one thread)
+_CHAIN_POINTS = (1, 2, 1025, 8193)
+
+
+@pytest.mark.parametrize("frame,step,on_device", [(1, 0, False), (2, 30000, True)])
+@pytest.mark.parametrize("edim,fdim", [(1, 32), (4, 32), (8, 32), (8, 56)])
+def test_actor_chain_launch_forms_agree_on_generated_shapes(edim, fdim, frame, step, on_device):
+    """The comparison of test_one_launch_actor_chain_equals_the_three_launch_path on generated inputs (the golden file has 4-wide embeddings only):
+    four actors of 1, 2, 1025 and 8193 points, three frames, 40 table rows; embeddings 1, 4 and 8 wide (the generic row path, the float4 path, the
+    widest) on a 32-wide table, and 8 wide on a 56-wide one (dim + E = 64 fills the wave); step 0 and a step past c2f_temporal_iter (k_fine = 30
+    and = the table's 40 rows); the middle frame from the host and the last one (t = 1: the sample's second row lies past the end) from the device.
+    The pose table bit for bit and every gradient within 2e-5 max|ref| + 1e-7 between the two forms, and the three-launch form's offsets and their
+    gradients against the checker (oracle/torch_ref.track_offsets) in fp64, with the tolerances of
+    test_fused_track_heads_match_the_checker_forward_and_backward."""
+    from oracle import torch_ref as tr
+    A, F_, rows = len(_CHAIN_POINTS), 3, 40
+    g = torch.Generator().manual_seed(1000 * edim + fdim + frame)
+    heads = motion.TrackOffsetHeads(A, temporal_embedding_dim=fdim, gaussian_embedding_dim=edim, max_embeddings=rows)
+    names = ("track_trans_c", "track_trans_f", "track_rot_c", "track_rot_f")
+    with torch.no_grad():
+        for n in names:
+            lin = getattr(heads, n)
+            lin.weight.copy_(0.3 * torch.randn(lin.weight.shape, generator=g))
+            lin.bias.copy_(0.1 * torch.randn(lin.bias.shape, generator=g))
+        heads.weight.copy_(0.5 * torch.randn(heads.weight.shape, generator=g))
+    ids_cpu = torch.repeat_interleave(torch.arange(A), torch.tensor(_CHAIN_POINTS))
+    emb0 = torch.randn(ids_cpu.numel(), edim, generator=g)
+    gt, gr = torch.randn(A, 3, generator=g), torch.randn(A, 4, generator=g)
+    iq0 = torch.randn(F_, A, 4, generator=g) * 1.3
+    it0 = torch.randn(F_, A, 3, generator=g)
+    fv = (torch.rand(F_, A, generator=g) > 0.2).to(DEV)
+    w = torch.randn(A, 12, generator=g).to(DEV)
+    # checker (CPU autograd, fp64)
+    w0 = heads.weight.detach().double().requires_grad_(True)
+    e0 = emb0.double().requires_grad_(True)
+    hp = {n: (getattr(heads, n).weight.detach().double().requires_grad_(True), getattr(heads, n).bias.detach().double().requires_grad_(True))
+          for n in names}
+    t0, r0 = tr.track_offsets(w0, hp, frame, F_, e0, ids_cpu, step, min_embeddings=heads.min_embeddings, max_embeddings=rows,
+                              c2f_temporal_iter=heads.c2f_temporal_iter)
+    ((t0 * gt.double()).sum() + (r0 * gr.double()).sum()).backward()
+    # product (GPU)
+    hd = heads.to(DEV)
+    ids = ids_cpu.to(DEV)
+    params = [hd.weight] + [p for n in names for p in (getattr(hd, n).weight, getattr(hd, n).bias)]
+    fr = torch.tensor([frame], dtype=torch.int32, device=DEV) if on_device else frame
+    st = torch.tensor([step], dtype=torch.int64, device=DEV) if on_device else step
+    e1 = emb0.to(DEV).requires_grad_(True)
+    t1, r1 = hd(fr, F_, e1, ids, st)
+    ((t1 * gt.to(DEV)).sum() + (r1 * gr.to(DEV)).sum()).backward()
+    err = lambda a, b: (np.abs(a.detach().cpu().numpy() - b.detach().numpy()).max(), np.abs(b.detach().numpy()).max())
+    print("offsets vs checker (max |err|, max |ref|):", err(t1, t0), err(r1, r0))
+    np.testing.assert_allclose(t1.detach().cpu().numpy(), t0.detach().numpy(), rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(r1.detach().cpu().numpy(), r0.detach().numpy(), rtol=1e-5, atol=1e-5)
+    pairs = [("temporal tables", hd.weight.grad, w0.grad), ("embeddings", e1.grad, e0.grad)]
+    for n in names:
+        pairs += [(n + ".weight", getattr(hd, n).weight.grad, hp[n][0].grad), (n + ".bias", getattr(hd, n).bias.grad, hp[n][1].grad)]
+    for what, a, b in pairs:
+        d, m = err(a, b)
+        print(f"{what} gradient vs checker: max |err| {d:.3e}, max |ref| {m:.3e}")
+        assert d <= 1e-4 * m + 1e-7, (what, d, m)
+
+    def run(fused):
+        for p in params:
+            p.grad = None
+        e = emb0.to(DEV).requires_grad_(True)
+        iq, it = iq0.to(DEV).requires_grad_(True), it0.to(DEV).requires_grad_(True)
+        if fused:
+            pose = hd.pose_table(iq, it, fv, fr, e, ids, st)
+        else:
+            tt, trq = hd(fr, F_, e, ids, st)
+            pose = motion.actor_pose_table(iq, it, fv, fr, tt, trq)
+        (pose * w).sum().backward()
+        return pose.detach().clone(), [e.grad.clone(), iq.grad.clone(), it.grad.clone()] + [p.grad.clone() for p in params]
+
+    ref_pose, ref_g = run(False)
+    for rep in range(2):
+        pose, got = run(True)
+        np.testing.assert_array_equal(pose.cpu().numpy(), ref_pose.cpu().numpy())
+        for a, b in zip(got, ref_g):
+            a, b = a.cpu().numpy(), b.cpu().numpy()
+            assert a.shape == b.shape
+            print("one launch vs three (max |err|, max |ref|):", rep, np.abs(a - b).max(), np.abs(b).max())
+            assert np.abs(a - b).max() <= 2e-5 * np.abs(b).max() + 1e-7, (rep, np.abs(a - b).max(), np.abs(b).max())
