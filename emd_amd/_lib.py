@@ -136,6 +136,20 @@ class EmdPlaneRegArgs(C.Structure):
                 ("out", _f), ("g", _f), ("dL_dplanes", (_f * 6) * HEX_MAX_SCALES)]
 
 
+TRAINER_LOSS_CHUNK = 1024    # EMD_TRAINER_LOSS_CHUNK: pixels per fp64 partial of the trainer's loss tail and of dL/dA (csrc/trainer_loss.hip)
+TRAINER_SSIM_TILE = 32       # EMD_TRAINER_SSIM_TILE: rows x floats of the [H-10][3 (W-10)] SSIM map one workgroup owns
+TL_MASK_BCE, TL_MASK_SAFE_BCE = 0, 1
+TL_DEPTH_L1, TL_DEPTH_L2, TL_DEPTH_SMOOTH_L1 = 0, 1, 2
+
+
+class EmdTrainerLossArgs(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("mask_type", C.c_int32), ("depth_type", C.c_int32), ("normalize", C.c_int32),
+                ("inverse", C.c_int32), ("rgb", _f), ("gt_rgb", _f), ("opacity", _f), ("sky_mask", _f), ("depth", _f), ("lidar_depth", _f),
+                ("w_rgb", C.c_float), ("w_ssim", C.c_float), ("w_mask", C.c_float), ("safe_limit", C.c_float), ("w_depth", C.c_float),
+                ("upper_bound", C.c_float), ("w_entropy", C.c_float), ("w_smooth", C.c_float), ("losses", _f), ("dL_drgb", _f),
+                ("dL_dopacity", _f), ("dL_ddepth", _f)]
+
+
 class EmdDeformInArgs(C.Structure):
     _fields_ = [("num_points", C.c_int32), ("num_freqs_x", C.c_int32), ("num_freqs_t", C.c_int32), ("embed_dim", C.c_int32),
                 ("ld", C.c_int32), ("reserved", C.c_int32), ("means", _f), ("point_ids", _f), ("inst_size", _f), ("inst_embed", _f),
@@ -281,7 +295,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_sky_det_workspace_size", "emd_sky_det_workspace_offsets", "emd_sky_backward_det",
                     "emd_motion_det_workspace_size", "emd_motion_det_workspace_offsets", "emd_motion_backward_det",
                     "emd_joint_chain_forward", "emd_joint_chain_backward", "emd_skin_forward", "emd_skin_backward",
-                    "emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward")
+                    "emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward",
+                    "emd_affine_workspace_size", "emd_affine_forward", "emd_affine_backward", "emd_trainer_loss_workspace_size", "emd_trainer_loss")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -405,6 +420,13 @@ def load():
     lib.emd_plane_reg_workspace_size.restype = C.c_size_t
     lib.emd_plane_reg_forward.argtypes = [C.POINTER(EmdPlaneRegArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_plane_reg_backward.argtypes = [C.POINTER(EmdPlaneRegArgs), C.c_void_p]
+    lib.emd_affine_workspace_size.argtypes = [C.c_int64]
+    lib.emd_affine_workspace_size.restype = C.c_size_t
+    lib.emd_affine_forward.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.emd_affine_backward.argtypes = [C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
+    lib.emd_trainer_loss_workspace_size.argtypes = [C.POINTER(EmdTrainerLossArgs)]
+    lib.emd_trainer_loss_workspace_size.restype = C.c_size_t
+    lib.emd_trainer_loss.argtypes = [C.POINTER(EmdTrainerLossArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p

@@ -35,6 +35,8 @@
  *                                       <- SMPLTemplate.forward          OmniRe/models/human_body.py:158-181
  *                                          SMPLNodes.transform_means_and_quats  OmniRe/models/nodes/smpl.py:438-532
  *   emd_plane_reg_forward / backward    <- compute_regulation            S3Gaussian/scene/gaussian_model.py:745-784
+ *   emd_affine_forward / backward       <- the affine colour correction  OmniRe/models/trainers/base.py:251-258
+ *   emd_trainer_loss                    <- compute_losses                OmniRe/models/trainers/base.py:518-620, models/losses.py
  *   emd_sh_grad_from_factors            (multi-GPU: rebuilds the SH gradient from all-gathered rank-one factors; no reference counterpart)
  *   emd_compact_rows / emd_scatter_rows (multi-GPU: visibility-compacted gradient rows for 2 / 4 ranks; no reference counterpart)
  *
@@ -1217,6 +1219,77 @@ typedef struct EmdPlaneRegArgs {
 size_t emd_plane_reg_workspace_size(const EmdPlaneRegArgs* args);
 int emd_plane_reg_forward(const EmdPlaneRegArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
 int emd_plane_reg_backward(const EmdPlaneRegArgs* args, void* hip_stream);
+
+/* ---- ABI 30 extension (new entry points and a struct only, so the number stays): the image tail of an OmniRe step (csrc/trainer_loss.hip) ----
+ * The per-image affine colour correction (models/trainers/base.py:251-258) and the trainer's image losses (compute_losses, base.py:518-620, with
+ * models/losses.py, pytorch_msssim.SSIM(data_range=1, channel=3) and kornia.losses.inverse_depth_smoothness_loss).  Everything is fp32 and
+ * channels-last, as the trainer's `outputs`: colour images [H][W][3], scalar images [H][W]; 4-byte alignment suffices (rows of 3 W floats are not
+ * 16-byte aligned for odd W).  No float atomics and no second mode: every scalar is a sum of per-workgroup fp64 partials added in a fixed order,
+ * every gradient element is WRITTEN exactly once by the pixel that owns it (no zero fill by the caller, nothing scattered), so all outputs are
+ * bit-identical from run to run, across streams and under hipGraph replay.  No host synchronisation.
+ *
+ * Affine colour, one A [3][4] (row-major, on the DEVICE) per image, P = num_pixels:
+ *     out[p] = A[:, :3] rgb[p] + A[:, 3]          each row ((a0 r + a1 g) + a2 b) + a3: A = [I | 0] returns rgb bit for bit
+ *     dL/drgb[p] = A[:, :3]^T g[p]                dL/dA = sum_p g[p] (x) [rgb[p], 1]     (12 sums: fp64 per chunk of EMD_TRAINER_LOSS_CHUNK pixels,
+ *                                                                                         the chunks added in ascending order)
+ * emd_affine_backward: dL_drgb or dL_daffine may be NULL (not both); `workspace` (emd_affine_workspace_size(P) bytes, 8-byte aligned, needs no
+ * clearing) is read only with dL_daffine. */
+size_t emd_affine_workspace_size(int64_t num_pixels);
+int emd_affine_forward(int64_t num_pixels, const float* rgb, const float* affine, float* out, void* hip_stream);
+int emd_affine_backward(int64_t num_pixels, const float* rgb, const float* affine, const float* dL_dout, float* dL_drgb, float* dL_daffine,
+                        void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* The loss tail.  Write x = rgb, y = gt_rgb, o = opacity, s = sky_mask (0 or 1), t = 1 - s, d = depth, l = lidar_depth, P = H W.  A term is SKIPPED
+ * when its weight is 0 or one of its inputs is NULL: its scalar is 0 and it adds nothing to any gradient.  sign(0) = 0 everywhere.
+ *   rgb      w_rgb * mean over 3 P of |y - x|                                                      d/dx = sign(x - y) / (3 P)
+ *   ssim     w_ssim * (1 - mean over 3 (H-10) (W-10) of map), per channel and per window position (i, j), i < H-10, j < W-10:
+ *                filt(u)[i,j] = sum_{a,b < 11} k[a] k[b] u[i+a, j+b],  k[a] = exp(-(a-5)^2 / (2 * 1.5^2)) normalised to sum 1   (no padding)
+ *                mu1 = filt(x), mu2 = filt(y), s1 = filt(x^2) - mu1^2, s2 = filt(y^2) - mu2^2, s12 = filt(x y) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2
+ *                map = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * (2 s12 + C2) / (s1 + s2 + C2)
+ *            H < 11 or W < 11 with w_ssim != 0 is EMD_ERR_INVALID.
+ *   mask     inputs o, s.  EMD_TL_MASK_BCE: w_mask * mean_P of -[t max(ln o, -100) + (1-t) max(ln(1-o), -100)], d/do = (o - t) / max(o (1-o), 1e-12)
+ *            (torch's binary_cross_entropy; o must lie in [0, 1]).  EMD_TL_MASK_SAFE_BCE, with o~ = clip(o, 0, 1) and o^ = clip(o~, safe_limit,
+ *            1 - safe_limit): value -max(ln(t ? o~ : 1 - o~), ln safe_limit), d/do = 1 / (1 - o^) where t = 0, -1 / o^ where t = 1: the gradient
+ *            survives the clip.  0 < safe_limit < 0.5.
+ *   depth    inputs d, l, s.  Over the hit pixels v = (t > 0) and (0.01 < l < upper_bound) and (d > 1e-4): with `normalize` d and l are divided by
+ *            upper_bound, then with `inverse` u -> 1 / (u + 1e-5); e = |z| (L1), z^2 (L2) or z^2 / 2 for |z| < 1, else |z| - 1/2 (SMOOTH_L1, beta = 1),
+ *            z = d' - l';  value w_depth * sum_v e / max(|v|, 1).  An empty hit set gives 0 and a zero gradient (the reference divides by 0 and
+ *            returns NaN).  upper_bound > 0.01.
+ *   entropy  input o.  w_entropy * mean_P of -o~ ln o~, o~ = clip(o, 1e-6, 1 - 1e-6); d/do = -(ln o~ + 1) where 1e-6 <= o <= 1 - 1e-6, else 0
+ *   smooth   input d.  q = 1 / (d + 1e-5), wx[i,j] = exp(-mean_c |y[i,j,c] - y[i,j+1,c]|), wy likewise down the rows:
+ *            w_smooth * [ mean over H (W-1) of |(q[i,j] - q[i,j+1]) wx[i,j]| + mean over (H-1) W of |(q[i,j] - q[i+1,j]) wy[i,j]| ];  no gradient
+ *            reaches y.  H < 2 or W < 2 with the term active is EMD_ERR_INVALID.
+ * losses [7] = total, rgb, ssim, mask, depth, entropy, smooth (each term weighted; the total is their sum).  dL_drgb [H][W][3], dL_dopacity [H][W]
+ * and dL_ddepth [H][W] (each may be NULL) are d total / d input: the sum over the terms that touch the input, zero where none does; dL_dopacity
+ * needs opacity, dL_ddepth needs depth.  The caller scales them by its upstream scalar.  `workspace`: emd_trainer_loss_workspace_size(args)
+ * bytes (a function of height and width alone; 0 for arguments the call would refuse), 8-byte aligned, needs no clearing.  Every argument is
+ * checked before anything is launched; at most five launches (point-wise sums, SSIM forward, the scalars, SSIM backward, dL/ddepth). */
+#define EMD_TRAINER_LOSS_CHUNK 1024        /* pixels whose sums one workgroup adds into one fp64 partial per term */
+#define EMD_TRAINER_SSIM_TILE 32           /* a workgroup of the SSIM forward owns 32 rows x 32 FLOATS of the [H-10][3 (W-10)] map (channels interleaved) */
+#define EMD_TL_MASK_BCE 0
+#define EMD_TL_MASK_SAFE_BCE 1
+#define EMD_TL_DEPTH_L1 0
+#define EMD_TL_DEPTH_L2 1
+#define EMD_TL_DEPTH_SMOOTH_L1 2
+typedef struct EmdTrainerLossArgs {
+    int32_t height, width;
+    int32_t mask_type, depth_type;               /* EMD_TL_MASK_*, EMD_TL_DEPTH_* */
+    int32_t normalize, inverse;                  /* the depth term's options, 0 or 1 */
+    const float* rgb;
+    const float* gt_rgb;
+    const float* opacity;                        /* or NULL */
+    const float* sky_mask;                       /* or NULL */
+    const float* depth;                          /* or NULL */
+    const float* lidar_depth;                    /* or NULL */
+    float w_rgb, w_ssim, w_mask, safe_limit;
+    float w_depth, upper_bound, w_entropy, w_smooth;
+    float* losses;                               /* [7] */
+    float* dL_drgb;                              /* or NULL */
+    float* dL_dopacity;                          /* or NULL */
+    float* dL_ddepth;                            /* or NULL */
+} EmdTrainerLossArgs;
+size_t emd_trainer_loss_workspace_size(const EmdTrainerLossArgs* args);
+int emd_trainer_loss(const EmdTrainerLossArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
