@@ -107,7 +107,9 @@ __device__ __forceinline__ v2f pinned_exp2(v2f x) {
 // prefetched one step ahead), keeps the entries whose tight footprint touches the quadrant in a 128-slot LDS ring and
 // appends the slot to the byte list of every sub-block it touches.  Once more than 64 entries are queued (or the list
 // ends) the four rows drain their lists.  No workgroup barriers, no 256-entry chunk granularity, and the scan stops as
-// soon as the 64 pixels of THIS quadrant are saturated rather than all 256 of the tile.
+// soon as the 64 pixels of THIS quadrant are saturated rather than all 256 of the tile.  The drain of a round stops as early:
+// it ends when no live pixel is left in a row that still holds an entry, and a sub-block whose 16 pixels are done gets no
+// further entries (13.8 % of the drain iterations of the headline frames, profiles/k6_drain_exit_ab.txt).
 // The position of an entry in the tile list (needed for n_contrib) rides in the unused .w of the colour record.
 // ---------------------------------------------------------------------------------------------------
 #define FQ_RING 128
@@ -180,7 +182,11 @@ __global__ void __launch_bounds__(EMD_WAVE) k_render_forward_q(RenderDims d, con
     uint32_t total = 0;
     uint32_t scanned = 0;
     while (scanned < n_tile) {
-        if (__ballot(!done) == 0ull) break;
+        const unsigned long long live = __ballot(!done);
+        if (live == 0ull) break;
+        // the sub-blocks (16-lane rows) that still hold a live pixel: a dead one queues nothing below (`done` changes in the drain only)
+        const uint32_t live4 = ((live & 0xFFFFull) ? 1u : 0u) | ((live & 0xFFFF0000ull) ? 2u : 0u) | ((live & 0xFFFF00000000ull) ? 4u : 0u) |
+                               ((live & 0xFFFF000000000000ull) ? 8u : 0u);
         // ---- scan: queue the entries whose footprint reaches this quadrant until more than 64 wait or the list ends ----
         uint32_t head = 0, len0 = 0, len1 = 0, len2 = 0, len3 = 0;
         if (STATS) st_round++;
@@ -227,59 +233,74 @@ __global__ void __launch_bounds__(EMD_WAVE) k_render_forward_q(RenderDims d, con
             const uint32_t slot = base + lane;
             uint32_t m4 = 0u, gid = 0u;
             if (slot < head) { gid = __float_as_uint(reinterpret_cast<const float*>(&s2[slot])[3]); m4 = ellipse_subblock_mask(s0[slot], s1[slot], qx0, qy0); }
-            const unsigned long long b0 = __ballot(m4 & 1u), b1 = __ballot(m4 & 2u), b2 = __ballot(m4 & 4u), b3 = __ballot(m4 & 8u);
-            const unsigned long long ba = b0 | b1 | b2 | b3;
+            // An entry that reaches only dead sub-blocks is still a numbered survivor (the numbering below uses the unmasked m4, so surv, n_contrib,
+            // quad_need and the backward's walk do not depend on it); it is not appended to a dead sub-block's list, whose 16 pixels it cannot change
+            const unsigned long long ba = __ballot(m4 != 0u);
+            const uint32_t ml = m4 & live4;
+            const unsigned long long b0 = __ballot(ml & 1u), b1 = __ballot(ml & 2u), b2 = __ballot(ml & 4u), b3 = __ballot(ml & 8u);
             if (m4) {
                 const uint32_t num = total + (uint32_t)__popcll(ba & lt);
                 sv[num] = gid;
                 reinterpret_cast<float*>(&s2[slot])[3] = __uint_as_float(num + 1);      // 1-based number of this survivor in the quadrant's list
             }
             total += (uint32_t)__popcll(ba);
-            if (m4 & 1u) s_list[0][len0 + (uint32_t)__popcll(b0 & lt)] = (uint8_t)slot;
-            if (m4 & 2u) s_list[1][len1 + (uint32_t)__popcll(b1 & lt)] = (uint8_t)slot;
-            if (m4 & 4u) s_list[2][len2 + (uint32_t)__popcll(b2 & lt)] = (uint8_t)slot;
-            if (m4 & 8u) s_list[3][len3 + (uint32_t)__popcll(b3 & lt)] = (uint8_t)slot;
+            if (ml & 1u) s_list[0][len0 + (uint32_t)__popcll(b0 & lt)] = (uint8_t)slot;
+            if (ml & 2u) s_list[1][len1 + (uint32_t)__popcll(b1 & lt)] = (uint8_t)slot;
+            if (ml & 4u) s_list[2][len2 + (uint32_t)__popcll(b2 & lt)] = (uint8_t)slot;
+            if (ml & 8u) s_list[3][len3 + (uint32_t)__popcll(b3 & lt)] = (uint8_t)slot;
             len0 += (uint32_t)__popcll(b0); len1 += (uint32_t)__popcll(b1); len2 += (uint32_t)__popcll(b2); len3 += (uint32_t)__popcll(b3);
         }
         __syncthreads();
-        const uint32_t nmax = max(max(len0, len1), max(len2, len3));
-        if (STATS) { st_drain += nmax; st_useful += len0 + len1 + len2 + len3; }
-        if (nmax) {
+        if (len0 | len1 | len2 | len3) {
             const uint32_t n = row == 0 ? len0 : row == 1 ? len1 : row == 2 ? len2 : len3;
-            const uint8_t* list = s_list[row];
-            // software pipeline: the index and record of entry i+1 are in flight while entry i is evaluated
-            uint32_t j = n ? list[0] : 0u;
+            // software pipeline: the index and record of entry i+1 are in flight while entry i is evaluated.  Every load of the loop is unconditional:
+            // past its end a row reads its last entry again (what j would hold anyway), and a row without entries reads entry 0 of a row that
+            // has one -- a valid slot that it never evaluates
+            const uint32_t some = len0 ? 0u : len1 ? 1u : len2 ? 2u : 3u;
+            const uint8_t* list = s_list[n ? row : some];
+            const uint32_t nl = n ? n - 1u : 0u;
+            uint32_t j = list[0];
             float4 g0 = s0[j], g1 = s1[j];
-#pragma unroll 2
-            for (uint32_t i = 0; i < nmax; i++) {
-                const bool active = i < n;
-                const uint32_t jn = (i + 1 < n) ? list[i + 1] : j;
-                const float4 g0n = s0[jn], g1n = s1[jn];
-                const float dx = g0.x - pfx, dy = g0.y - pfy;
-                const float power = gauss_power(g1.x, g1.y, g1.z, dx, dy);
-                const float alpha = fminf(0.99f, g0.w * pinned_exp(power));
-                const bool hit = active && !done && power <= 0.f && alpha >= (1.f / 255.f);
-                const float test_T = T * (1.f - alpha);
-                const bool stop = hit && test_T < 0.0001f;
-                const bool take = hit && !stop;
-                const float w = take ? alpha * T : 0.f;
-                const float4 g2 = s2[j];
-                C0 = __builtin_fmaf(g2.x, w, C0); C1 = __builtin_fmaf(g2.y, w, C1); C2 = __builtin_fmaf(g2.z, w, C2);
-                Dz = __builtin_fmaf(g0.z, w, Dz);
-                if (NORMAL) {
-                    const float4 g3 = s3[j];
-                    N0 = __builtin_fmaf(g3.x, w, N0); N1 = __builtin_fmaf(g3.y, w, N1); N2 = __builtin_fmaf(g3.z, w, N2);
-                }
+            // Two entries per trip, and the trip is taken only while some lane is both live and in a row that still holds an entry.  Once there
+            // is none -- the quadrant saturated in mid-drain, or only rows whose 16 pixels are done have entries left -- `hit` is false in every
+            // lane of every later iteration: nothing below can change, so the round ends here (j, g0, g1 are set up afresh by the next round).
+            // One compare + ballot and a scalar branch per pair; it is the loop's only exit (all rows exhausted gives the same empty ballot).  (The
+            // builtin takes the bool as it is; __ballot's int argument costs this loop 19 more vector instructions per pair.)
+            uint32_t i0 = 0;
+            for (; __builtin_amdgcn_ballot_w64(!done && i0 < n) != 0ull; i0 += 2) {
 #pragma unroll
-                for (int k = 0; k < NX; k++) {          // the same fma as the main colour: an extra set equals a separate call bit for bit
-                    const float4 gx = sx[k][j];
-                    X[k][0] = __builtin_fmaf(gx.x, w, X[k][0]); X[k][1] = __builtin_fmaf(gx.y, w, X[k][1]); X[k][2] = __builtin_fmaf(gx.z, w, X[k][2]);
+                for (uint32_t u = 0; u < 2; u++) {
+                    const uint32_t i = i0 + u;
+                    const bool active = i < n;
+                    const uint32_t jn = list[min(i + 1u, nl)];
+                    const float4 g0n = s0[jn], g1n = s1[jn];
+                    const float dx = g0.x - pfx, dy = g0.y - pfy;
+                    const float power = gauss_power(g1.x, g1.y, g1.z, dx, dy);
+                    const float alpha = fminf(0.99f, g0.w * pinned_exp(power));
+                    const bool hit = active && !done && power <= 0.f && alpha >= (1.f / 255.f);
+                    const float test_T = T * (1.f - alpha);
+                    const bool stop = hit && test_T < 0.0001f;
+                    const bool take = hit && !stop;
+                    const float w = take ? alpha * T : 0.f;
+                    const float4 g2 = s2[j];
+                    C0 = __builtin_fmaf(g2.x, w, C0); C1 = __builtin_fmaf(g2.y, w, C1); C2 = __builtin_fmaf(g2.z, w, C2);
+                    Dz = __builtin_fmaf(g0.z, w, Dz);
+                    if (NORMAL) {
+                        const float4 g3 = s3[j];
+                        N0 = __builtin_fmaf(g3.x, w, N0); N1 = __builtin_fmaf(g3.y, w, N1); N2 = __builtin_fmaf(g3.z, w, N2);
+                    }
+#pragma unroll
+                    for (int k = 0; k < NX; k++) {          // the same fma as the main colour: an extra set equals a separate call bit for bit
+                        const float4 gx = sx[k][j];
+                        X[k][0] = __builtin_fmaf(gx.x, w, X[k][0]); X[k][1] = __builtin_fmaf(gx.y, w, X[k][1]); X[k][2] = __builtin_fmaf(gx.z, w, X[k][2]);
+                    }
+                    T = take ? test_T : T;
+                    last = take ? __float_as_uint(g2.w) : last;
+                    done = done || stop;
+                    j = jn; g0 = g0n; g1 = g1n;
                 }
-                T = take ? test_T : T;
-                last = take ? __float_as_uint(g2.w) : last;
-                done = done || stop;
-                j = jn; g0 = g0n; g1 = g1n;
             }
+            if (STATS) { st_drain += i0; st_useful += min(len0, i0) + min(len1, i0) + min(len2, i0) + min(len3, i0); }   // iterations issued, entries held in them
         }
         __syncthreads();   // ring and lists fully consumed before the next scan overwrites them
     }
@@ -305,8 +326,8 @@ __global__ void __launch_bounds__(EMD_WAVE) k_render_forward_q(RenderDims d, con
     for (int off = 32; off; off >>= 1) need = max(need, (uint32_t)__shfl_xor((int)need, off));
     if (lane == 0) quad_need[4 * tile + quad] = need;
     if (STATS && lane == 0) {
-        // [0] scan steps (64 list words each)  [1] cull steps (64 queued entries each)  [2] drain iterations (one entry per 16-lane row each)
-        // [3] entries the four rows actually held (<= 4 x [2])  [4] scan -> cull -> drain rounds  [5] waves with a non-empty tile
+        // [0] scan steps (64 list words each)  [1] cull steps (64 queued entries each)  [2] drain iterations issued (one entry per 16-lane row each)
+        // [3] entries the four rows held in those iterations (<= 4 x [2])  [4] scan -> cull -> drain rounds  [5] waves with a non-empty tile
         atomicAdd(loop_stats, st_scan); atomicAdd(loop_stats + 1, st_cull); atomicAdd(loop_stats + 2, st_drain); atomicAdd(loop_stats + 3, st_useful);
         atomicAdd(loop_stats + 4, st_round); atomicAdd(loop_stats + 5, 1ull);
     }

@@ -4,9 +4,10 @@
     python profiles/make_isa_mix.py > profiles/r06_render_isa_mix.txt          # CPU only: hipcc -S cross-compiles gfx950
 
 render.hip is compiled to assembly with the Makefile's flags (--offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize), the two instantiations
-the headline step launches -- k_render_forward_q<true, 0> (normal image, no extra colour set) and k_render_backward_q<false, false, 0, false> --
+the headline step launches -- k_render_forward_q<true, 0, false> (normal image, no extra colour set, no counters) and k_render_backward_q<false, false, 0, false> --
 are cut into basic blocks, natural loops are found from the backward branches, and every loop body (innermost blocks only: a block belongs to
-the innermost loop that contains it) is counted by instruction class:
+the innermost loop that contains it) is counted by instruction class (K6's LOOP and MIX lines: by the loop the compiler itself names beside every
+block -- block placement around the drain's early exit makes the backward branches show six loops where there are four):
 
     plain    v_* that are none of the below (one issue slot: 1.32 ns per wave64 instruction and SIMD as measured, r02_issue_rate_microbench.txt)
     pk       v_pk_*                      two-wide fp32 (2.0 ns)
@@ -28,7 +29,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "emd_amd", "csrc")
 KERNELS = {
-    "k_render_forward_q": "k_render_forward_qILb1ELi0E",            # <NORMAL = true, NX = 0>
+    "k_render_forward_q": "k_render_forward_qILb1ELi0ELb0E",        # <NORMAL = true, NX = 0, STATS = false>
     "k_render_backward_q": "k_render_backward_qILb0ELb0ELi0ELb0E",   # <NORMAL = false, ABS = false, NX = 0, STATS = false>
 }
 NS = {"plain": 1.32, "pk": 2.0, "dpp": 2.0, "trans": 3.4}          # measured issue time per wave64 instruction and SIMD, 8 waves resident
@@ -79,14 +80,23 @@ def function_body(lines, mangled_part):
 
 
 def blocks_of(body):
-    """-> [(label, [(op, text)])] in layout order; the entry block is labelled '<entry>'.  Labels lose the function index (.LBB<n>_<m> -> .LBB_<m>, as
-    profiles/compare_kernel_isa.py normalises them): it is the kernel's position in the unit and says nothing about the block."""
-    blocks, cur, name = [], [], "<entry>"
+    """-> [(label, [(op, text, header)])] in layout order; the entry block is labelled '<entry>'.  Labels lose the function index (.LBB<n>_<m> -> .LBB_<m>, as
+    profiles/compare_kernel_isa.py normalises them): it is the kernel's position in the unit and says nothing about the block.  `header` is the label of
+    the innermost loop the COMPILER places the instruction's basic block in (None outside every loop): the asm printer writes it beside every block,
+    fall-through ones included ("in Loop: Header=BB2_12 Depth=1"; "=>This Loop Header: Depth=1" on the header itself)."""
+    blocks, cur, name, header, start = [], [], "<entry>", None, None
     for l in body:
         s = re.sub(r"\.LBB\d+_", ".LBB_", l.strip())
-        if not s or s.startswith((";", ".")) and not re.match(r"^\.LBB_\d+:", s):
-            continue
         m = re.match(r"^(\.LBB_\d+):", s)
+        if m or re.match(r"^; %bb\.\d+:", s):
+            header, start = None, (m.group(1) if m else None)
+        h = re.search(r"in Loop: Header=BB\d+_(\d+) Depth=", s)
+        if h:
+            header = ".LBB_" + h.group(1)
+        elif start and re.search(r"This (Inner )?Loop Header: Depth=", s):
+            header = start
+        if not s or s.startswith((";", ".")) and not m:
+            continue
         if m:
             blocks.append((name, cur))
             name, cur = m.group(1), []
@@ -95,7 +105,7 @@ def blocks_of(body):
         if not s:
             continue
         op = s.split()[0]
-        cur.append((op, s))
+        cur.append((op, s, header))
     blocks.append((name, cur))
     return blocks
 
@@ -105,7 +115,7 @@ def loops_of(blocks):
     index = {name: k for k, (name, _) in enumerate(blocks)}
     loops = set()
     for j, (_, ins) in enumerate(blocks):
-        for op, text in ins:
+        for op, text, _ in ins:
             if op.startswith(("s_cbranch", "s_branch")):
                 tgt = text.split()[-1]
                 if tgt in index and index[tgt] <= j:
@@ -119,7 +129,7 @@ def loops_of(blocks):
 
 def count(ins):
     c = {}
-    for op, text in ins:
+    for op, text, _ in ins:
         k = classify(op, text)
         c[k] = c.get(k, 0) + 1
     return c
@@ -169,11 +179,20 @@ def main():
         print("\n".join(out))
         # the loop that carries the per-(pixel, entry) arithmetic: the DEEPEST loop, among those the one with the most VALU instructions of its own
         best = max(rows, key=lambda r: (r[1], sum(r[2].get(k, 0) for k in ("plain", "pk", "dpp", "trans"))))
+        if kernel == "k_render_forward_q":
+            # K6's loops are siblings, and since the drain leaves early (its exit test sits in a block of its own, a latch is placed in front of the round
+            # loop's header) the layout reading above shows six "loops" where the compiler has four.  Its roles are therefore read off the compiler's own
+            # loop of every instruction: four headers in layout (= source) order.
+            ins = [x for _, b in blocks for x in b]
+            heads = [name for name, _ in blocks if any(x[2] == name for x in ins)]
+            rows = [((name, name), 1, count([x for x in ins if x[2] == name])) for name in heads]
+            straight = count([x for x in ins if x[2] is None])
         if kernel == "k_render_forward_q" and len(rows) == 4:
-            best = rows[3]          # K6's loops are siblings: the compositing drain (78.5 % of the kernel's vector instructions, r06_render_loop_trips.txt) is the last
+            best = rows[3]          # the compositing drain (78.5 % of the kernel's vector instructions, r06_render_loop_trips.txt) is the last
         c = best[2]
         valu = sum(c.get(k, 0) for k in ("plain", "pk", "dpp", "trans"))
-        summary[kernel] = dict(loop=f"{blocks[best[0][0]][0]}..{blocks[best[0][1]][0]}", valu=valu, plain=c.get("plain", 0), pk=c.get("pk", 0), dpp=c.get("dpp", 0),
+        name = lambda b: b if isinstance(b, str) else blocks[b][0]
+        summary[kernel] = dict(loop=name(best[0][0]) if best[0][0] == best[0][1] else f"{name(best[0][0])}..{name(best[0][1])}", valu=valu, plain=c.get("plain", 0), pk=c.get("pk", 0), dpp=c.get("dpp", 0),
                                trans=c.get("trans", 0), lds=c.get("lds", 0), vmem=c.get("vmem", 0), salu=c.get("salu", 0),
                                wide_fraction=round((c.get("pk", 0) + c.get("dpp", 0) + c.get("trans", 0)) / max(valu, 1), 4),
                                ns_per_valu=round(sum(c.get(k, 0) * NS[k] for k in NS) / max(valu, 1), 4))
@@ -186,7 +205,7 @@ def main():
                 valu = sum(c.get(k, 0) for k in ("plain", "pk", "dpp", "trans"))
                 k6_loops.append(f"LOOP k_render_forward_q {role} valu={valu} lds={c.get('lds', 0)} vmem={c.get('vmem', 0)} salu={c.get('salu', 0)} "
                                 f"unroll={2 if role == 'drain' else 1} ns={sum(c.get(k, 0) * NS[k] for k in NS):.1f}")
-            st = count([x for k_ in range(len(blocks)) if not any(i <= k_ <= j for (i, j), _, _ in rows) for x in blocks[k_][1]])
+            st = straight
             k6_loops.append(f"LOOP k_render_forward_q straight valu={sum(st.get(k, 0) for k in ('plain', 'pk', 'dpp', 'trans'))} lds={st.get('lds', 0)} "
                             f"vmem={st.get('vmem', 0)} salu={st.get('salu', 0)} unroll=1 ns={sum(st.get(k, 0) * NS[k] for k in NS):.1f}")
     print()

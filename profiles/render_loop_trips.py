@@ -1,6 +1,7 @@
 """K6's instructions split by loop: trip counts of the compositing kernel's loops on the headline scene (counting instantiation,
 EmdFwdArgs.loop_stats) x the static instruction counts of each loop's body (profiles/r06_render_isa_mix.txt, LOOP lines).  Run on the GPU:
-    python profiles/render_loop_trips.py > profiles/r06_render_loop_trips.txt
+    python profiles/render_loop_trips.py [MIX FILE] > profiles/r06_render_loop_trips.txt
+(MIX FILE: the make_isa_mix.py output of the build that EMD_LIB_PATH selects, when that is not the tree's.)
 The product is checked against the counter total of the same kernel (SQ_INSTS_VALU of profiles/r0N_pmc_valu.csv)."""
 import os
 import sys
@@ -31,7 +32,8 @@ with torch.no_grad():
 torch.cuda.synchronize()
 scan, cull, drain, useful, rounds, waves = [x / len(frames) for x in st.cpu().tolist()]
 loops = {}
-for line in open(os.path.join(ROOT, "profiles", "r06_render_isa_mix.txt")):
+mix_file = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r06_render_isa_mix.txt")     # (another build's static counts: its file)
+for line in open(mix_file):
     if line.startswith("LOOP k_render_forward_q"):
         f_ = line.split()
         loops[f_[2]] = {k: float(v) for k, v in (kv.split("=") for kv in f_[3:])}
