@@ -128,8 +128,9 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_sh_backward(int n, int deg, int M
         sh_basis(deg, d, bs);
         float* o = d_coeffs + (size_t)i * M * 3;
         for (int k = 0; k < M; k++) {
-            float bk = k < K ? bs[k] : 0.f;
-            o[3 * k] = bk * gc[0]; o[3 * k + 1] = bk * gc[1]; o[3 * k + 2] = bk * gc[2];
+            // a row the degree does not use is +0, not 0 * g (that is -0 for g < 0 and NaN for a non-finite g)
+            if (k < K) { o[3 * k] = bs[k] * gc[0]; o[3 * k + 1] = bs[k] * gc[1]; o[3 * k + 2] = bs[k] * gc[2]; }
+            else { o[3 * k] = 0.f; o[3 * k + 1] = 0.f; o[3 * k + 2] = 0.f; }
         }
     }
     if (d_dirs) {
