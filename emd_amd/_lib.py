@@ -236,6 +236,20 @@ class EmdMlpBranchGrads(C.Structure):
                 ("l1_grad", _f), ("out", _f), ("g_h_in", _f)]
 
 
+MLP_DET_MAX_TENSORS, MLP_DET_MAX_JOBS = 6, 64
+MLP_DET_BRANCH_BWD, MLP_DET_TRUNK_BWD, MLP_DET_BRANCH_FWD = 0, 1, 2
+
+
+class EmdMlpDetLayout(C.Structure):
+    _fields_ = [("groups", C.c_int32), ("num_tensors", C.c_int32), ("pitch", C.c_int32 * MLP_DET_MAX_TENSORS),
+                ("offset", C.c_size_t * MLP_DET_MAX_TENSORS), ("bytes", C.c_size_t)]
+
+
+class EmdMlpDetJob(C.Structure):
+    _fields_ = [("slab", _f), ("dst", _f), ("groups", C.c_int32), ("pitch", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("ld", C.c_int32), ("col0", C.c_int32), ("scale", C.c_double)]
+
+
 ADAM_MAX_TENSORS = 32
 
 
@@ -296,7 +310,9 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_motion_det_workspace_size", "emd_motion_det_workspace_offsets", "emd_motion_backward_det",
                     "emd_joint_chain_forward", "emd_joint_chain_backward", "emd_skin_forward", "emd_skin_backward",
                     "emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward",
-                    "emd_affine_workspace_size", "emd_affine_forward", "emd_affine_backward", "emd_trainer_loss_workspace_size", "emd_trainer_loss")
+                    "emd_affine_workspace_size", "emd_affine_forward", "emd_affine_backward", "emd_trainer_loss_workspace_size", "emd_trainer_loss",
+                    "emd_mlp_det_slab_bytes", "emd_mlp_branch_forward_det", "emd_mlp_branch_backward_det", "emd_mlp_trunk_backward_det", "emd_mlp_det_reduce",
+                    "emd_temporal_embed_backward_det")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -385,6 +401,13 @@ def load():
     lib.emd_mlp_trunk_backward.argtypes = [C.POINTER(EmdMlpTrunk), C.POINTER(EmdMlpTrunkGrads), C.c_void_p]
     lib.emd_mlp_branch_forward.argtypes = [C.POINTER(EmdMlpBranch), C.c_void_p]
     lib.emd_mlp_branch_backward.argtypes = [C.POINTER(EmdMlpBranch), C.POINTER(EmdMlpBranchGrads), C.c_void_p]
+    lib.emd_mlp_det_slab_bytes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(EmdMlpDetLayout)]
+    lib.emd_mlp_det_slab_bytes.restype = C.c_size_t
+    lib.emd_mlp_branch_forward_det.argtypes = [C.POINTER(EmdMlpBranch), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_mlp_branch_backward_det.argtypes = [C.POINTER(EmdMlpBranch), C.POINTER(EmdMlpBranchGrads), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_mlp_trunk_backward_det.argtypes = [C.POINTER(EmdMlpTrunk), C.POINTER(EmdMlpTrunkGrads), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_mlp_det_reduce.argtypes = [C.POINTER(EmdMlpDetJob), C.c_int, C.c_void_p]
+    lib.emd_temporal_embed_backward_det.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     lib.emd_track_heads_forward.argtypes = [C.POINTER(EmdTrackArgs), C.c_void_p]
     lib.emd_track_heads_backward.argtypes = [C.POINTER(EmdTrackArgs), C.POINTER(EmdTrackGrads), C.c_void_p]
     lib.emd_select_step_inputs.argtypes = [C.POINTER(EmdStepSelect), C.c_void_p]
@@ -537,3 +560,11 @@ def motion_det_layout(n, num_actors):
     check(load().emd_motion_det_workspace_offsets(int(n), int(num_actors), out), "emd_motion_det_workspace_offsets")
     return _det_offsets([int(x) for x in out])
 
+
+
+def mlp_det_layout(kind, args, grads=None):
+    """The slab of one deterministic MLP call (emd_mlp_det_slab_bytes): dict(groups, pitch, offset, bytes); `args` / `grads` are the call's structs."""
+    out = EmdMlpDetLayout()
+    n = int(load().emd_mlp_det_slab_bytes(int(kind), C.byref(args), None if grads is None else C.byref(grads), C.byref(out)))
+    k = out.num_tensors
+    return dict(groups=int(out.groups), pitch=[int(x) for x in out.pitch[:k]], offset=[int(x) for x in out.offset[:k]], bytes=n)

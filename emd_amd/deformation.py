@@ -54,7 +54,9 @@ class DeformOptions:
         self.apply_coarse_dx = self.apply_final_dx = True
         self.direct_add_dx = self.direct_add_ds = self.direct_add_dr = self.direct_add_do = self.direct_add_dshs = True
         self.no_ds = self.no_dr = self.no_fine_hexplane_features = True          # run_dynamic_nvs.sh
-        self.deterministic = False   # (not a reference option) bit-reproducible HexPlane gradients: HexPlaneField.deterministic
+        # (not a reference option) every output and gradient of the network a fixed function of the call's inputs: HexPlaneField.deterministic (DESIGN.md
+        # section 8.9), the MLP kernels' and the temporal table's forms without float atomics (section 8.14: mlp.level_mlp, temporal_embed)
+        self.deterministic = False
         self.fused_mlp = True        # (not a reference option) trunk + heads on the fused fp32-MFMA kernels of csrc/mlp.hip; False: rocBLAS GEMMs
         for k, v in kw.items():
             setattr(self, k, v)
@@ -64,7 +66,7 @@ class _TemporalEmbed(torch.autograd.Function):
     """weight [B, rows, dim] (or [rows, dim]), t: 1-element device tensor -> the embedding row(s) at time t after a resize to k rows."""
 
     @staticmethod
-    def forward(ctx, weight, t, k):
+    def forward(ctx, weight, t, k, deterministic=False):
         if weight.device.type != "cuda":
             raise L.EmdError("temporal_embed needs tensors on a ROCm device; there is no CPU path")
         w = weight.detach().contiguous().float()
@@ -77,7 +79,7 @@ class _TemporalEmbed(torch.autograd.Function):
         L.check(L.load().emd_temporal_embed_forward(w.data_ptr(), tables, rows, dim, int(k), tt.data_ptr(), out.data_ptr(), _stream()),
                 "emd_temporal_embed_forward")
         ctx.save_for_backward(w, tt)
-        ctx.k, ctx.t_shape = int(k), tuple(t.shape)
+        ctx.k, ctx.t_shape, ctx.deterministic = int(k), tuple(t.shape), bool(deterministic)
         return out
 
     @staticmethod
@@ -87,10 +89,15 @@ class _TemporalEmbed(torch.autograd.Function):
         rows, dim = w.shape[-2:]
         g_w = torch.zeros_like(w) if ctx.needs_input_grad[0] else None
         g_t = torch.zeros(1, device=w.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
-        L.check(L.load().emd_temporal_embed_backward(w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(),
-                                                     g_out.contiguous().float().data_ptr(), L.ptr(g_w), L.ptr(g_t), _stream()),
-                "emd_temporal_embed_backward")
-        return g_w, (g_t.reshape(ctx.t_shape) if g_t is not None else None), None
+        g = g_out.contiguous().float()
+        if ctx.deterministic:      # the gather form: no atomics (csrc/embed_det.hip); several tables leave one dL/dt partial each
+            parts = torch.empty(tables, device=w.device, dtype=torch.float32) if g_t is not None and tables > 1 else None
+            L.check(L.load().emd_temporal_embed_backward_det(w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(), g.data_ptr(), L.ptr(g_w), L.ptr(g_t),
+                                                             L.ptr(parts), _stream()), "emd_temporal_embed_backward_det")
+        else:
+            L.check(L.load().emd_temporal_embed_backward(w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(), g.data_ptr(), L.ptr(g_w), L.ptr(g_t),
+                                                         _stream()), "emd_temporal_embed_backward")
+        return g_w, (g_t.reshape(ctx.t_shape) if g_t is not None else None), None, None
 
 
 def _first_time(time_emb):
@@ -105,9 +112,10 @@ def _first_time(time_emb):
     return time_emb.reshape(-1)[:1]
 
 
-def temporal_embed(weight, t, k):
-    """Row of the temporal table (resized to k rows) at time t (a 1-element tensor ON THE DEVICE: no host sync)."""
-    return _TemporalEmbed.apply(weight, t, k)
+def temporal_embed(weight, t, k, deterministic=False):
+    """Row of the temporal table (resized to k rows) at time t (a 1-element tensor ON THE DEVICE: no host sync).
+    `deterministic`: the backward without float atomics: the same sums in a fixed order."""
+    return _TemporalEmbed.apply(weight, t, k, bool(deterministic))
 
 
 def batch_quaternion_multiply(q1, q2):
@@ -340,10 +348,19 @@ class Deformation(nn.Module):
 
     def _level_fused(self, pts, time_emb, embeddings, coarse, it, num_down_emb, need_feat=True, l1_dshs=False, l1_keys=()):
         """The same level as `_feature` + `_heads`, or None when the configuration is outside what the fused kernels serve (width 64,
-        defor_depth 1, at most 128 HexPlane features, an embedding of at most 8 values, at most six heads): the GEMM path then runs."""
+        defor_depth 1, at most 128 HexPlane features, an embedding of at most 8 values, at most six heads): the GEMM path then runs -- unless
+        `args.deterministic` is set: the rocBLAS path has no fixed-order form, so such a level raises NotImplementedError."""
         from . import mlp
         a = self.args
-        if not getattr(a, "fused_mlp", True) or self.D != 1 or self.W != mlp.WIDTH or pts.device.type != "cuda":
+        det = bool(getattr(a, "deterministic", False))
+
+        def outside(why):
+            if det:
+                raise NotImplementedError(f"DeformOptions.deterministic needs the fused MLP kernels (DESIGN.md section 8.14), which do not serve {why}")
+            return None
+        if not getattr(a, "fused_mlp", True) or self.D != 1 or self.W != mlp.WIDTH:
+            return outside("fused_mlp = False, defor_depth != 1 or a width other than 64")
+        if pts.device.type != "cuda":
             return None
         suffix = "" if coarse else "_f"
         lin = (self.feature_out if coarse else self.feature_out_f)[0]
@@ -357,12 +374,14 @@ class Deformation(nn.Module):
             d = self.dino_head
             branches.append((False, [(d[0].weight, d[0].bias), (d[2].weight, d[2].bias)], (d[4].weight, d[4].bias)))
         hidden_shapes = [w.shape for _, hid, _ in branches for w, _ in hid]
-        if not branches or not mlp.eligible(ka, kb, hidden_shapes, [wo.shape[0] for _, _, (wo, _) in branches]):
+        if not branches:
             return None
+        if not mlp.eligible(ka, kb, hidden_shapes, [wo.shape[0] for _, _, (wo, _) in branches]):
+            return outside("these shapes (more than six heads, more than 128 HexPlane features or an embedding wider than 8)")
         Wm, bias, col = lin.weight, lin.bias, ka
         if not a.no_temporal_embedding_dim:
             T = self.temporal_embedding_dim
-            te = temporal_embed(self.weight, _first_time(time_emb), self._num_rows(coarse, it, num_down_emb))
+            te = temporal_embed(self.weight, _first_time(time_emb), self._num_rows(coarse, it, num_down_emb), deterministic=det)
             bias = torch.addmv(bias, Wm[:, col:col + T], te)           # the same row for every Gaussian: a bias, not N copies
             col += T
         xa = self.grid(pts[:, :3], time_emb[:, :1]) if use_hex else None
@@ -370,7 +389,7 @@ class Deformation(nn.Module):
         l1_names = [k for k in (tuple(l1_keys) + (("dshs",) if l1_dshs else ())) if k in keys]
         l1_names = list(dict.fromkeys(l1_names))                   # (unique, in the order asked for)
         l1_heads = [keys.index(k) for k in l1_names]
-        outs = mlp.level_mlp(xa, embeddings if use_emb else None, Wm, bias, 0, col, branches, l1_heads=l1_heads)
+        outs = mlp.level_mlp(xa, embeddings if use_emb else None, Wm, bias, 0, col, branches, l1_heads=l1_heads, deterministic=det)
         out = dict(dx=None, ds=None, dr=None, do=None, dshs=None, feat=None)
         for (_, key), o in zip(heads, outs):
             out[key] = o.reshape(o.shape[0], 16, 3) if key == "dshs" else o

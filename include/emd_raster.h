@@ -720,6 +720,14 @@ int emd_temporal_embed_forward(const float* weight, int num_tables, int rows, in
                                void* hip_stream);
 int emd_temporal_embed_backward(const float* weight, int num_tables, int rows, int dim, int k, const float* t, const float* dL_dout,
                                 float* dL_dweight, float* dL_dt, void* hip_stream);
+/* The same gradients without atomics (a compatible extension of ABI 30), in gather form: one lane per column of the at most
+ * four table rows a sample touches adds ITS contributions in the default kernel's issue order -- column j ascending, then the resized row r = 0, 1,
+ * then (ha, x0), (hb, x0), (ha, x1), (hb, x1) --, each product formed as the default kernel forms it, in double precision from 0.0 with one
+ * rounding, and WRITES the result to dL_dweight (the caller zeroes it, as for the default entry: rows no sample touches keep the zeros).  dL_dt: the
+ * fixed xor tree of each table, the tables then added in ascending order by one thread onto the caller's value.  `dt_partials`: num_tables floats,
+ * device, never cleared; needed when dL_dt is given and num_tables > 1 (EMD_ERR_WORKSPACE when missing). */
+int emd_temporal_embed_backward_det(const float* weight, int num_tables, int rows, int dim, int k, const float* t, const float* dL_dout,
+                                    float* dL_dweight, float* dL_dt, float* dt_partials, void* hip_stream);
 
 /* Learned per-actor track offsets, all actors and both levels in one launch each way
  * (embedding_track_trans_offset / embedding_track_rot_offset / query_coarse_to_fine / get_temporal_embed,
@@ -880,6 +888,51 @@ int emd_mlp_trunk_forward(const EmdMlpTrunk* args, void* hip_stream);
 int emd_mlp_trunk_backward(const EmdMlpTrunk* args, const EmdMlpTrunkGrads* grads, void* hip_stream);
 int emd_mlp_branch_forward(const EmdMlpBranch* args, void* hip_stream);
 int emd_mlp_branch_backward(const EmdMlpBranch* args, const EmdMlpBranchGrads* grads, void* hip_stream);
+
+/* ---- Deterministic forms of the MLP kernels: no float atomics (a compatible extension of ABI 30) --------------
+ * The default kernels above add one total per workgroup onto every weight / bias gradient element (and onto l1_sum) with float atomics: the
+ * order in which the up to 512 workgroups of a launch reach an address is the only scheduling-dependent step.  The forms below run the SAME
+ * kernel bodies up to and including the workgroup's sum and then STORE the total to slot blockIdx.x of a slab [G][pitch] per tensor, with the
+ * default flush's bounds: every workgroup writes every element of its slot, zeros included, so the slab is caller-owned, 256-byte aligned and
+ * NEVER cleared.  emd_mlp_det_reduce then adds, per destination element, the G slots in ascending workgroup order in double precision from 0.0,
+ * multiplies by the job's scale (still in double precision), rounds once to float and WRITES the result: the destination need not be cleared,
+ * and elements the default kernels never add to (the temporal columns of the trunk's d_w) are not written.  Every other output (out, g_h, d_xa,
+ * d_xb) has the default call's bits.  (A bias partial lives in both lane halves of wave 0, which the atomic form adds onto one address: the slab
+ * holds lower half + upper half, added in that order.)
+ *   G = the grid of the kernel that serves the call: ceil(ceil(N / 32) / 4) workgroups, at most 256 per_cu (per_cu = 2 for the forward of a
+ *   one-hidden-layer head of at most 32 outputs and for the trunk backward with ka = 0 outside the embedding kernel, else 1).
+ *   tensors of a slab, in this order, `pitch` floats per slot, element (o, i) of the [rows, cols] gradient block at o cols + i:
+ *     EMD_MLP_DET_BRANCH_BWD  0 d_w_hidden[0] 4096 | 1 d_b_hidden[0] 64 | 2 d_w_hidden[1] 4096 | 3 d_b_hidden[1] 64 (pitch 0 for depth 1) |
+ *                             4 d_w_out 64 out_dim | 5 d_b_out out_dim
+ *     EMD_MLP_DET_TRUNK_BWD   0 d_w[:, col_a : col_a + ka] 64 ka | 1 d_w[:, col_b : col_b + kb] 64 kb | 2 d_b 64
+ *     EMD_MLP_DET_BRANCH_FWD  0 the workgroup's share of sum |out|, 1 float (scale of the reduction: 1 / (N out_dim))
+ *   offset[t] (bytes, multiples of 256) = the sum of the earlier tensors' 4 G pitch bytes, each rounded up to 256; bytes = the end of the last.
+ * emd_mlp_det_slab_bytes is host-only: it fills *layout (may be NULL) and returns `bytes`; 0 for num_points == 0 or arguments the entry points
+ * refuse.  `grads` is read by EMD_MLP_DET_TRUNK_BWD alone (the alignment of d_xb takes part in the choice of the kernel) and may be NULL.
+ * The entry points apply every refusal of the default ones; a missing, unaligned (256 B) or short slab is EMD_ERR_WORKSPACE, decided before
+ * anything is launched; num_points == 0 launches nothing and needs no slab.  The forward form needs l1_sum (it is what the call is for). */
+#define EMD_MLP_DET_MAX_TENSORS 6
+#define EMD_MLP_DET_MAX_JOBS 64
+enum { EMD_MLP_DET_BRANCH_BWD = 0, EMD_MLP_DET_TRUNK_BWD = 1, EMD_MLP_DET_BRANCH_FWD = 2 };
+typedef struct EmdMlpDetLayout {
+    int32_t groups, num_tensors;                 /* G; 6 / 3 / 1 */
+    int32_t pitch[EMD_MLP_DET_MAX_TENSORS];      /* floats per slot (0: the call has no such tensor) */
+    size_t offset[EMD_MLP_DET_MAX_TENSORS];      /* bytes from the slab's start */
+    size_t bytes;
+} EmdMlpDetLayout;
+typedef struct EmdMlpDetJob {
+    const float* slab;                           /* [groups][pitch], pitch >= rows cols */
+    float* dst;                                  /* element (o, i) -> dst[o ld + col0 + i] = (float)(scale * sum over the slots, ascending) */
+    int32_t groups, pitch, rows, cols, ld, col0;
+    double scale;
+} EmdMlpDetJob;
+size_t emd_mlp_det_slab_bytes(int kind, const void* args, const void* grads, EmdMlpDetLayout* layout);
+int emd_mlp_branch_forward_det(const EmdMlpBranch* args, void* l1_slab, size_t slab_bytes, void* hip_stream);
+int emd_mlp_branch_backward_det(const EmdMlpBranch* args, const EmdMlpBranchGrads* grads, void* slabs, size_t slab_bytes, void* hip_stream);
+int emd_mlp_trunk_backward_det(const EmdMlpTrunk* args, const EmdMlpTrunkGrads* grads, void* slabs, size_t slab_bytes, void* hip_stream);
+/* `jobs`: a HOST array of 1..EMD_MLP_DET_MAX_JOBS jobs (passed to the one launch by value: nothing is read from it after the call returns).
+ * groups >= 1, pitch >= rows cols, rows, cols >= 1, ld >= col0 + cols, non-NULL pointers; EMD_ERR_INVALID otherwise. */
+int emd_mlp_det_reduce(const EmdMlpDetJob* jobs, int num_jobs, void* hip_stream);
 
 /* ---- Adaptive density control on the device ----------------------------------------------------
  * densify = densify_and_clone + densify_and_split, prune = prune / prune_points of S3Gaussian/scene/gaussian_model.py:441-603,
