@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libemd_raster.so")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 MAX_EXTRA = 2
 SETTINGS_DEV_FLOATS = 38
 TILE = 16
@@ -163,8 +163,8 @@ DENSIFY_MAX_TENSORS = 40
 
 class EmdDensifyArgs(C.Structure):
     _fields_ = [("num_points", C.c_int32), ("mode", C.c_int32), ("scaling", _f), ("opacity", _f), ("grad_accum", _f), ("denom", _f),
-                ("max_radii2D", _f), ("extra_drop", _f), ("grad_threshold", C.c_float), ("percent_dense", C.c_float),
-                ("scene_extent", C.c_float), ("min_opacity", C.c_float), ("max_screen_size", C.c_float)]
+                ("max_radii2D", _f), ("extra_drop", _f), ("grad_threshold", C.c_float), ("size_threshold", C.c_float),
+                ("min_opacity", C.c_float), ("max_screen_size", C.c_float)]
 
 
 class EmdRefineArgs(C.Structure):

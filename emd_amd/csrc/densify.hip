@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_densify_decide(EmdDensifyArgs a, 
         float g = a.grad_accum[i] / a.denom[i];
         if (g != g) g = 0.f;
         const bool hot = g >= a.grad_threshold;                       // (torch.norm of the [N,1] column = |g|; g >= 0)
-        const bool small_ = smax <= a.percent_dense * a.scene_extent;
+        const bool small_ = smax <= a.size_threshold;                     // the host's product, rounded once (EmdDensifyArgs)
         if (hot && small_) c |= CODE_CLONE;
         if (hot && !small_) c = CODE_SPLIT;                           // the original is removed after its two samples are appended
     } else {
@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_densify_decide(EmdDensifyArgs a, 
         // the world
         const float op = 1.f / (1.f + expf(-a.opacity[i]));
         bool drop = op < a.min_opacity;
-        if (a.max_screen_size > 0.f) drop = drop || a.max_radii2D[i] > a.max_screen_size || smax > 0.1f * a.scene_extent;
+        if (a.max_screen_size > 0.f) drop = drop || a.max_radii2D[i] > a.max_screen_size || smax > a.size_threshold;
         if (a.extra_drop && a.extra_drop[i]) drop = true;
         if (drop) c = 0;
     }

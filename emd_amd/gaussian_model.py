@@ -391,7 +391,7 @@ class GaussianModel:
         `samples [2, n_split, 3]`: standard normals to use instead of the Philox draw (tests)."""
         a = L.EmdDensifyArgs()
         a.scaling, a.grad_accum, a.denom = self._scaling.data_ptr(), self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr()
-        a.grad_threshold, a.percent_dense, a.scene_extent = float(max_grad), float(self.percent_dense), float(extent)
+        a.grad_threshold, a.size_threshold = float(max_grad), float(self.percent_dense * extent)       # the double product, rounded to float once
         return self._restructure(L.DENSIFY_MODE_DENSIFY, a, samples)
 
     def prune(self, max_grad, min_opacity, extent, max_screen_size):
@@ -411,7 +411,7 @@ class GaussianModel:
         if mask is not None:
             m8 = mask.to(self.device).to(torch.uint8).contiguous()
             a.extra_drop = m8.data_ptr()
-        a.min_opacity, a.scene_extent = float(min_opacity), float(extent)
+        a.min_opacity, a.size_threshold = float(min_opacity), float(0.1 * extent)       # the double product, rounded to float once
         a.max_screen_size = float(max_screen_size) if max_screen_size else 0.0
         return self._restructure(L.DENSIFY_MODE_PRUNE, a)
 

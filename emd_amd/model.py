@@ -125,10 +125,10 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
             a.scaling = bg(full["_scaling"]).data_ptr()
             if mode == L.DENSIFY_MODE_DENSIFY:
                 a.grad_accum, a.denom = bg(stats[0]).data_ptr(), bg(stats[1]).data_ptr()
-                a.grad_threshold, a.percent_dense, a.scene_extent = float(max_grad), float(percent_dense), float(extent)
+                a.grad_threshold, a.size_threshold = float(max_grad), float(percent_dense * extent)       # the double product, rounded to float once
             else:
                 a.opacity, a.max_radii2D = bg(full["_opacity"]).data_ptr(), bg(stats[2]).data_ptr()
-                a.min_opacity, a.scene_extent = float(min_opacity), float(extent)
+                a.min_opacity, a.size_threshold = float(min_opacity), float(0.1 * extent)
                 a.max_screen_size = float(max_screen_size) if max_screen_size else 0.0
             jobs = [(bg(full[nm]), roles[nm]) for nm in names]
             keys = [("param", nm) for nm in names]

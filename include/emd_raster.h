@@ -66,7 +66,7 @@ extern "C" {
 /* (the deterministic backward extends ABI 30 compatibly -- a new flag bit, two fields at the END of EmdBwdArgs that are read only when the flag
  * is set, new entry points -- so a caller built against the earlier ABI 30 header keeps working and the number stays; the skinning entry points
  * and the plane regularisers at the end of this header are the same kind of extension: new functions and structs only) */
-#define EMD_ABI_VERSION 30
+#define EMD_ABI_VERSION 31
 
 /* tile geometry is part of the sort-key contract (tile_id << 32 | depth bits) */
 #define EMD_TILE_X 16
@@ -942,7 +942,10 @@ int emd_mlp_det_reduce(const EmdMlpDetJob* jobs, int num_jobs, void* hip_stream)
  *   emd_densify_scan    -> the counts become exclusive block offsets; totals[3]: num_out = keep + clone + 2 split is the event's one host read
  *   emd_densify_index   -> src[num_out], kind[num_out] (0 survivor, 1 clone, 2 / 3 split sample replica 0 / 1), in the
  *                          reference's output order: survivors, clones, replica 0, replica 1
- *   emd_densify_gather  -> every output tensor */
+ *   emd_densify_gather  -> every output tensor
+ * Thresholds are the host's products (size_threshold = percent_dense * scene_extent, 0.1 * scene_extent) formed in double and rounded to float
+ * once, as torch rounds a Python scalar: the device multiplies nothing (a product of two rounded floats differs from it by an ulp for about
+ * a quarter of all extents, and a Gaussian whose max exp(scale) sits between the two would be cloned where the reference splits it). */
 enum { EMD_DENSIFY_MODE_DENSIFY = 0, EMD_DENSIFY_MODE_PRUNE = 1,
        EMD_DENSIFY_MODE_REFINE = 2   /* OmniRe's per-class refinement (VanillaGaussians.refinement_after, models/gaussians/vanilla.py:206-297): split (the original
                                         STAYS, its log-scale reduced in place), duplicate and cull as ONE event -- see EmdRefineArgs below */ };
@@ -962,7 +965,9 @@ typedef struct EmdDensifyArgs {
     const float* denom;            /* [N] (densify) */
     const float* max_radii2D;      /* [N] (prune with max_screen_size > 0) */
     const uint8_t* extra_drop;     /* [N] or NULL: additional rows to drop in prune mode (prune_points(mask) with a caller's mask) */
-    float grad_threshold, percent_dense, scene_extent;      /* densify */
+    float grad_threshold;                                   /* densify */
+    float size_threshold;                                   /* densify: percent_dense * scene_extent (clone where max exp(scale) <= it, split above);
+                                                               prune: 0.1 * scene_extent (drop where max exp(scale) > it) */
     float min_opacity, max_screen_size;                     /* prune; max_screen_size <= 0: the size tests are off */
 } EmdDensifyArgs;
 

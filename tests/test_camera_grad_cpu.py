@@ -23,9 +23,9 @@ def test_entry_points_are_declared_and_exported():
         assert n in L.EXPORTED_SYMBOLS and hasattr(lib, n)
 
 
-def test_abi_30_in_header_binding_and_library():
+def test_abi_31_in_header_binding_and_library():
     v = int(re.search(r"#define EMD_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "emd_raster.h")).read()).group(1))
-    assert v == L.ABI_VERSION == L.load().emd_abi_version() == 30
+    assert v == L.ABI_VERSION == L.load().emd_abi_version() == 31
 
 
 def test_workspace_size_is_monotone_and_never_empty():

@@ -71,6 +71,31 @@ def test_tile_pass_counts(kw):
         compare_forward(hip, orc, tol=IMAGE_TOL)
 
 
+@pytest.mark.parametrize("kw,late_nonempty,late_buckets", [
+    (dict(n=3000, H=2048, W=2048, seed=43, scale_mult=6.0), 8192, 26),   # 16 384 tiles, D = 1 778 619: every late tile has a list
+    (dict(n=400, H=4096, W=4096, seed=43), 44861, 2),                    # 65 536 tiles: the last size that takes the ordering kernel
+], ids=lambda k: "-".join(f"{a}{b}" for a, b in k.items()) if isinstance(k, dict) else str(k))
+def test_tile_order_past_the_kept_tiles(kw, late_nonempty, late_buckets):
+    """The dispatch-order kernel keeps a thread's first eight tiles (8 192 in all) in registers and walks the tiles past them with two plain
+    loops (histogram, then placement); above 65 536 tiles the identity order replaces it.  Both cases sit between the two: a tile missing
+    from the order would stay unrendered, one placed twice would leave another out.  The oracle's list lengths (16-entry buckets, as the kernel
+    forms them) say how many late tiles are non-empty and how many buckets they span."""
+    case = make_case(**kw)
+    orc = run_oracle(case, backward=False)
+    ranges = np.asarray(orc["bin"]["ranges"]).astype(np.int64)
+    T = ranges.shape[0]
+    late = (ranges[:, 1] - ranges[:, 0])[8192:]
+    assert 8192 < T <= 65536, "the case does not reach the plain loops of the ordering kernel"
+    assert int((late > 0).sum()) == late_nonempty and np.unique(np.minimum(late >> 4, 1023)).size == late_buckets
+    if kw["H"] == 2048:
+        assert T == 16384 and orc["bin"]["D"] == 1778619 and late_buckets >= 8
+    else:
+        assert T == 65536
+    for keep_all in (False, True):
+        hip = run_hip(case, backward=False, keep_all_pairs=keep_all)
+        compare_forward(hip, orc, tol=IMAGE_TOL)
+
+
 @pytest.mark.parametrize("kw", [
     dict(n=12000, H=16, W=16, seed=45),                # one tile: zero tile passes
     dict(n=12000, H=16, W=40, seed=46),                # three tiles: one tile pass

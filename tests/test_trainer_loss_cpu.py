@@ -127,7 +127,7 @@ def test_new_symbols_exported_and_abi_unchanged():
     lib = L.load()
     for n in NEW_SYMBOLS:
         assert n in L.EXPORTED_SYMBOLS and hasattr(lib, n)
-    assert lib.emd_abi_version() == L.ABI_VERSION == 30
+    assert lib.emd_abi_version() == L.ABI_VERSION == 31
 
 
 def test_new_struct_layout_and_constants_match_c():
