@@ -13,6 +13,7 @@
 //   k_ssim_backward    same tiling: dL/dx = conv(dmu1) + 2 x conv(dsigma1^2) + y conv(dsigma12), scaled by
 //                      -lambda_dssim / (3 H W) and ADDED to the L1 gradient; also normalises the depth gradient by the
 //                      valid count that is only known after the first pass
+//   k_depth_normalize  that normalisation and the "no sky pixel at all" gate alone, when dL/dimage is not wanted or lambda_dssim is 0
 //   k_loss_finalize    the five scalars
 // HBM-bound: ~12 image-sized reads / writes in total.  fp32 throughout; the separable window equals the reference's outer
 // product window up to rounding (tests: loss terms 1e-6, gradients 1e-4 of the largest entry).
@@ -59,6 +60,9 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_loss_pointwise(EmdLossArgs a, flo
     const float weight_v = (use_sky ? a.weight : a.image)[pc];
     const uint8_t sky_v = (use_sky ? a.sky_mask : reinterpret_cast<const uint8_t*>(a.image))[pc];
     if (p < HW) {
+        // a requested gradient whose term is off (no input, or its lambda switches it off) is +0 everywhere, and is written here
+        if (a.dL_ddepth && !use_depth) a.dL_ddepth[p] = 0.f;
+        if (a.dL_dweight && !use_sky) a.dL_dweight[p] = 0.f;
         const float inv_n = 1.f / (float)(3 * HW);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -283,7 +287,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_ssim_backward(EmdLossArgs a, Win 
     }
 }
 
-// no SSIM term: the depth gradient still needs its 1 / count, the sky gradient its "any sky pixel at all" gate
+// no SSIM gradient: the depth gradient still needs its 1 / count, the sky gradient its "any sky pixel at all" gate
 __global__ void __launch_bounds__(EMD_BLOCK) k_depth_normalize(EmdLossArgs a, const float* __restrict__ sums) {
     const size_t HW = (size_t)a.height * a.width;
     const size_t p = (size_t)blockIdx.x * EMD_BLOCK + threadIdx.x;
@@ -338,14 +342,17 @@ extern "C" int emd_image_loss(const EmdLossArgs* a, void* workspace, size_t work
     hipLaunchKernelGGL(k_loss_pointwise, dim3(pb), dim3(EMD_BLOCK), 0, st, *a, sums);
     EMD_LAUNCH_CHECK();
     const unsigned tiles = (unsigned)(((a->width + SS_T - 1) / SS_T) * ((a->height + SS_T - 1) / SS_T));
+    // after the point-wise pass the depth gradient still needs its 1 / count and the sky gradient its "any sky pixel at all" gate: k_ssim_backward
+    // does both on its way when dL/dimage is wanted (the ordinary step: no launch of their own), k_depth_normalize otherwise
+    const bool fix_depth = a->dL_ddepth && a->depth && a->lambda_depth != 0.f, fix_sky = a->dL_dweight && a->weight && a->lambda_sky > 0.f;
     if (a->lambda_dssim != 0.f) {
         hipLaunchKernelGGL(k_ssim_forward, dim3(tiles, 3), dim3(EMD_BLOCK), 0, st, *a, win, sums, a->dL_dimage ? dmaps : nullptr);
         EMD_LAUNCH_CHECK();
-        if (a->dL_dimage || a->dL_ddepth) {
-            hipLaunchKernelGGL(k_ssim_backward, dim3(tiles, 3), dim3(EMD_BLOCK), 0, st, *a, win, sums, dmaps);
-            EMD_LAUNCH_CHECK();
-        }
-    } else if ((a->dL_ddepth && a->depth && a->lambda_depth != 0.f) || (a->dL_dweight && a->weight && a->lambda_sky > 0.f)) {
+    }
+    if (a->lambda_dssim != 0.f && a->dL_dimage) {
+        hipLaunchKernelGGL(k_ssim_backward, dim3(tiles, 3), dim3(EMD_BLOCK), 0, st, *a, win, sums, dmaps);
+        EMD_LAUNCH_CHECK();
+    } else if (fix_depth || fix_sky) {
         hipLaunchKernelGGL(k_depth_normalize, dim3(pb), dim3(EMD_BLOCK), 0, st, *a, sums);
         EMD_LAUNCH_CHECK();
     }

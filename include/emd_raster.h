@@ -585,7 +585,14 @@ int emd_sky_backward_det(const EmdSkyBwdArgs* args, void* det_ws, size_t det_byt
 /* ---- image-loss tail -----------------------------------------------------------------
  * loss = L1 + lambda_depth * depth L2 + lambda_dssim * (1 - SSIM 11x11) + lambda_sky * sky BCE, with the gradients with
  * respect to the rendered image, depth and weight in the planar layouts emd_raster_backward consumes.  Replaces
- * S3Gaussian/utils/loss_utils.py:21-98 (compute_depth "l2", l1_loss, ssim) as used in S3Gaussian/train.py:226-363. */
+ * S3Gaussian/utils/loss_utils.py:21-98 (compute_depth "l2", l1_loss, ssim) as used in S3Gaussian/train.py:226-363.
+ * The depth term is on when depth / gt_depth are given and lambda_depth != 0, the sky term when weight / sky_mask are given and lambda_sky > 0.
+ * Two rules about the gradients:
+ *   - every requested gradient (pointer not NULL) is written in full by the call.  One whose term is off is +0 everywhere, as is dL_ddepth
+ *     without a single valid lidar pixel: the caller may hand over uninitialised memory.  An output passed as NULL is not computed, and the
+ *     other outputs are bit for bit what they are when all are requested;
+ *   - the sky term is applied only when sky_mask holds at least one sky pixel (train.py:360).  Without one its loss is 0 and dL_dweight is +0
+ *     everywhere, whichever other gradients are requested and whatever lambda_dssim is. */
 typedef struct EmdLossArgs {
     int32_t height, width;
     const float* image;        /* [3,H,W] rendered */
