@@ -312,7 +312,9 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward",
                     "emd_affine_workspace_size", "emd_affine_forward", "emd_affine_backward", "emd_trainer_loss_workspace_size", "emd_trainer_loss",
                     "emd_mlp_det_slab_bytes", "emd_mlp_branch_forward_det", "emd_mlp_branch_backward_det", "emd_mlp_trunk_backward_det", "emd_mlp_det_reduce",
-                    "emd_temporal_embed_backward_det")
+                    "emd_temporal_embed_backward_det",
+                    "emd_track_det_workspace_size", "emd_track_det_workspace_offsets", "emd_actor_row_sum_det", "emd_track_heads_forward_det",
+                    "emd_track_heads_backward_det", "emd_tracked_pose_backward_det")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -409,6 +411,14 @@ def load():
     lib.emd_mlp_det_reduce.argtypes = [C.POINTER(EmdMlpDetJob), C.c_int, C.c_void_p]
     lib.emd_temporal_embed_backward_det.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     lib.emd_track_heads_forward.argtypes = [C.POINTER(EmdTrackArgs), C.c_void_p]
+    lib.emd_track_det_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.emd_track_det_workspace_size.restype = C.c_size_t
+    lib.emd_track_det_workspace_offsets.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.emd_actor_row_sum_det.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]
+    lib.emd_track_heads_forward_det.argtypes = [C.POINTER(EmdTrackArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_track_heads_backward_det.argtypes = [C.POINTER(EmdTrackArgs), C.POINTER(EmdTrackGrads), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_tracked_pose_backward_det.argtypes = [C.POINTER(EmdTrackedPoseArgs), C.POINTER(EmdTrackedPoseGrads), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_track_heads_backward.argtypes = [C.POINTER(EmdTrackArgs), C.POINTER(EmdTrackGrads), C.c_void_p]
     lib.emd_select_step_inputs.argtypes = [C.POINTER(EmdStepSelect), C.c_void_p]
     lib.emd_tracked_pose_forward.argtypes = [C.POINTER(EmdTrackedPoseArgs), C.c_void_p]
@@ -560,6 +570,35 @@ def motion_det_layout(n, num_actors):
     check(load().emd_motion_det_workspace_offsets(int(n), int(num_actors), out), "emd_motion_det_workspace_offsets")
     return _det_offsets([int(x) for x in out])
 
+def track_det_workspace_size(num_actors, head_width=0, num_points=0, row_width=0):
+    """Bytes of the workspace of the deterministic actor chain (emd_track_det_workspace_size): (A, dim + E, 0, 0) for the chain's backward,
+    (A, 0, n, width) for emd_actor_row_sum_det."""
+    b = int(load().emd_track_det_workspace_size(int(num_actors), int(head_width), int(num_points), int(row_width)))
+    if b == 0:
+        raise EmdError(f"the deterministic actor chain does not serve {num_actors} actors, width {head_width}, {num_points} points, rows of {row_width}")
+    return b
+
+
+def track_det_layout(num_actors, head_width=0, num_points=0, row_width=0):
+    """Offsets inside that workspace (emd_track_det_workspace_offsets): a dict; `pitch` is the slab's row pitch in floats, the rest are bytes."""
+    out = (C.c_size_t * 8)()
+    check(load().emd_track_det_workspace_offsets(int(num_actors), int(head_width), int(num_points), int(row_width), out), "emd_track_det_workspace_offsets")
+    o = [int(x) for x in out]
+    return dict(slab=o[0], pitch=o[1], dh=o[2], raw_keys=o[3], keys=o[4], slots=o[5], counts=o[6], bytes=o[7])
+
+
+def actor_row_sum_det(rows, width, ids, num_actors, segment_start=None, col0=0):
+    """[num_actors, width]: per actor the pinned segmented sum of rows[i, col0 : col0 + width] over the points with ids[i] == a, in ascending i
+    (emd_actor_row_sum_det).  rows: contiguous fp32 [n, pitch]; ids: int32 [n]; segment_start: int32 [A + 1] when the ids are sorted by actor."""
+    import torch
+    n, pitch = rows.shape
+    out = torch.empty(int(num_actors), int(width), device=rows.device, dtype=torch.float32)
+    if n == 0 or num_actors == 0 or width == 0:
+        return out.zero_()
+    ws = torch.empty(track_det_workspace_size(num_actors, 0, n, width), device=rows.device, dtype=torch.uint8)
+    check(load().emd_actor_row_sum_det(n, int(width), rows.data_ptr() + 4 * int(col0), pitch, ptr(ids), int(num_actors), ptr(segment_start), out.data_ptr(),
+                                       int(width), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_actor_row_sum_det")
+    return out
 
 
 def mlp_det_layout(kind, args, grads=None):

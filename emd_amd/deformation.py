@@ -525,7 +525,7 @@ DeformNetwork = deform_network
 # ------------------------------------------------------------------------------------------------------------ OmniRe (a15)
 class _DeformInput(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means, point_ids, inst_size, inst_embed, t, num_freqs_x, num_freqs_t):
+    def forward(ctx, means, point_ids, inst_size, inst_embed, t, num_freqs_x, num_freqs_t, deterministic=False):
         if means.device.type != "cuda":
             raise L.EmdError("deform_input needs tensors on a ROCm device; there is no CPU path")
         lib = L.load()
@@ -540,7 +540,7 @@ class _DeformInput(torch.autograd.Function):
         a.means, a.point_ids, a.inst_size, a.inst_embed, a.t, a.out = (keep[0].data_ptr(), L.ptr(keep[1]), L.ptr(keep[2]), keep[3].data_ptr(),
                                                                        keep[4].data_ptr(), out.data_ptr())
         L.check(lib.emd_deform_input_forward(C.byref(a), _stream()), "emd_deform_input_forward")
-        ctx.ids, ctx.embed_shape, ctx.col0 = keep[1], tuple(inst_embed.shape), width - E
+        ctx.ids, ctx.embed_shape, ctx.col0, ctx.deterministic = keep[1], tuple(inst_embed.shape), width - E, bool(deterministic)
         return out
 
     @staticmethod
@@ -550,16 +550,21 @@ class _DeformInput(torch.autograd.Function):
             A, E = ctx.embed_shape
             if ctx.ids is None:
                 g_embed = g[:, ctx.col0:].contiguous()
+            elif ctx.deterministic:
+                # per actor the pinned segmented sum of the rows in ascending point index, no atomics (emd_actor_row_sum_det)
+                g_embed = L.actor_row_sum_det(g.contiguous().float(), E, ctx.ids, A, col0=ctx.col0)
             else:
                 g = g.contiguous().float()
                 g_embed = torch.zeros(A, E, device=g.device, dtype=torch.float32)
                 L.check(L.load().emd_deform_input_backward(g.shape[0], E, g.shape[1], ctx.col0, ctx.ids.data_ptr(), g.data_ptr(),
                                                            g_embed.data_ptr(), _stream()), "emd_deform_input_backward")
-        return None, None, None, g_embed, None, None, None          # positions and time are detached in the reference
+        return None, None, None, g_embed, None, None, None, None    # positions and time are detached in the reference
 
 
 class ConditionalDeformNetwork(nn.Module):
-    """OmniRe/models/modules.py:411-457 (same parameters: `linear`, `gaussian_warp`, `gaussian_rotation`, `gaussian_scaling`)."""
+    """OmniRe/models/modules.py:411-457 (same parameters: `linear`, `gaussian_warp`, `gaussian_rotation`, `gaussian_scaling`).
+    The layers run on `tall_linear` (rocBLAS), which has no fixed-order form: `nonrigid_deformation(..., deterministic=True)` covers the gradient of
+    the actor embeddings behind the encoder input, not the gradients of these layers."""
 
     def __init__(self, D=8, W=256, input_ch=3, embed_dim=10, x_multires=10, t_multires=10, deform_quat=True, deform_scale=True):
         super().__init__()
@@ -596,9 +601,12 @@ class ConditionalDeformNetwork(nn.Module):
         return self.trunk(_DeformInput.apply(x, None, None, condition, t, self.x_multires, self.t_multires))
 
 
-def nonrigid_deformation(network, local_means, point_ids, instances_size, instances_embedding, t):
+def nonrigid_deformation(network, local_means, point_ids, instances_size, instances_embedding, t, deterministic=False):
     """DeformableNodes.get_deformation (OmniRe/models/nodes/deformable.py:35-47): gather of the actor's embedding and height,
     x = mean.data / height * 2, both frequency encodings and the concat in one launch, then the network's layers.
-    t: 1-element device tensor (normalized_timestamps[cur_frame])."""
+    t: 1-element device tensor (normalized_timestamps[cur_frame]).
+    deterministic: dL/d instances_embedding is summed per actor in ascending point index with a pinned association instead of float atomics (DESIGN.md
+    section 8.15); the network's own layers (rocBLAS) are not covered."""
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
-    return network.trunk(_DeformInput.apply(local_means, ids, instances_size, instances_embedding, t, network.x_multires, network.t_multires))
+    return network.trunk(_DeformInput.apply(local_means, ids, instances_size, instances_embedding, t, network.x_multires, network.t_multires,
+                                            bool(deterministic)))

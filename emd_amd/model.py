@@ -62,7 +62,9 @@ class StreetGaussians(torch.nn.Module):
     def actor_pose(self, frame, step=0):
         """[A,12] pose rows for one frame, with the learned track offsets (translation and rotation about z) when the model has
         the heads: rigid.py:519-532,547-566.  `frame` / `step` may be device tensors (int32 [1] / any integer [1]): the row and the
-        coarse-to-fine level are then selected on the device and the call can be replayed from a hipGraph."""
+        coarse-to-fine level are then selected on the device and the call can be replayed from a hipGraph.
+        `model.track_heads.deterministic = True` switches the chain's backward to the forms without float atomics (TrackOffsetHeads.deterministic;
+        DESIGN.md section 8.15): with the rasterizer's `deterministic=True` every gradient of a step is then a fixed function of its inputs."""
         from .motion import actor_pose_table
         if self.track_heads is not None:
             return self.track_heads.pose_table(self.instances_quats, self.instances_trans, self.instances_fv, frame, self._embeddings,

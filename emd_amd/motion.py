@@ -22,8 +22,28 @@ import torch.nn.functional as F
 from . import _lib as L
 
 
+# a list: every deterministic backward of the actor chain appends dict(form, ws, num_actors, width) -- the workspace tensor the call was given (slab and
+# dL/dh rows: _lib.track_det_layout(num_actors, width)) -- so that a test can read them back; None: nothing is kept
+DET_TRACE = None
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _alloc_det_ws(nbytes, dev):
+    """The workspace of one deterministic call of the actor chain: never cleared.  A function of its own so that a test can put guard bands around it."""
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
+
+def _alloc_det_grads(numel, dev):
+    """The gradients a deterministic backward of the actor chain writes in full (temporal tables, head tensors): ONE allocation, never cleared."""
+    return torch.empty(numel, device=dev)
+
+
+def _trace_det(form, ws, num_actors, width):
+    if DET_TRACE is not None:
+        DET_TRACE.append(dict(form=form, ws=ws, num_actors=num_actors, width=width))
 
 
 def _track_inputs(weight, emb, head_params):
@@ -90,11 +110,19 @@ class TrackOffsetHeads(torch.nn.Module):
     Delta t = W_c h_c + W_f h_f,   theta_{c,f} = w_{c,f} . h_{c,f},   Delta q = (cos th_c,0,0,sin th_c) (x) (cos th_f,0,0,sin th_f)
     with h = cat[TE_k(t) from the actor's temporal table, mean of the actor's Gaussian embeddings];
     k = 30 for the coarse head, int_lininterp(step, 30, 150, 25000) for the fine head.
+
+    `deterministic` (class attribute, constructor keyword, or set on an instance): every gradient of `forward` and `pose_table` is a fixed function
+    of the call's inputs -- the head gradients are stored per actor and added in ascending actor index, the temporal tables' in gather form, the
+    embedding mean of unsorted ids by a pinned segmented sum; no float atomics (csrc/track_det.hip).  Values agree with the
+    default mode to rounding (bit for bit in the forward when the ids are sorted by actor).
     """
+    deterministic = False
 
     def __init__(self, num_actors, temporal_embedding_dim=32, gaussian_embedding_dim=4, max_embeddings=150,
-                 min_embeddings=30, c2f_temporal_iter=25000):
+                 min_embeddings=30, c2f_temporal_iter=25000, deterministic=None):
         super().__init__()
+        if deterministic is not None:
+            self.deterministic = bool(deterministic)
         self.fdim, self.edim = temporal_embedding_dim, gaussian_embedding_dim
         self.max_embeddings, self.min_embeddings, self.c2f_temporal_iter = max_embeddings, min_embeddings, c2f_temporal_iter
         self.weight = torch.nn.Parameter(torch.randn(num_actors, max_embeddings, temporal_embedding_dim) * 0.01 / temporal_embedding_dim ** 0.5)
@@ -162,7 +190,7 @@ class TrackOffsetHeads(torch.nn.Module):
         t, k_f = self._time_and_k(frame, num_frames, step)
         return _TrackHeads.apply(self.weight, embeddings, self.track_trans_c.weight, self.track_trans_c.bias, self.track_trans_f.weight,
                                  self.track_trans_f.bias, self.track_rot_c.weight, self.track_rot_c.bias, self.track_rot_f.weight,
-                                 self.track_rot_f.bias, ids32, cnt, seg, t, self.min_embeddings, k_f)
+                                 self.track_rot_f.bias, ids32, cnt, seg, t, self.min_embeddings, k_f, bool(self.deterministic))
 
     def pose_table(self, instances_quats, instances_trans, instances_fv, frame, embeddings, point_ids, step):
         """The frame's [A,12] pose table WITH the learned offsets, the whole per-actor chain (embedding sums -> heads -> pose row) in
@@ -179,7 +207,7 @@ class TrackOffsetHeads(torch.nn.Module):
         return _TrackedPose.apply(self.weight, embeddings, self.track_trans_c.weight, self.track_trans_c.bias, self.track_trans_f.weight,
                                   self.track_trans_f.bias, self.track_rot_c.weight, self.track_rot_c.bias, self.track_rot_f.weight,
                                   self.track_rot_f.bias, instances_quats, instances_trans, instances_fv, ids32, cnt, seg, t,
-                                  self.min_embeddings, k_f, frame)
+                                  self.min_embeddings, k_f, frame, bool(self.deterministic))
 
 
 class _TrackHeads(torch.autograd.Function):
@@ -204,16 +232,23 @@ class _TrackHeads(torch.autograd.Function):
         return a
 
     @staticmethod
-    def forward(ctx, weight, emb, wtc, btc, wtf, btf, wrc, brc, wrf, brf, ids32, cnt, seg, t, k_c, k_f):
+    def forward(ctx, weight, emb, wtc, btc, wtf, btf, wrc, brc, wrf, brf, ids32, cnt, seg, t, k_c, k_f, deterministic=False):
         dev = weight.device
         weight_c, emb_c, heads = _track_inputs(weight, emb, (wtc, btc, wtf, btf, wrc, brc, wrf, brf))
         A, E = weight_c.shape[0], emb_c.shape[1]
         emb_sum = (torch.empty if seg is not None else torch.zeros)(A, max(E, 1), device=dev)
         trans, rot = torch.empty(A, 3, device=dev), torch.empty(A, 4, device=dev)
         a = _TrackHeads._args(weight_c, emb_c, heads, ids32, cnt, seg, t, k_c, k_f, emb_sum, trans, rot)
-        L.check(L.load().emd_track_heads_forward(C.byref(a), _stream()), "emd_track_heads_forward")
+        if deterministic:
+            # the embedding sums of unsorted ids by the pinned segmented sum (emd_actor_row_sum_det) instead of atomics
+            ws = None
+            if E > 0 and emb_c.shape[0] > 0 and (seg is None or E > 8):
+                ws = torch.empty(L.track_det_workspace_size(A, 0, emb_c.shape[0], E), device=dev, dtype=torch.uint8)
+            L.check(L.load().emd_track_heads_forward_det(C.byref(a), L.ptr(ws), 0 if ws is None else ws.numel(), _stream()), "emd_track_heads_forward_det")
+        else:
+            L.check(L.load().emd_track_heads_forward(C.byref(a), _stream()), "emd_track_heads_forward")
         ctx.save_for_backward(weight_c, emb_c, ids32, cnt, emb_sum, *heads)
-        ctx.scal, ctx.seg = (t, k_c, k_f), seg
+        ctx.scal, ctx.seg, ctx.deterministic = (t, k_c, k_f), seg, bool(deterministic)
         return trans, rot
 
     @staticmethod
@@ -224,9 +259,9 @@ class _TrackHeads(torch.autograd.Function):
         z = lambda t_: torch.empty_like(t_)
         g_trans = torch.zeros(A, 3, device=dev) if g_trans is None else g_trans.contiguous().float()
         g_rot = torch.zeros(A, 4, device=dev) if g_rot is None else g_rot.contiguous().float()
-        # everything the kernel accumulates into comes from ONE zero-filled allocation
+        # everything the kernel accumulates into comes from ONE zero-filled allocation (deterministic: every element is written, nothing is cleared)
         sizes = [weight.numel()] + [h.numel() for h in heads]
-        flat = torch.zeros(sum(sizes), device=dev)
+        flat = _alloc_det_grads(sum(sizes), dev) if ctx.deterministic else torch.zeros(sum(sizes), device=dev)
         parts = torch.split(flat, sizes)
         d_weight, d_heads = parts[0].view_as(weight), [p.view_as(h) for p, h in zip(parts[1:], heads)]
         d_emb, d_mean = z(emb), torch.empty(A, max(E, 1), device=dev)
@@ -235,15 +270,20 @@ class _TrackHeads(torch.autograd.Function):
         g.g_trans, g.g_rot, g.d_weight, g.d_embeddings, g.d_mean = g_trans.data_ptr(), g_rot.data_ptr(), d_weight.data_ptr(), d_emb.data_ptr(), d_mean.data_ptr()
         for h in range(4):
             g.d_head_w[h], g.d_head_b[h] = d_heads[2 * h].data_ptr(), d_heads[2 * h + 1].data_ptr()
-        L.check(L.load().emd_track_heads_backward(C.byref(a), C.byref(g), _stream()), "emd_track_heads_backward")
-        return (d_weight, d_emb, *d_heads, None, None, None, None, None, None)
+        if ctx.deterministic:
+            ws = _alloc_det_ws(L.track_det_workspace_size(A, weight.shape[2] + E), dev)
+            _trace_det("heads", ws, A, weight.shape[2] + E)
+            L.check(L.load().emd_track_heads_backward_det(C.byref(a), C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "emd_track_heads_backward_det")
+        else:
+            L.check(L.load().emd_track_heads_backward(C.byref(a), C.byref(g), _stream()), "emd_track_heads_backward")
+        return (d_weight, d_emb, *d_heads, None, None, None, None, None, None, None)
 
 
 class _TrackedPose(torch.autograd.Function):
     """embedding sums -> track heads -> pose row: one launch forward, one backward (csrc/embed.hip: k_tracked_pose)."""
 
     @staticmethod
-    def forward(ctx, weight, emb, wtc, btc, wtf, btf, wrc, brc, wrf, brf, q_all, t_all, fv, ids32, cnt, seg, t, k_c, k_f, frame):
+    def forward(ctx, weight, emb, wtc, btc, wtf, btf, wrc, brc, wrf, brf, q_all, t_all, fv, ids32, cnt, seg, t, k_c, k_f, frame, deterministic=False):
         dev = weight.device
         weight_c, emb_c, heads = _track_inputs(weight, emb, (wtc, btc, wtf, btf, wrc, brc, wrf, brf))
         q_c, t_c = q_all.detach().contiguous().float(), t_all.detach().contiguous().float()
@@ -255,12 +295,13 @@ class _TrackedPose(torch.autograd.Function):
         emb_sum = torch.empty(A, max(E, 1), device=dev)
         pose = torch.empty(A, L.ACTOR_STRIDE, device=dev, dtype=torch.float32)
         # the shared head gradients of the backward are accumulated into this buffer, which the forward launch clears (no fill launch)
-        head_acc = torch.empty(sum(h.numel() for h in heads), device=dev) if any(ctx.needs_input_grad[:10]) else None
+        # (deterministic: no accumulator -- the backward stores per actor and reduces: emd_tracked_pose_backward_det)
+        head_acc = torch.empty(sum(h.numel() for h in heads), device=dev) if any(ctx.needs_input_grad[:10]) and not deterministic else None
         p = _TrackedPose._args(weight_c, emb_c, heads, ids32, cnt, seg, t, k_c, k_f, emb_sum, q_c, t_c, valid, frame, pose, head_acc)
         L.check(L.load().emd_tracked_pose_forward(C.byref(p), _stream()), "emd_tracked_pose_forward")
         ctx.save_for_backward(weight_c, emb_c, ids32, cnt, seg, emb_sum, q_c, t_c, *heads)
         ctx.scal, ctx.valid, ctx.head_acc, ctx.acc_used = (t, k_c, k_f, frame), valid, head_acc, False
-        ctx.shapes = (q_all.shape, t_all.shape)
+        ctx.shapes, ctx.deterministic = (q_all.shape, t_all.shape), bool(deterministic)
         return pose
 
     @staticmethod
@@ -287,7 +328,10 @@ class _TrackedPose(torch.autograd.Function):
         # dense outputs are written in full by the kernel; the head gradients are added into the accumulator the forward launch cleared
         d_weight, d_emb, d_q, d_t = e(weight), e(emb), e(q_all), e(t_all)
         acc = ctx.head_acc
-        if acc is None:
+        if ctx.deterministic:        # every element is written by the call: nothing to clear, a second backward needs no special case
+            flat = _alloc_det_grads(weight.numel() + sum(h.numel() for h in heads), dev)
+            d_weight, acc = flat[:weight.numel()].view_as(weight), flat[weight.numel():]
+        elif acc is None:
             acc = torch.zeros(sum(h.numel() for h in heads), device=dev)
         elif ctx.acc_used:           # a second backward through the same forward (retain_graph): the kernel's clearing happened only once
             acc = torch.zeros_like(acc)
@@ -300,8 +344,13 @@ class _TrackedPose(torch.autograd.Function):
         g.d_q_all, g.d_t_all, g.d_weight, g.d_embeddings = d_q.data_ptr(), d_t.data_ptr(), d_weight.data_ptr(), d_emb.data_ptr()
         for h in range(4):
             g.d_head_w[h], g.d_head_b[h] = d_heads[2 * h].data_ptr(), d_heads[2 * h + 1].data_ptr()
-        L.check(L.load().emd_tracked_pose_backward(C.byref(p), C.byref(g), _stream()), "emd_tracked_pose_backward")
-        return (d_weight, d_emb, *d_heads, d_q.view(ctx.shapes[0]), d_t.view(ctx.shapes[1]), *([None] * 8))
+        if ctx.deterministic:
+            ws = _alloc_det_ws(L.track_det_workspace_size(A, width), dev)
+            _trace_det("pose", ws, A, width)
+            L.check(L.load().emd_tracked_pose_backward_det(C.byref(p), C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "emd_tracked_pose_backward_det")
+        else:
+            L.check(L.load().emd_tracked_pose_backward(C.byref(p), C.byref(g), _stream()), "emd_tracked_pose_backward")
+        return (d_weight, d_emb, *d_heads, d_q.view(ctx.shapes[0]), d_t.view(ctx.shapes[1]), *([None] * 9))
 
 
 def build_actor_pose(instances_quats, instances_trans, instances_fv, cur_frame, track_trans=None, track_rot=None,

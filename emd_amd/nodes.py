@@ -72,12 +72,13 @@ def deformable_gaussians(network, means, quats, opacity_logits, log_scales, feat
                          use_deformation=True, stop_optimizing_canonical_xyz=True, check_finite=True, deterministic=False):
     """DeformableNodes.get_gaussians: delta_xyz on the canonical means (detached when `stop_optimizing_canonical_xyz`), delta_quat on
     the normalised quaternions, delta_scale (when the network has that head) on the activated scales; then as rigid_gaussians
-    (`deterministic` included: it covers the motion transform, not the network)."""
+    (`deterministic` included: it covers the motion transform and, through `nonrigid_deformation(..., deterministic=True)`, the gradient of
+    `instances_embedding` behind the encoder input; the layers of ConditionalDeformNetwork run on rocBLAS and are not covered)."""
     from .deformation import nonrigid_deformation
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
     dx = dq = ds = None
     if use_deformation:
-        dx, dq, ds = nonrigid_deformation(network, means, ids, instances_size, instances_embedding, t)
+        dx, dq, ds = nonrigid_deformation(network, means, ids, instances_size, instances_embedding, t, deterministic=deterministic)
     base = means.detach() if (dx is not None and stop_optimizing_canonical_xyz) else means
     # the residuals enter the HIP transform as `residual_dx` / `residual_dq`, added before the rigid motion; the reference adds
     # delta_quat to get_quats = q / |q| (deformable.py:69), so the quaternions are normalised first when a residual is present

@@ -822,6 +822,49 @@ int emd_deform_input_forward(const EmdDeformInArgs* args, void* hip_stream);
 int emd_deform_input_backward(int num_points, int embed_dim, int ld, int col0, const int32_t* point_ids, const float* dL_din,
                               float* dL_dembed, void* hip_stream);
 
+/* ---- The actor chain and the encoder-input gradient without float atomics (csrc/track_det.hip).  Opt-in entry points of their
+ * own: a compatible extension (no struct changed, EMD_ABI_VERSION kept); the default entries and their kernels are untouched.  Nothing of what they
+ * compute depends on workgroup order, the stream, other work on the device, or eager execution against hipGraph replay.
+ *
+ * Workspace `ws` of every entry below: caller-owned, device, 256-byte aligned, never cleared; missing, misaligned or shorter than
+ * emd_track_det_workspace_size reports for the call is EMD_ERR_WORKSPACE, decided before anything is launched.  Layout for (num_actors A, head_width w,
+ * num_points n, row_width g), up(b) = b rounded up to 256, sort(m, g) as for emd_raster_det_workspace_size:
+ *     bytes = up(4 A pitch) + up(4 * 128 A) + sort(n, min(g, 32)) + up(64) + 256,   pitch = 8 w + 8 rounded up to 16 floats
+ *             the slab [A][pitch], the per-lane dL/dh rows [A][2][64], the sort by actor with the chunk sums, the count words
+ * -- the first two terms only when w > 0 (the chain's backward), the sort only when g > 0 and n > 0 (the row sum).  emd_track_det_workspace_size is
+ * host-only and returns 0 for sizes outside the limits (w <= 64, g <= 64, n <= 2^31 - 1 - 2048).  emd_track_det_workspace_offsets: out[0] byte offset of
+ * the slab, [1] its pitch IN FLOATS, [2] byte offset of the dL/dh rows, [3] the raw keys (actor of every point, 0xFFFFFFFF = none), [4] the sorted keys
+ * and [5] the sorted point indices (the ping-pong pair that holds the result for this A), [6] the count words (uint32 [0] = points the sort kept),
+ * out[7] = the total.
+ *
+ * emd_actor_row_sum_det: out[a * out_pitch + f], f < width, = the sum of rows[i * row_pitch + f] over the points i with ids[i] == a in ASCENDING i with
+ *   the association of emd_segmented_row_sum (chunks of EMD_SEG_CHUNK = 512, fp64 from 0.0, one rounding).  An actor without a point gets +0.0 (written
+ *   here: `out` need not be initialised); an id outside [0, num_actors) contributes nothing.  1 <= width <= 64 (columns in bands of at most 32 over one
+ *   sorted list), row_pitch, out_pitch >= width; EMD_ERR_INVALID otherwise.  segment_start ([num_actors + 1], start[0] = 0, start[A] = n; or NULL): the
+ *   ids are sorted by actor and the sort is skipped -- the association depends on run length and position alone, so the bits are the same.  n == 0 or
+ *   num_actors == 0 launches nothing and needs no workspace.  ws: (num_actors, 0, n, width).
+ * emd_track_heads_forward_det: emd_track_heads_forward with the embedding sums formed by emd_actor_row_sum_det when segment_start is NULL or
+ *   embed_dim > 8 (emb_sum need not be zero-filled; ws: (A, 0, num_points, embed_dim)); otherwise the default forward, which has no atomics, as it is
+ *   (ws may be NULL).
+ * emd_track_heads_backward_det / emd_tracked_pose_backward_det: emd_track_heads_backward / emd_tracked_pose_backward with every refusal of theirs;
+ *   ws: (A, dim + embed_dim, 0, 0).  Nothing arrives zero-filled and the forward clears nothing (EmdTrackedPoseArgs.head_acc = NULL there):
+ *   - head gradients: actor a STORES its share of the eight head tensors to slab[a] -- the tensors back to back as head_acc has them, w_tc b_tc w_tf
+ *     b_tf w_rc b_rc w_rf b_rf, 8 w + 8 floats, each product formed as the default forms it, +0.0 where the default skips the add of a zero gradient --
+ *     and one launch adds the slots per element in ascending actor index in fp64 from 0.0, rounds once and writes all 8 w + 8 destination elements;
+ *   - d_weight, in gather form: the at most eight touched rows of an actor's table are slots q = 4 level + 2 r + (0: ha, 1: hb); the lane of (q, c)
+ *     owns element (row[q], c) when no earlier slot names the same row and adds its contributions in the default's issue order -- column j ascending,
+ *     coarse before fine, r = 0, 1, then (ha, x0), (hb, x0), (ha, x1), (hb, x1) --, each product g * wx * wy * l formed left to right in fp32 without
+ *     contraction, in fp64 from 0.0 with one rounding; every other element of [A, rows, dim] is written +0.0;
+ *   - the per-lane dL/dh_c and dL/dh_f of every actor are left in the workspace ([A][2][64]);
+ *   - d_q_all / d_t_all / d_mean / d_embeddings are per actor or per point and keep the default's arithmetic. */
+size_t emd_track_det_workspace_size(int32_t num_actors, int32_t head_width, int64_t num_points, int32_t row_width);
+int emd_track_det_workspace_offsets(int32_t num_actors, int32_t head_width, int64_t num_points, int32_t row_width, size_t out[8]);
+int emd_actor_row_sum_det(int32_t n, int32_t width, const float* rows, int32_t row_pitch, const int32_t* ids, int32_t num_actors,
+                          const int32_t* segment_start, float* out, int32_t out_pitch, void* ws, size_t ws_bytes, void* hip_stream);
+int emd_track_heads_forward_det(const EmdTrackArgs* args, void* ws, size_t ws_bytes, void* hip_stream);
+int emd_track_heads_backward_det(const EmdTrackArgs* args, const EmdTrackGrads* grads, void* ws, size_t ws_bytes, void* hip_stream);
+int emd_tracked_pose_backward_det(const EmdTrackedPoseArgs* args, const EmdTrackedPoseGrads* grads, void* ws, size_t ws_bytes, void* hip_stream);
+
 /* ---- The width-64 MLPs of the EMD deformation network as fused fp32-MFMA kernels -------------------
  * Deformation.feature_out (defor_depth = 1) + the pos / scales / rotations / opacity / shs heads + dino_head of
  * S3Gaussian/scene/deformation.py:100-185,254-337: see the block comment of csrc/mlp.hip.  One trunk call and one branch call per
