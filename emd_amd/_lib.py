@@ -269,6 +269,12 @@ class EmdRadixSortArgs(C.Structure):
                 ("count_out", _f)]
 
 
+class EmdBinningArgs(C.Structure):
+    _fields_ = [("num_gaussians", C.c_int32), ("image_height", C.c_int32), ("image_width", C.c_int32), ("flags", C.c_int32),
+                ("near_plane", C.c_float), ("bin_capacity", C.c_int64), ("depth_key", _f), ("binrec", _f), ("geom_ws", _f),
+                ("geom_bytes", C.c_size_t), ("bin_ws", _f), ("bin_bytes", C.c_size_t), ("status", _f), ("tile_order", _f)]
+
+
 class EmdSegSumArgs(C.Structure):
     _fields_ = [("keys", _f), ("slots", _f), ("n_dev", _f), ("n_cap", C.c_int64), ("rows", _f), ("row_pitch", C.c_int32), ("width", C.c_int32),
                 ("out", _f), ("out_pitch", C.c_int32), ("reserved", C.c_int32), ("partials", _f), ("partial_bytes", C.c_size_t)]
@@ -303,7 +309,7 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_abs_mean_backward", "emd_residual_l1_backward", "emd_tracked_pose_forward", "emd_tracked_pose_backward",
                     "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
                     "emd_knn_workspace", "emd_knn", "emd_knn_reverse_workspace", "emd_knn_reverse", "emd_embed_reg_forward", "emd_embed_reg_backward",
-                    "emd_radix_sort", "emd_camera_grad_workspace_size", "emd_raster_backward_camera",
+                    "emd_radix_sort", "emd_raster_binning", "emd_camera_grad_workspace_size", "emd_raster_backward_camera",
                     "emd_raster_det_workspace_size", "emd_raster_det_layout", "emd_segmented_row_sum_workspace", "emd_segmented_row_sum",
                     "emd_hexplane_det_workspace_size", "emd_hexplane_det_workspace_offsets",
                     "emd_sky_det_workspace_size", "emd_sky_det_workspace_offsets", "emd_sky_backward_det",
@@ -438,6 +444,7 @@ def load():
     lib.emd_embed_reg_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     lib.emd_embed_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]
     lib.emd_radix_sort.argtypes = [C.POINTER(EmdRadixSortArgs), C.c_void_p]
+    lib.emd_raster_binning.argtypes = [C.POINTER(EmdBinningArgs), C.c_void_p]
     lib.emd_camera_grad_workspace_size.argtypes = [C.c_int32, C.POINTER(C.c_size_t)]
     lib.emd_raster_backward_camera.argtypes = [C.POINTER(EmdBwdArgs), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_raster_det_workspace_size.argtypes = [C.POINTER(EmdDims), C.POINTER(C.c_size_t)]

@@ -497,6 +497,41 @@ int emd_raster_backward_camera(const EmdBwdArgs* a, float* dL_dcamera, void* wor
     return stage_sync(a->s.debug != 0, st, "camera_backward");
 }
 
+// The binning stage on caller-supplied projection outputs (tests/test_binning_gpu.py): the records go where K1 leaves them, the stage runs as in the forward.
+int emd_raster_binning(const EmdBinningArgs* a, void* hip_stream) {
+    if (!a) { emd_set_error("binning: null args"); return EMD_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int N = a->num_gaussians;
+    if (a->flags & ~EMD_FLAG_WIDE_DEPTH_SORT) { emd_set_error("binning: flags 0x%x: only EMD_FLAG_WIDE_DEPTH_SORT is read", a->flags); return EMD_ERR_INVALID; }
+    if (N < 0 || a->image_height <= 0 || a->image_width <= 0 || a->bin_capacity < 0) {
+        emd_set_error("binning: bad sizes N=%d H=%d W=%d cap=%lld", N, a->image_height, a->image_width, (long long)a->bin_capacity); return EMD_ERR_INVALID;
+    }
+    if ((int64_t)N >= (int64_t)1 << 28) { emd_set_error("binning: %d Gaussians; a list word holds a 28-bit Gaussian id beside the pair's quadrant mask", N); return EMD_ERR_INVALID; }
+    const int gx = (a->image_width - 1) / EMD_TILE_X + 1, gy = (a->image_height - 1) / EMD_TILE_Y + 1;
+    if (gx >= 1024 || gy >= 1024) { emd_set_error("binning: image too large: %d x %d tiles (max 1023)", gx, gy); return EMD_ERR_INVALID; }
+    if (!a->geom_ws || !a->bin_ws || !a->status || (N > 0 && (!a->depth_key || !a->binrec))) { emd_set_error("binning: null pointer"); return EMD_ERR_INVALID; }
+    GeomWs g; BinWs b;
+    emd_carve_geom(a->geom_ws, N, &g);
+    emd_carve_bin(a->bin_ws, a->bin_capacity, gx * gy, &b);
+    if (g.bytes > a->geom_bytes || b.bytes > a->bin_bytes) {
+        emd_set_error("binning: workspace too small (geom %zu/%zu bin %zu/%zu)", a->geom_bytes, g.bytes, a->bin_bytes, b.bytes);
+        return EMD_ERR_WORKSPACE;
+    }
+    if (N > 0) {
+        EMD_HIP_CHECK(hipMemcpyAsync(g.depth_key, a->depth_key, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+        EMD_HIP_CHECK(hipMemcpyAsync(g.binrec, a->binrec, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
+    }
+    { int zrc = emd_zero_async(a->status, sizeof(EmdStatus), st); if (zrc) return zrc; }      // (K1 clears it: the depth sort ORs into the overflow word)
+    EmdSettings s;
+    memset(&s, 0, sizeof(s));
+    s.image_height = a->image_height; s.image_width = a->image_width; s.near_plane = a->near_plane;
+    const int rc = emd_launch_binning(s, a->flags, N, g, b, a->bin_capacity, a->status, st);
+    emd_prof_end(PROF_RANGES, st);
+    if (rc) return rc;
+    if (a->tile_order) EMD_HIP_CHECK(hipMemcpyAsync(a->tile_order, b.tile_order, (size_t)gx * gy * 4, hipMemcpyDeviceToDevice, st));
+    return EMD_OK;
+}
+
 int emd_raster_export_binning(const EmdDims* dims, const void* geom_ws, size_t geom_bytes, const void* bin_ws, size_t bin_bytes,
                               int64_t num_rendered, uint64_t* keys, uint32_t* ids, uint32_t* ranges, uint32_t* quad_masks,
                               void* hip_stream) {

@@ -1193,6 +1193,39 @@ typedef struct EmdRadixSortArgs {
 } EmdRadixSortArgs;
 int emd_radix_sort(const EmdRadixSortArgs* args, void* hip_stream);
 
+/* ---- ABI 31 extension (a new entry point and a struct only, so the number stays): the binning stage on its own ------------------------------
+ * Everything between the projection kernel and the render kernels (csrc/binning.hip: depth order, duplication, partition by tile, tile ranges,
+ * dispatch order) on CALLER-SUPPLIED projection outputs, exported so that the stage can be tested directly, as emd_radix_sort is.  It runs the
+ * launcher emd_raster_forward runs, on the same workspaces:
+ *   - depth_key [N]: float bits of the view depth of every Gaussian, 0xFFFFFFFF = not visible.
+ *   - binrec [N][2]: the projection kernel's record (GeomWs::binrec of csrc/common.h): word 0 = x0 | y0 << 10 | width << 20 | skip-left << 30 |
+ *     skip-right << 31 of the tile rectangle, word 1 = height | skip-top << 10 | skip-bottom << 11 (bits from 12 up are not read by the stage).
+ *     A visible Gaussian emits width * height (tile, Gaussian) pairs, row-major; width or height 0: visible, no pairs.
+ *   - both arrays are copied into geom_ws (device to device, on the stream) and are not written; geom_ws / bin_ws are sized by
+ *     emd_raster_workspace_size for (num_gaussians, image_height, image_width, bin_capacity) and need no clearing; `status` is cleared here, as
+ *     the projection kernel would, and then holds D, the overflow bits, V (EmdStatus).
+ *   - tile_order [T] (T = tiles of the image), or NULL: receives BinWs::tile_order, the dispatch order of the render kernels: a permutation of
+ *     0 .. T-1 along which min(list length >> 4, 1023) does not increase; the identity when T > 65 536, num_gaussians == 0 or bin_capacity == 0.
+ *   - the sorted list, the ranges and the quadrant masks are then read with emd_raster_export_binning on the same workspaces.
+ * Checked on the host before anything is launched (EMD_ERR_INVALID): null args / depth_key / binrec (with num_gaussians > 0) / geom_ws / bin_ws /
+ * status, negative num_gaussians or bin_capacity, image sizes below 1, num_gaussians >= 2^28, 1024 or more tiles along an axis, a flag other than
+ * EMD_FLAG_WIDE_DEPTH_SORT; a workspace shorter than emd_raster_workspace_size reports is EMD_ERR_WORKSPACE.  No host read-back, no synchronisation.
+ * PRECONDITIONS on the device data, which the entry cannot check (the projection kernel guarantees them): every rectangle lies inside the tile
+ * grid (x0 + width <= tiles across, y0 + height <= tiles down), and the pairs of all visible Gaussians sum to less than 2^32. */
+typedef struct EmdBinningArgs {
+    int32_t num_gaussians, image_height, image_width;
+    int32_t flags;              /* EMD_FLAG_WIDE_DEPTH_SORT or 0 */
+    float   near_plane;         /* the narrow depth sort orders by key - bits(max(near_plane, 0)) */
+    int64_t bin_capacity;
+    const uint32_t* depth_key;
+    const uint32_t* binrec;
+    void* geom_ws; size_t geom_bytes;
+    void* bin_ws;  size_t bin_bytes;
+    EmdStatus* status;          /* device, 16 B */
+    uint32_t* tile_order;       /* [T] device out, or NULL */
+} EmdBinningArgs;
+int emd_raster_binning(const EmdBinningArgs* args, void* hip_stream);
+
 /* ---- ABI 30 extension: segmented row sum with a pinned association (csrc/segsum.h), the deterministic stand-in for per-destination float atomics ----
  * n elements (n = n_cap, or *n_dev <= n_cap when n_dev != NULL) with NON-DECREASING destination ids keys[e] and row indices slots[e].  For every
  * maximal run of equal keys: out[key * out_pitch + f] = sum over the run of rows[slots[e] * row_pitch + f], f < width.  Destinations without a
