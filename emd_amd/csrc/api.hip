@@ -399,7 +399,7 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
             if (rc) return rc;
         }
         if (!do_project && a->dL_dsh_color) {      // the SH factor right behind K7: a view-parallel step starts gathering it under K8
-            rc = emd_launch_sh_factor(N, a->radii, g, (const float*)a->bwd_ws, emd_bwd_stride(a->num_extra), a->dL_dsh_color, st);
+            rc = emd_launch_sh_factor(N, emd_bwd_visible_words(a->flags, a->radii, g), g, (const float*)a->bwd_ws, emd_bwd_stride(a->num_extra), a->dL_dsh_color, st);
             if (rc) return rc;
         }
         if ((rc = stage_sync(dbg, st, "render_backward"))) return rc;
@@ -557,6 +557,17 @@ int emd_raster_export_geometry(const EmdDims* dims, const void* geom_ws, size_t 
     if (g.bytes > geom_bytes) { emd_set_error("export_geometry: workspace too small"); return EMD_ERR_WORKSPACE; }
     return emd_launch_export_geometry(dims->num_gaussians, g, means2D, depths, conic_opacity, rgb, normal, tiles_touched,
                                       (hipStream_t)hip_stream);
+}
+
+int emd_raster_export_contributed(const EmdDims* dims, const void* geom_ws, size_t geom_bytes, uint32_t* contributed, void* hip_stream) {
+    if (!dims || !geom_ws || !contributed) { emd_set_error("export_contributed: null argument"); return EMD_ERR_INVALID; }
+    if (dims->num_gaussians < 0) { emd_set_error("export_contributed: bad dims N=%d", dims->num_gaussians); return EMD_ERR_INVALID; }
+    GeomWs g;
+    emd_carve_geom((void*)geom_ws, dims->num_gaussians, &g);
+    if (g.bytes > geom_bytes) { emd_set_error("export_contributed: workspace too small"); return EMD_ERR_WORKSPACE; }
+    if (dims->num_gaussians > 0)
+        EMD_HIP_CHECK(hipMemcpyAsync(contributed, g.contrib, (size_t)dims->num_gaussians * 4, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    return EMD_OK;
 }
 
 int emd_motion_forward(int32_t n, const float* means, const float* quats, const float* opacities,

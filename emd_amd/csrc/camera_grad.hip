@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(CAM_BLOCK) k_camera_backward(PreBwdArgs a, flo
     emd_settings_from_device(S, a.sdev, a.flags);
     __shared__ float s_part[CAM_WAVES][CAM_LIVE + 1];
     const int i = blockIdx.x * CAM_BLOCK + threadIdx.x;
-    const bool vis = i < a.N && a.radii[i] > 0;
+    const bool vis = i < a.N && emd_bwd_visible_words(a.flags, a.radii, a.g)[i] > 0;     // (K8's set: a Gaussian K7 never added to has an all-zero row)
     float acc[CAM_LIVE];
 #pragma unroll
     for (int k = 0; k < CAM_LIVE; k++) acc[k] = 0.f;

@@ -39,6 +39,8 @@ struct GeomWs {
     uint2* bin_s;            // [N] the same records in depth order
     uint32_t* ghist;         // radix histograms of the depth sort [bins][ceil(N / sort tile)]
     uint32_t* block_sums;    // [ceil(N/256)] pairs emitted per block of 256 depth-ordered Gaussians (added up by the last depth pass)
+    uint32_t* contrib;       // [N] by Gaussian id: 0 from K1; 1 once the render backward has staged a row with a non-zero float for the Gaussian, i.e. has
+                             //   added to its accumulator row.  What K8 takes for "visible" (not under EMD_FLAG_DETERMINISTIC, whose K7 does not write it)
     size_t bytes;
 };
 
@@ -110,6 +112,7 @@ static inline void emd_carve_geom(void* base, int N, GeomWs* w) {
     w->ghist = (uint32_t*)(p + off); off = emd_align_up(off + nsb * EMD_DEPTH_BINS_MAX * 4, 256);
     size_t nb = (n + EMD_BLOCK - 1) / EMD_BLOCK;
     w->block_sums = (uint32_t*)(p + off); off = emd_align_up(off + (nb + 8) * 4, 256);
+    w->contrib = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);
     w->bytes = off + 256;
 }
 
@@ -245,8 +248,15 @@ __device__ __forceinline__ void emd_settings_from_device(EmdSettings& S, const f
 #pragma unroll
     for (int k = 0; k < 3; k++) S.campos[k] = sdev[35 + k];
 }
+// The per-Gaussian words the projection backward and its siblings (k_sh_factor, the camera gradient) test with `> 0` for "this Gaussian has a gradient
+// row": the contributed words K7 set, or the radii under EMD_FLAG_DETERMINISTIC (the pose rows and their sort keys there are keyed by the radii, and the
+// deterministic K7 does not write the words).  Kernel-uniform, so the load behind it stays unconditional.
+__host__ __device__ inline const int32_t* emd_bwd_visible_words(int flags, const int32_t* radii, const GeomWs& g) {
+    return (flags & EMD_FLAG_DETERMINISTIC) ? radii : reinterpret_cast<const int32_t*>(g.contrib);
+}
 int emd_launch_preprocess_backward(const PreBwdArgs& a, hipStream_t st);     // preprocess.hip
 // the clamp-masked colour gradient of every Gaussian (the factor of its rank-one dL/dshs) from the render backward's accumulator rows
+// (`radii`: the words of emd_bwd_visible_words, declared above the projection backward's launcher -- a row is read where its word is > 0)
 int emd_launch_sh_factor(int N, const int32_t* radii, const GeomWs& g, const float* grad_rec, int bwd_stride, float* dL_dsh_color, hipStream_t st);
 // camera_grad.hip: dL/d(viewmatrix, projmatrix, campos) from the accumulator rows K7 left (read, not cleared), between the two halves of the
 // backward.  `partials`: emd_camera_grad_bytes(N) bytes, 16-byte aligned, one 36-float row per workgroup; every one of the 35 outputs is written.

@@ -274,6 +274,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_waves_per_eu(
         // y = its height | skip-top/bottom bits << 10 | upstream's tiles touched << 12
         a.g.binrec[i] = make_uint2(rect, rect_h | (touched << 12));
         a.g.depth_key[i] = dkey;                         // key of the depth sort (invisible: sorts last)
+        a.g.contrib[i] = 0u;                             // every forward hands the backward a clean array: K7 raises the words, K8 reads them
     }
     const bool vis = touched != 0u;
     float sh[48];
@@ -413,7 +414,11 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
     __shared__ uint16_t s_list[K8_BLOCK];
     const int inat = blockIdx.x * K8_BLOCK + threadIdx.x;
     const bool nat_in = inat < a.N;
-    const bool nat_vis = nat_in && a.radii[inat] > 0;
+    // "Visible" here is "the render backward added to this Gaussian's accumulator row" (GeomWs::contrib): more than half of the radii > 0 Gaussians of a
+    // street view sit behind the depth at which their tiles saturate, their rows are all zero and so is every output -- they take the zero-row duty
+    // instead of a compacted lane.  (EMD_FLAG_DETERMINISTIC keeps radii > 0: its pose rows are keyed by the radii.)  One pointer, chosen kernel-uniformly.
+    const int32_t* const vis_words = emd_bwd_visible_words(a.flags, a.radii, a.g);
+    const bool nat_vis = nat_in && vis_words[inat] > 0;
     uint32_t nv;
     {
         // inclusive scan of the visibility flags over the workgroup (any number of waves)

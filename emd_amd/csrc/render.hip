@@ -385,7 +385,8 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
                                                                 const float* __restrict__ dL_dnormal,
                                                                 float* __restrict__ grad_rec,
                                                                 float* __restrict__ zero_buf, int zero_n,
-                                                                unsigned long long* __restrict__ pair_stats) {
+                                                                unsigned long long* __restrict__ pair_stats,
+                                                                uint32_t* __restrict__ contrib) {
     // the tiny actor-pose gradient table K8 accumulates into is cleared here (K8 starts after this kernel): no memset launch
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < zero_n; i += EMD_WAVE) zero_buf[i] = 0.f;
@@ -568,11 +569,23 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
         // rows through LDS so that consecutive lanes add consecutive floats of one accumulator row
         q_id[lane] = DET ? pos : gid;
         float4* row = reinterpret_cast<float4*>(s_stage + lane * STRIDE);
-        row[0] = make_float4(-gx, -gy, a_dz, m0 * __builtin_amdgcn_rcpf(g0.w));
-        row[1] = make_float4(-0.5f * m2xx, -m2xy, -0.5f * m2yy, a_r);
-        row[2] = make_float4(a_g, a_b, ABS ? a_ax : 0.f, ABS ? a_ay : 0.f);
+        const float4 w0 = make_float4(-gx, -gy, a_dz, m0 * __builtin_amdgcn_rcpf(g0.w));
+        const float4 w1 = make_float4(-0.5f * m2xx, -m2xy, -0.5f * m2yy, a_r);
+        const float4 w2 = make_float4(a_g, a_b, ABS ? a_ax : 0.f, ABS ? a_ay : 0.f);
+        row[0] = w0; row[1] = w1; row[2] = w2;
+        // (the bit patterns OR-ed together and the sign shifted out: non-zero iff some float of the row compares != 0.f -- a NaN included, -0.f not)
+        auto or4 = [](const float4 v) { return __float_as_uint(v.x) | __float_as_uint(v.y) | __float_as_uint(v.z) | __float_as_uint(v.w); };
+        uint32_t row_bits = or4(w0) | or4(w1) | or4(w2);
 #pragma unroll
-        for (int k = 0; k < NX; k++) row[3 + k] = make_float4(xr_2[k].x + xr_2[k].y, xg_2[k].x + xg_2[k].y, xb_2[k].x + xb_2[k].y, 0.f);
+        for (int k = 0; k < NX; k++) {
+            const float4 wx = make_float4(xr_2[k].x + xr_2[k].y, xg_2[k].x + xg_2[k].y, xb_2[k].x + xb_2[k].y, 0.f);
+            row[3 + k] = wx;
+            row_bits |= or4(wx);
+        }
+        // GeomWs::contrib: the lane that owns an entry (in the half-wave form the lower half, after the fold) marks its Gaussian when the row it has just
+        // staged holds a non-zero float -- exactly when the flush below issues at least one atomic for that row.  A plain store of a constant (several waves
+        // may write it), once per batch; K8 compacts onto the marked Gaussians only.  (The deterministic K8 keeps the radii: nothing is marked there.)
+        if (!DET && lane < nb && (row_bits << 1) != 0u) contrib[gid] = 1u;
         __syncthreads();
         if (STATS) {
             bool nz = false;
@@ -673,8 +686,8 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
         const uint32_t *__restrict__ quad_need, const float4 *__restrict__ rec, const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib, \
         const float *__restrict__ out_color, const float *__restrict__ out_depth, const float *__restrict__ out_normal, const float *__restrict__ dL_dcolor, \
         const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, const float *__restrict__ dL_dnormal, float *__restrict__ grad_rec,  \
-        float *__restrict__ zero_buf, int zero_n, unsigned long long *__restrict__ pair_stats
-#define K7_ARGS d, tile_order, ranges, surv, quad_need, rec, final_T, n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, grad_rec, zero_buf, zero_n, pair_stats
+        float *__restrict__ zero_buf, int zero_n, unsigned long long *__restrict__ pair_stats, uint32_t *__restrict__ contrib
+#define K7_ARGS d, tile_order, ranges, surv, quad_need, rec, final_T, n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, grad_rec, zero_buf, zero_n, pair_stats, contrib
 template <bool NORMAL, bool ABS, int NX, bool STATS = false>
 __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(NX == 0 ? 4 : NX == 1 ? 3 : 2))) k_render_backward_q(K7_PARAMS) {
     render_backward_body<NORMAL, ABS, NX, STATS, false>(K7_ARGS);
@@ -760,7 +773,7 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
     const int nx = x ? x->num : 0;
     auto launch = [&](auto kernel, const float* dnormal, float* rows, unsigned long long* stats) {
         hipLaunchKernelGGL(kernel, dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv, b.quad_need, g.rec, im.final_T,
-                           im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dnormal, rows, zero_buf, zero_n, stats);
+                           im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dnormal, rows, zero_buf, zero_n, stats, g.contrib);
     };
     if (!det_part && nx == 0 && pair_stats)          // diagnostic: the plain kernel with the pair counters compiled in
         launch(k_render_backward_q<false, false, 0, true>, nullptr, grad_rec, pair_stats);

@@ -114,10 +114,14 @@ class RasterCall:
     first count[1] are valid), counts = int32[16]: [0] slots in use, [1] contributions kept, [2] actor-bound visible points; pose_rows [N, 12],
     pose_keys / pose_points = the sorted actor ids and point indices).
     `camera_grad` (after the backward of a call whose camera tensors require grad, else None): the 35 floats dL/d(viewmatrix[16],
-    projmatrix[16], campos[3]) of emd_raster_backward_camera; `camera_partials`: that call's per-workgroup rows (the same allocation)."""
+    projmatrix[16], campos[3]) of emd_raster_backward_camera; `camera_partials`: that call's per-workgroup rows (the same allocation).
+    `contributed` (after a backward with keep_render_grads, else None; None for a deterministic backward, which does not use the words): a bool [N]
+    copy of the contributed words of geom_ws -- True where the render backward added to the Gaussian's accumulator row, i.e. the Gaussians the
+    projection backward ran its chain rule for; every other Gaussian's gradients are exact zeros.  `export_contributed()` copies them at any time."""
     __slots__ = ("status", "num_rendered", "num_visible", "geom_ws", "bin_ws", "img_ws", "sizes", "capacity", "N", "H", "W",
                  "flags", "settings_dev", "absgrad", "sh_color_grad", "grad_slab", "on_backward", "render_grads", "pair_stats",
-                 "status_buffer", "slab_inputs", "on_sh_factor", "radii", "loop_stats", "camera_grad", "camera_partials", "det_state")
+                 "status_buffer", "slab_inputs", "on_sh_factor", "radii", "loop_stats", "camera_grad", "camera_partials", "det_state",
+                 "contributed")
 
     def __init__(self):
         for k in self.__slots__:
@@ -146,6 +150,14 @@ class RasterCall:
                                               keys.data_ptr(), ids.data_ptr(), ranges.data_ptr(), L.ptr(masks), _stream()),
                 "emd_raster_export_binning")
         return (keys[:D], ids[:D], ranges, masks[:D]) if with_masks else (keys[:D], ids[:D], ranges)
+
+    def export_contributed(self):
+        """bool [N]: the contributed words of this call's geom_ws as they are now (all False between the forward and its backward)."""
+        words = torch.empty(max(self.N, 1), device=self.status.device, dtype=torch.int32)
+        d = L.EmdDims(self.N, self.H, self.W, self.capacity, self.flags)
+        L.check(L.load().emd_raster_export_contributed(C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], words.data_ptr(), _stream()),
+                "emd_raster_export_contributed")
+        return words[:self.N] != 0
 
     def export_geometry(self):
         lib = L.load()
@@ -572,6 +584,7 @@ class _Rasterize(torch.autograd.Function):
         rec.absgrad, rec.sh_color_grad, rec.grad_slab = d_abs, d_shc, slab
         rec.render_grads = bwd_ws.view(max(N, 1), -1) if opts.keep_render_grads else None
         rec.camera_grad, rec.camera_partials = (d_cam, cam_rows) if want_cam else (None, None)
+        rec.contributed = rec.export_contributed() if (opts.keep_render_grads and not opts.deterministic) else None
         rec.det_state = _det_views(det_ws, N, ctx.capacity, nx, 0 if actor_pose is None else int(actor_pose.shape[0])) \
             if (det_ws is not None and opts.keep_render_grads) else None
         if d_abs is not None and ctx.means2D_ref is not None:

@@ -253,7 +253,7 @@ typedef struct EmdBwdArgs {
     const float* cov3D_precomp;
     EmdMotion motion;
     const int32_t* radii;
-    /* forward state */
+    /* forward state (of geom_ws the render backward writes the contributed words, see emd_raster_workspace_size; nothing else in it changes) */
     const void* geom_ws;  size_t geom_bytes;
     const void* bin_ws;   size_t bin_bytes;
     const void* img_ws;   size_t img_bytes;
@@ -340,7 +340,14 @@ int emd_select_step_inputs(const EmdStepSelect* args, void* hip_stream);
 int emd_abi_version(void);
 const char* emd_last_error(void);
 
-/* out[0..3] = bytes of geom_ws, bin_ws, img_ws, bwd_ws */
+/* out[0..3] = bytes of geom_ws, bin_ws, img_ws, bwd_ws.
+ * geom_ws ends with the "contributed" words, one uint32 per Gaussian (a compatible extension of ABI 31: the size reported here grew by 4 N bytes
+ * rounded up to 256, no struct changed, and every caller sizes geom_ws through this query).  The forward's projection kernel clears them, the
+ * render backward sets word i to 1 when it adds at least one non-zero float to accumulator row i, and the projection backward runs its chain
+ * rule for exactly those Gaussians: a Gaussian with radii > 0 that no pixel's gradient reached (occluded behind saturated tiles: more than half
+ * of the visible set of a street view) has an all-zero row and exact +0 gradients, written without the loads and the arithmetic.  Under
+ * EMD_FLAG_DETERMINISTIC the words are neither written by the backward nor read (radii > 0 decides, as before).  A two-call backward
+ * (EMD_FLAG_BWD_RENDER_ONLY, then EMD_FLAG_BWD_PROJECT_ONLY) passes the same geom_ws to both halves, as it always had to. */
 int emd_raster_workspace_size(const EmdDims* dims, size_t out[4]);
 
 int emd_raster_forward(EmdFwdArgs* args, void* hip_stream);
@@ -392,6 +399,10 @@ int emd_raster_export_geometry(const EmdDims* dims, const void* geom_ws, size_t 
                                float* means2D /*[N,2]*/, float* depths /*[N]*/, float* conic_opacity /*[N,4]*/,
                                float* rgb /*[N,3]*/, float* normal /*[N,3]*/, uint32_t* tiles_touched /*[N]*/,
                                void* hip_stream);
+
+/* Copy the contributed words of geom_ws (emd_raster_workspace_size) out for tests and counts: contributed[i] = 1 when the last render backward on
+ * this geom_ws added to the accumulator row of Gaussian i, 0 otherwise (all 0 between a forward and its backward).  dims: num_gaussians only. */
+int emd_raster_export_contributed(const EmdDims* dims, const void* geom_ws, size_t geom_bytes, uint32_t* contributed /*[N]*/, void* hip_stream);
 
 /* Stand-alone explicit-motion transform (same arithmetic as the fused path):
  *   world_mean = R(q_mean[a]) (mean + dx) + trans[a];  world_quat = q_rot[a] (x) normalize(quat + dq);
