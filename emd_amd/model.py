@@ -425,6 +425,14 @@ def _l1_call(n, a_ptr, b_ptr, loss, grad_ptr):
     L.check(L.load().emd_l1_loss_ws(n, a_ptr, b_ptr, loss.data_ptr(), grad_ptr, L.ptr(sc), C.c_void_p(st.cuda_stream)), "emd_l1_loss")
 
 
+def _aligned(t):
+    """`t` contiguous at a 16-byte aligned address, which the flat L1 entry points require (they load float4).  `.contiguous()` returns a
+    contiguous VIEW unchanged -- `batch[1]` of a stack starts wherever the slice falls -- so such a view is copied to a fresh buffer (a rare
+    path: whole tensors come from the allocator aligned)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _L1Loss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -432,7 +440,7 @@ class _L1Loss(torch.autograd.Function):
         from . import _lib as L
         if a.device.type != "cuda":
             raise L.EmdError("l1_loss needs tensors on a ROCm device; there is no CPU path")
-        a, b = a.contiguous(), b.contiguous()
+        a, b = _aligned(a), _aligned(b)
         loss = torch.empty(1, device=a.device, dtype=torch.float32)
         grad = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         _l1_call(a.numel(), a.data_ptr(), b.data_ptr(), loss, L.ptr(grad))
@@ -470,7 +478,7 @@ class _AbsMean(torch.autograd.Function):
         from . import _lib as L
         if x.device.type != "cuda":
             raise L.EmdError("abs_mean needs a tensor on a ROCm device; there is no CPU path")
-        xc = x.detach().contiguous().float()
+        xc = _aligned(x.detach().float())
         out = torch.empty(1, device=x.device, dtype=torch.float32)
         _l1_call(xc.numel(), xc.data_ptr(), None, out, None)
         ctx.save_for_backward(xc)
@@ -509,7 +517,7 @@ class _ResidualPairL1(torch.autograd.Function):
             raise L.EmdError("residual_pair_l1 needs tensors on a ROCm device; there is no CPU path")
         if xa.shape != xb.shape:
             raise ValueError("residual_pair_l1: the two residuals must have one shape")
-        a, b = xa.detach().contiguous().float(), xb.detach().contiguous().float()
+        a, b = _aligned(xa.detach().float()), _aligned(xb.detach().float())
         out = torch.empty(2, device=xa.device, dtype=torch.float32)
         _l1_call(a.numel(), a.data_ptr(), None, out, None)
         _l1_call(b.numel(), b.data_ptr(), None, out[1:], None)
@@ -522,8 +530,8 @@ class _ResidualPairL1(torch.autograd.Function):
         from . import _lib as L
         a, b = ctx.saved_tensors
         same = up_a is not None and up_b is not None and (up_a is up_b or (up_a.data_ptr() == up_b.data_ptr() and up_a.stride() == up_b.stride()))
-        ua = None if up_a is None else up_a.contiguous().float()
-        ub = ua if same else (None if up_b is None else up_b.contiguous().float())
+        ua = None if up_a is None else _aligned(up_a.float())
+        ub = ua if same else (None if up_b is None else _aligned(up_b.float()))
         ga = None if g_a is None else g_a.detach().reshape(1).float().contiguous()
         gb = None if g_b is None else g_b.detach().reshape(1).float().contiguous()
         grad_a, grad_b = torch.empty_like(a), torch.empty_like(b)

@@ -78,6 +78,7 @@ def test_adam_vs_torch_adam_many_tensors_and_layouts():
         _close(a, b.detach().cpu().numpy(), f"param {i}")
         if i < len(mine) - 1:
             _close(o1.state[a]["exp_avg_sq"], o2.state[b]["exp_avg_sq"].cpu().numpy(), f"v {i}")
+            _close(o1.state[a]["exp_avg"], o2.state[b]["exp_avg"].cpu().numpy(), f"m {i}")
     assert len(o1.state[mine[-1]]) == 0 and torch.equal(mine[-1].data, torch.ones(5, device=dev))        # no gradient: untouched
     assert mine[-3].is_contiguous(memory_format=torch.channels_last)
 
