@@ -150,6 +150,24 @@ class EmdTrainerLossArgs(C.Structure):
                 ("dL_dopacity", _f), ("dL_ddepth", _f)]
 
 
+VANILLA_REG_CHUNK = 1024     # EMD_VANILLA_REG_CHUNK: Gaussians per fp64 partial of the VanillaGaussians regularisers (csrc/vanilla.hip)
+
+
+class EmdVanillaArgs(C.Structure):
+    _fields_ = [("num_points", C.c_int32), ("sh_coeffs", C.c_int32), ("degree", C.c_int32), ("sh_mode", C.c_int32),
+                ("means", _f), ("log_scales", _f), ("quats", _f), ("opacity_logits", _f), ("features_dc", _f), ("features_rest", _f),
+                ("camera_center", _f), ("opacities", _f), ("scales", _f), ("quats_out", _f), ("rgbs", _f), ("clamp_mask", _f),
+                ("g_opacities", _f), ("g_scales", _f), ("g_quats", _f), ("g_rgbs", _f), ("dL_dopacity_logits", _f), ("dL_dlog_scales", _f),
+                ("dL_dquats", _f), ("dL_dfeatures_dc", _f), ("dL_dfeatures_rest", _f)]
+
+
+class EmdVanillaRegArgs(C.Structure):
+    _fields_ = [("num_points", C.c_int32), ("reserved", C.c_int32), ("log_scales", _f), ("opacity_logits", _f), ("radii", _f),
+                ("w_sharp", C.c_float), ("max_gauss_ratio", C.c_float), ("w_flatten", C.c_float), ("w_sparse", C.c_float),
+                ("w_max_s_square", C.c_float), ("reserved1", C.c_float), ("terms", _f), ("g", _f), ("dL_dlog_scales", _f),
+                ("dL_dopacity_logits", _f)]
+
+
 class EmdDeformInArgs(C.Structure):
     _fields_ = [("num_points", C.c_int32), ("num_freqs_x", C.c_int32), ("num_freqs_t", C.c_int32), ("embed_dim", C.c_int32),
                 ("ld", C.c_int32), ("reserved", C.c_int32), ("means", _f), ("point_ids", _f), ("inst_size", _f), ("inst_embed", _f),
@@ -320,7 +338,8 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_mlp_det_slab_bytes", "emd_mlp_branch_forward_det", "emd_mlp_branch_backward_det", "emd_mlp_trunk_backward_det", "emd_mlp_det_reduce",
                     "emd_temporal_embed_backward_det",
                     "emd_track_det_workspace_size", "emd_track_det_workspace_offsets", "emd_actor_row_sum_det", "emd_track_heads_forward_det",
-                    "emd_track_heads_backward_det", "emd_tracked_pose_backward_det")
+                    "emd_track_heads_backward_det", "emd_tracked_pose_backward_det",
+                    "emd_vanilla_forward", "emd_vanilla_backward", "emd_vanilla_reg_workspace_size", "emd_vanilla_reg_forward", "emd_vanilla_reg_backward")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
@@ -468,6 +487,12 @@ def load():
     lib.emd_trainer_loss_workspace_size.argtypes = [C.POINTER(EmdTrainerLossArgs)]
     lib.emd_trainer_loss_workspace_size.restype = C.c_size_t
     lib.emd_trainer_loss.argtypes = [C.POINTER(EmdTrainerLossArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_vanilla_forward.argtypes = [C.POINTER(EmdVanillaArgs), C.c_void_p]
+    lib.emd_vanilla_backward.argtypes = [C.POINTER(EmdVanillaArgs), C.c_void_p]
+    lib.emd_vanilla_reg_workspace_size.argtypes = [C.c_int32]
+    lib.emd_vanilla_reg_workspace_size.restype = C.c_size_t
+    lib.emd_vanilla_reg_forward.argtypes = [C.POINTER(EmdVanillaRegArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_vanilla_reg_backward.argtypes = [C.POINTER(EmdVanillaRegArgs), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     lib.emd_profile_stage_name.argtypes = [C.c_int]
     lib.emd_profile_stage_name.restype = C.c_char_p

@@ -17,7 +17,15 @@ at `EmdRefineArgs` in include/emd_raster.h -- the ones that are easy to get wron
 duplicate test runs AFTER that reduction (a Gaussian just above the size threshold is split AND duplicated), the cull sees the grown arrays with
 `max_2Dsize` 0 on the new rows, and the output order is originals, samples replica 0, replica 1, duplicates.  The split samples are a Philox
 draw keyed by (seed, event, source index, replica): every rank of a view-parallel job draws the same samples (`samples=` takes a recorded draw
-instead: tests).  There is no CPU path."""
+instead: tests).  There is no CPU path.
+
+The render path and the regularisers of the class (csrc/vanilla.hip):
+  `get_gaussians(cam)` (:378-414) is `nodes.vanilla_gaussians`: one launch each way for the activations and the SH colour
+  `compute_reg_loss()` is `gaussian_regulation`: sharp-shape, flatten, sparse and max-s-square in two launches forward, one backward.  The trainer
+  assigns `cur_radii` per class from `info["radii"]`; where the reference reads `(cur_radii > 0).sum()` on the host and drops `sparse_reg` when
+  nothing is visible, the key stays here with value 0 and a zero gradient, and there is no sync.
+Not covered: `create_from_pcd` from a point cloud (the caller supplies kNN scales: `create_from_tensors`), the state-dict loaders, ball
+Gaussians (`[N,1]` scales: NotImplementedError)."""
 import ctypes as C
 
 import torch
@@ -39,6 +47,59 @@ def _get(cfg, key, default=None):
     return getattr(cfg, key, default)
 
 
+class _GaussianReg(torch.autograd.Function):
+    """One autograd node: `emd_vanilla_reg_forward` (two launches) and `emd_vanilla_reg_backward` (one)."""
+
+    @staticmethod
+    def forward(ctx, log_scales, opacity_logits, radii, weights):
+        lib, dev, n = L.load(), log_scales.device, log_scales.shape[0]
+        a = L.EmdVanillaRegArgs()
+        a.num_points = n
+        a.log_scales, a.opacity_logits, a.radii = log_scales.data_ptr(), L.ptr(opacity_logits), L.ptr(radii)
+        a.w_sharp, a.max_gauss_ratio, a.w_flatten, a.w_sparse, a.w_max_s_square = weights
+        terms = torch.empty(4, device=dev, dtype=torch.float32)
+        ws = torch.empty(max(int(lib.emd_vanilla_reg_workspace_size(n)), 8), device=dev, dtype=torch.uint8)
+        a.terms = terms.data_ptr()
+        L.check(lib.emd_vanilla_reg_forward(C.byref(a), ws.data_ptr(), ws.numel(), _stream()), "emd_vanilla_reg_forward")
+        ctx.save_for_backward(log_scales, opacity_logits, radii, ws)
+        ctx.weights = weights
+        return terms
+
+    @staticmethod
+    def backward(ctx, g):
+        log_scales, opacity_logits, radii, ws = ctx.saved_tensors
+        a = L.EmdVanillaRegArgs()
+        a.num_points = log_scales.shape[0]
+        a.log_scales, a.opacity_logits, a.radii = log_scales.data_ptr(), L.ptr(opacity_logits), L.ptr(radii)
+        a.w_sharp, a.max_gauss_ratio, a.w_flatten, a.w_sparse, a.w_max_s_square = ctx.weights
+        g = g.contiguous().float()
+        d_ls = torch.empty_like(log_scales)
+        sparse = ctx.weights[3] != 0.0 and opacity_logits is not None and radii is not None
+        d_lo = torch.empty_like(opacity_logits) if (sparse and ctx.needs_input_grad[1]) else None
+        a.g, a.dL_dlog_scales, a.dL_dopacity_logits = g.data_ptr(), d_ls.data_ptr(), L.ptr(d_lo)
+        L.check(L.load().emd_vanilla_reg_backward(C.byref(a), ws.data_ptr(), ws.numel(), _stream()), "emd_vanilla_reg_backward")
+        return d_ls, d_lo, None, None
+
+
+def gaussian_regulation(log_scales, opacity_logits=None, radii=None, *, w_sharp=0., max_gauss_ratio=10., w_flatten=0., w_sparse=0., w_max_s_square=0.):
+    """The regularisers of VanillaGaussians.compute_reg_loss over `log_scales` [N,3], `opacity_logits` [N] or [N,1] and the rasterizer's `radii` [N]
+    (> 0: visible) -> terms [4] = sharp_shape, flatten, sparse, max_s_square, each weighted, a differentiable output of one node (the formulas:
+    EmdVanillaRegArgs, include/emd_raster.h).  A term whose weight is 0 is skipped (value 0, no gradient), the sparse term also without
+    `opacity_logits` or `radii`; `opacity_logits` receives no gradient when there is no sparse term.  The weights are Python numbers.
+    Bit-reproducible, forward and backward; no host synchronisation."""
+    if log_scales.device.type != "cuda":
+        raise L.EmdError("gaussian_regulation needs tensors on a ROCm device; there is no CPU path")
+    if log_scales.dim() != 2 or log_scales.shape[1] != 3:
+        raise NotImplementedError("ball gaussians ([N,1] scales) are not served")
+    lo = None if opacity_logits is None else opacity_logits.contiguous().float()
+    r = None if radii is None else radii.detach().reshape(-1).to(torch.int32).contiguous()
+    n = log_scales.shape[0]
+    if (lo is not None and lo.numel() != n) or (r is not None and r.numel() != n):
+        raise ValueError("opacity_logits / radii do not have one entry per Gaussian")
+    weights = (float(w_sharp), float(max_gauss_ratio), float(w_flatten), float(w_sparse), float(w_max_s_square))
+    return _GaussianReg.apply(log_scales.contiguous().float(), lo, r, weights)
+
+
 class VanillaGaussians(torch.nn.Module):
     def __init__(self, class_name, ctrl, reg=None, networks=None, scene_scale=30.0, scene_origin=None, num_train_images=300, device="cuda",
                  refine_seed=0, **kwargs):
@@ -53,6 +114,8 @@ class VanillaGaussians(torch.nn.Module):
         self.in_test_set = False
         self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
         self.filter_mask = None
+        self.cur_radii = None                # this class's rows of info["radii"], assigned by the trainer: the visible set of the sparse regulariser
+        self.ball_gaussians = bool(_get(ctrl, "ball_gaussians", False))
         self.refine_seed, self.refine_events = int(refine_seed), 0
         z = lambda *s: torch.zeros(*s, device=self.device)
         self._means, self._scales, self._quats, self._opacities = z(1, 3), z(1, 3), z(1, 4), z(1, 1)
@@ -102,6 +165,50 @@ class VanillaGaussians(torch.nn.Module):
                 p + "scaling": [self._scales], p + "rotation": [self._quats]}
 
     get_param_groups = get_gaussian_param_groups
+
+    # ---- the render path and the regularisers (csrc/vanilla.hip) ----------------------------------------------------------------------------
+    def get_gaussians(self, cam, check_finite=None):
+        """vanilla.py:378-414: the dictionary `collect_gaussians` concatenates over classes.  `cam.camtoworlds` [..., 4, 4] stays on the device.
+        check_finite (default: ctrl key `check_finite`, else True) is the finite check of the node functions, one host sync; with it off the call
+        makes no host synchronisation and can be captured into a graph."""
+        from .nodes import vanilla_gaussians
+        if self.ball_gaussians or self._scales.shape[-1] != 3:
+            raise NotImplementedError("ball gaussians ([N,1] scales) are not served")
+        self.filter_mask = torch.ones(self.num_points, dtype=torch.bool, device=self._means.device)
+        return vanilla_gaussians(self._means, self._quats, self._opacities, self._scales, self._features_dc, self._features_rest,
+                                 cam.camtoworlds[..., :3, 3], sh_degree=self.sh_degree, step=self.step,
+                                 sh_degree_interval=_get(self.ctrl_cfg, "sh_degree_interval", 1000),
+                                 check_finite=bool(_get(self.ctrl_cfg, "check_finite", True)) if check_finite is None else check_finite)
+
+    def compute_reg_loss(self):
+        """The reference's dict: `sharp_shape_reg` (when reg_cfg names it and step % step_interval == 0), `flatten`, `sparse_reg` (when reg_cfg names
+        it and `cur_radii` is set), `max_s_square` (reg_cfg key `max_s_square_reg`).  Every value is an element of ONE node's output, so the
+        trainer's sum over the dict back-propagates through that node once.  Nothing visible: `sparse_reg` stays, with value 0 (no host read)."""
+        cfg = self.reg_cfg
+        if not cfg:
+            return {}
+        if self.ball_gaussians or self._scales.shape[-1] != 3:
+            raise NotImplementedError("ball gaussians ([N,1] scales) are not served")
+        keys, w = {}, dict(w_sharp=0., max_gauss_ratio=10., w_flatten=0., w_sparse=0., w_max_s_square=0.)
+        sharp = _get(cfg, "sharp_shape_reg")
+        if sharp is not None and self.step % int(_get(sharp, "step_interval", 1)) == 0:
+            w["w_sharp"], w["max_gauss_ratio"], keys["sharp_shape_reg"] = float(_get(sharp, "w")), float(_get(sharp, "max_gauss_ratio", 10.)), 0
+        flatten = _get(cfg, "flatten")
+        if flatten is not None:
+            w["w_flatten"], keys["flatten"] = float(_get(flatten, "w")), 1
+        sparse = _get(cfg, "sparse_reg")
+        if sparse and self.cur_radii is not None:
+            w["w_sparse"], keys["sparse_reg"] = float(_get(sparse, "w")), 2
+        msq = _get(cfg, "max_s_square_reg")
+        if msq is None:
+            msq = _get(cfg, "max_s_square")
+        if msq is not None:
+            w["w_max_s_square"], keys["max_s_square"] = float(_get(msq, "w")), 3
+        if not keys:
+            return {}
+        terms = gaussian_regulation(self._scales, self._opacities if "sparse_reg" in keys else None,
+                                    self.cur_radii if "sparse_reg" in keys else None, **w)
+        return {k: terms[i] for k, i in keys.items()}
 
     # ---- a17: the running statistics of the refinement --------------------------------------------------------------------------------------
     def after_train(self, radii, xys_grad, last_size):

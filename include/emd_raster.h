@@ -37,6 +37,8 @@
  *   emd_plane_reg_forward / backward    <- compute_regulation            S3Gaussian/scene/gaussian_model.py:745-784
  *   emd_affine_forward / backward       <- the affine colour correction  OmniRe/models/trainers/base.py:251-258
  *   emd_trainer_loss                    <- compute_losses                OmniRe/models/trainers/base.py:518-620, models/losses.py
+ *   emd_vanilla_forward / backward      <- VanillaGaussians.get_gaussians   OmniRe/models/gaussians/vanilla.py:378-414
+ *   emd_vanilla_reg_forward / backward  <- VanillaGaussians.compute_reg_loss (the same file)
  *   emd_sh_grad_from_factors            (multi-GPU: rebuilds the SH gradient from all-gathered rank-one factors; no reference counterpart)
  *   emd_compact_rows / emd_scatter_rows (multi-GPU: visibility-compacted gradient rows for 2 / 4 ranks; no reference counterpart)
  *
@@ -1442,6 +1444,93 @@ typedef struct EmdTrainerLossArgs {
 } EmdTrainerLossArgs;
 size_t emd_trainer_loss_workspace_size(const EmdTrainerLossArgs* args);
 int emd_trainer_loss(const EmdTrainerLossArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- ABI 31 extension (new entry points and structs only, so the number stays): VanillaGaussians (csrc/vanilla.hip) ----
+ * The per-class dictionary of get_gaussians (OmniRe/models/gaussians/vanilla.py:378-414) in one launch each way.  Everything is fp32, contiguous and
+ * 16-byte aligned (camera_center: 4-byte); N = num_points, M = sh_coeffs (1 .. 16), n = degree (0 .. 3, (n + 1)^2 <= M), K = (n + 1)^2.
+ *     opacities [N,1] = sigmoid(a)          scales [N,3] = exp(l)          quats_out [N,4] = q / max(|q|, 1e-12)
+ *     sh mode (sh_mode = 1, the class's sh_degree > 0):
+ *         d = mean - c;  d^ = d / |d|;  pre = sum_{k < K} basis_k(n, d^) coeffs_k,  coeffs = [features_dc, features_rest]
+ *         rgbs = clamp(pre + 0.5, 0, 1)        no gradient reaches the means or the camera (the directions are detached)
+ *     dc mode (sh_mode = 0, sh_degree == 0):  rgbs = sigmoid(features_dc);  features_rest and camera_center are not read
+ * The means themselves are the dictionary's `_means` (no copy).  The arithmetic is that of emd_activations_forward and of emd_sh_forward on
+ * dirs = means - camera_center, operation for operation: the outputs carry the same bits.  Of features_rest [N,M-1,3] only the K - 1 rows the
+ * degree uses are loaded (none at n = 0; NULL is allowed when M = 1); camera_center [3] is read on the DEVICE.  clamp_mask [N] bytes (or NULL in a
+ * forward that no backward follows): bit c set where 0 <= pre_c + 0.5 <= 1, torch's closed-interval rule for the gradient of clamp; the backward
+ * reads it instead of evaluating the colour again.
+ * Backward, for the upstream g_opacities [N], g_scales [N,3], g_quats [N,4], g_rgbs [N,3], any of which may be NULL and then counts as 0
+ * (g_opacities, g_scales and g_rgbs need 4-byte alignment only: autograd hands them over as views at any row offset; g_quats 16-byte):
+ *     dL/da = g o (1 - o)        dL/dl_k = g_k s_k        dL/dq = (g - q^ (q^ . g)) / max(|q|, 1e-12)
+ *     dL/dcoeffs_k = basis_k g~ for k < K and +0 for K <= k < M, g~ = g_rgbs where the mask bit is set and 0 elsewhere
+ *     dc mode: dL/dfeatures_dc = g c (1 - c), dL/dfeatures_rest = +0
+ * Row 0 of dL/dcoeffs is dL_dfeatures_dc [N,3], rows 1.. are dL_dfeatures_rest [N,M-1,3]: no concatenated buffer.  Every element of every non-NULL
+ * gradient tensor is WRITTEN exactly once (no zero fill by the caller); a NULL gradient tensor is not computed.  No atomics, no second mode, no host
+ * synchronisation: all outputs are bit-identical from run to run, across streams and under hipGraph replay.  Every argument is checked before the
+ * launch: a NULL required pointer, num_points < 0 or above INT32_MAX - 256 (the kernels index Gaussians as int), a degree outside 0 .. 3,
+ * (n + 1)^2 > M, M outside 1 .. 16 or a misaligned tensor is EMD_ERR_INVALID.  num_points == 0 launches nothing. */
+typedef struct EmdVanillaArgs {
+    int32_t num_points, sh_coeffs;               /* N, M */
+    int32_t degree, sh_mode;                     /* n; 1 = sh mode, 0 = dc mode */
+    const float* means;                          /* [N,3] */
+    const float* log_scales;                     /* [N,3] */
+    const float* quats;                          /* [N,4] */
+    const float* opacity_logits;                 /* [N] */
+    const float* features_dc;                    /* [N,3] */
+    const float* features_rest;                  /* [N,M-1,3], or NULL when M = 1 */
+    const float* camera_center;                  /* [3], device */
+    float* opacities;                            /* forward: [N] */
+    float* scales;                               /* forward: [N,3] */
+    float* quats_out;                            /* forward: [N,4] */
+    float* rgbs;                                 /* forward: [N,3] */
+    uint8_t* clamp_mask;                         /* [N]: written by the forward, read by the backward (sh mode) */
+    const float* g_opacities;                    /* backward: upstream gradients, each or NULL */
+    const float* g_scales;
+    const float* g_quats;
+    const float* g_rgbs;
+    float* dL_dopacity_logits;                   /* backward: [N], each or NULL */
+    float* dL_dlog_scales;                       /* [N,3] */
+    float* dL_dquats;                            /* [N,4] */
+    float* dL_dfeatures_dc;                      /* [N,3] */
+    float* dL_dfeatures_rest;                    /* [N,M-1,3] */
+} EmdVanillaArgs;
+int emd_vanilla_forward(const EmdVanillaArgs* args, void* hip_stream);
+int emd_vanilla_backward(const EmdVanillaArgs* args, void* hip_stream);
+
+/* The regularisers of compute_reg_loss (the same file).  With s = exp(l), smax / smin over the three columns, V = {i : radii[i] > 0} and
+ * R = max_gauss_ratio, terms [4] = sharp_shape, flatten, sparse, max_s_square (each weighted):
+ *     sharp_shape   w_sharp * mean_N (max(smax / smin, R) - R)
+ *                   gradient only where smax / smin > R: +ratio / N to l of the largest column, -ratio / N to the smallest; equal largest
+ *                   (smallest) columns share it evenly (torch.amax / amin)
+ *     flatten       w_flatten * mean_N |clamp(smin, 0, 30)|
+ *                   smin / N to l of the smallest column where smin < 30; among equal columns the LOWEST index takes all (torch.min with indices)
+ *     max_s_square  w_max_s_square * mean_N smax^2
+ *                   2 smax^2 / N to l of the largest column; among equal columns the lowest index takes all
+ *     sparse        w_sparse * mean_V -(o~ ln o~ + (1 - o~) ln(1 - o~)),  o~ = clamp(sigmoid(a), 1e-6, 1 - 1e-6)
+ *                   d/da = -a o (1 - o) / |V| inside the clip (ln((1 - o~) / o~) = -a there), 0 outside, 0 off V; |V| = 0: the term is 0 with a
+ *                   zero gradient (the reference drops its key after a host read of |V|).  1 - o is formed as sigmoid(-a), without cancellation.
+ * A term whose weight is 0 is SKIPPED: its value is 0 and it adds nothing to a gradient; so is the sparse term when opacity_logits or radii is NULL.
+ * Forward: one workgroup per EMD_VANILLA_REG_CHUNK Gaussians writes four fp64 sums and the chunk's visible count; one workgroup then adds the chunks
+ * in a fixed order, writes terms and keeps 1 / N and 1 / max(|V|, 1) at the head of the workspace.  Backward (one launch, the forward's workspace,
+ * g [4] = the upstream scalar of each term on the device): every element of dL_dlog_scales [N,3] and, when not NULL, of dL_dopacity_logits [N] is
+ * WRITTEN exactly once.  `workspace`: emd_vanilla_reg_workspace_size(N) bytes (a function of N alone; 0 for N < 1 or above INT32_MAX - 256), 8-byte aligned, never cleared.
+ * 4-byte alignment suffices for the tensors.  No float atomics, no host synchronisation: values and gradients are fixed functions of the inputs.
+ * num_points < 1 (a mean over nothing) or above INT32_MAX - 256, a NULL log_scales / terms / g / dL_dlog_scales or max_gauss_ratio <= 0 is EMD_ERR_INVALID. */
+#define EMD_VANILLA_REG_CHUNK 1024         /* Gaussians whose sums one workgroup adds into one fp64 partial per term */
+typedef struct EmdVanillaRegArgs {
+    int32_t num_points, reserved;
+    const float* log_scales;                     /* [N,3] */
+    const float* opacity_logits;                 /* [N] or NULL */
+    const int32_t* radii;                        /* [N] or NULL */
+    float w_sharp, max_gauss_ratio, w_flatten, w_sparse;
+    float w_max_s_square, reserved1;
+    float* terms;                                /* forward: [4] */
+    const float* g;                              /* backward: [4] */
+    float* dL_dlog_scales;                       /* backward: [N,3] */
+    float* dL_dopacity_logits;                   /* backward: [N] or NULL */
+} EmdVanillaRegArgs;
+size_t emd_vanilla_reg_workspace_size(int32_t num_points);
+int emd_vanilla_reg_forward(const EmdVanillaRegArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
+int emd_vanilla_reg_backward(const EmdVanillaRegArgs* args, const void* workspace, size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }
