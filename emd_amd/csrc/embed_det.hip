@@ -1,6 +1,9 @@
 // embed_det.hip -- emd_temporal_embed_backward_det: the backward of the temporal embedding row (embed.hip, k_temporal_embed<true>) without atomics
 // (DESIGN.md section 8.14).  A unit of its own: embed.hip's kernels are pinned instruction for instruction (profiles/mlp_det_isa.txt), and a further
-// kernel inside that unit changed the code of its neighbours.
+// kernel inside that unit changed the code of its neighbours.  What the units share is shared as text: the sampling set-up is temporal_sample.h, the
+// gather-form accumulation te_gather_body.inc (also track_det.hip's).  One pair stays written twice, the dL/dt column walk below and in
+// k_temporal_embed<true>: that kernel's set-up is written out in place because it came out with other registers when taken from the helpers, so
+// a text both could include would change its instructions (profiles/shared_source_isa.txt).
 #include "common.h"
 #include "temporal_sample.h"
 
@@ -9,8 +12,8 @@ namespace {
 // The backward of k_temporal_embed without atomics, in gather form.  k_temporal_embed<true> adds onto addresses that collide
 // between lanes (lane j's x1 is lane j + 1's x0; ha and hb of the two resized rows can coincide), and every table adds onto one g_t.  Here the at most
 // four touched table rows are slots q = 2 r + (0: ha, 1: hb); the lane of (q, column c) owns element (row[q], c) when no earlier slot names the same
-// row, and adds ITS contributions in the default kernel's issue order -- j ascending, r = 0, 1, then (ha, x0), (hb, x0), (ha, x1), (hb, x1) --, each
-// product formed as te_scatter forms it, in double precision from 0.0, rounded once and WRITTEN (rows no sample touches keep the caller's zeros).
+// row, and adds ITS contributions in the default kernel's issue order -- j ascending, then te_gather_body.inc's --, in double precision
+// from 0.0, rounded once and WRITTEN (rows no sample touches keep the caller's zeros).
 // dL/dt: wave 0 walks the columns as the default kernel does, the fixed xor tree follows; one table adds onto g_t itself, several leave one partial
 // each in `dt_part` for k_temporal_dt_sum.
 #define TE_DET_THREADS 256
@@ -35,21 +38,10 @@ __global__ void __launch_bounds__(TE_DET_THREADS) k_temporal_embed_bwd_det(const
             double acc = 0.0;
             for (int j = 0; j < dim; j++) {
                 const TeCol col = te_col(j, dim);
-                if (col.x0 != c && !(col.inx1 && col.x1 == c)) continue;
-                const float g = g_out[j];
-#pragma unroll
-                for (int r = 0; r < 2; r++) {
-                    if (r == 1 && !s.in1) continue;
-                    const float wy = r ? s.wy1 : s.wy0;
-                    if (col.x0 == c) {
-                        if (s.ha[r] == R) acc += (double)(g * col.wx0 * wy * s.la[r]);
-                        if (s.hb[r] == R) acc += (double)(g * col.wx0 * wy * s.lb[r]);
-                    }
-                    if (col.inx1 && col.x1 == c) {
-                        if (s.ha[r] == R) acc += (double)(g * col.wx1 * wy * s.la[r]);
-                        if (s.hb[r] == R) acc += (double)(g * col.wx1 * wy * s.lb[r]);
-                    }
-                }
+                const bool m0 = col.x0 == c, m1 = col.inx1 && col.x1 == c;
+                if (!m0 && !m1) continue;
+                const float g = g_out[j], wx0 = col.wx0, wx1 = col.wx1;
+#include "te_gather_body.inc"
             }
             G[(size_t)R * dim + c] = (float)acc;
         }

@@ -14,6 +14,7 @@
 // No atomics anywhere: every output is a fixed function of the inputs.
 #include "common.h"
 #include "device_utils.h"
+#include "fixed_sum.h"
 
 namespace {
 
@@ -118,11 +119,6 @@ __device__ __forceinline__ void pr_forward_rows(const float* __restrict__ x, con
     }
 }
 
-__device__ __forceinline__ double pr_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);          // a fixed tree; every lane ends with the same bits
-    return v;
-}
 __device__ __forceinline__ double pr_lane_sum(const F4& s) { return ((double)s.v[0] + (double)s.v[1]) + ((double)s.v[2] + (double)s.v[3]); }
 
 __global__ void __launch_bounds__(EMD_BLOCK) k_plane_reg_forward(PlaneTab t, double* __restrict__ partials) {
@@ -135,7 +131,9 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_plane_reg_forward(PlaneTab t, dou
         if (wide) { if (time) pr_forward_rows<true, true>(x, k, s2, s1); else pr_forward_rows<true, false>(x, k, s2, s1); }
         else { if (time) pr_forward_rows<false, true>(x, k, s2, s1); else pr_forward_rows<false, false>(x, k, s2, s1); }
     }
-    const double a = pr_wave_sum(pr_lane_sum(s2)), b = pr_wave_sum(pr_lane_sum(s1));
+    // (the four waves meet as in fixed_block_store, fixed_sum.h, but thread 0 stores both sums: through the template the kernel came out with other
+    //  instructions, profiles/shared_source_isa.txt)
+    const double a = fixed_wave_sum(pr_lane_sum(s2)), b = fixed_wave_sum(pr_lane_sum(s1));
     if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6][0] = a; sm[threadIdx.x >> 6][1] = b; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -152,7 +150,7 @@ __global__ void __launch_bounds__(PR_FINAL_THREADS) k_plane_reg_finalize(PlaneTa
     for (int p = wave; p < t.num_planes; p += PR_FINAL_THREADS / EMD_WAVE) {
         double a = 0.0, b = 0.0;
         for (int i = t.first[p] + lane; i < t.first[p + 1]; i += EMD_WAVE) { a += partials[2 * (size_t)i]; b += partials[2 * (size_t)i + 1]; }
-        a = pr_wave_sum(a); b = pr_wave_sum(b);
+        a = fixed_wave_sum(a); b = fixed_wave_sum(b);
         if (lane == 0) {
             const double R = (double)t.R[p], H = (double)t.H[p];
             smooth[p] = a / (R * (H - 2.0));

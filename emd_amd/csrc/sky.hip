@@ -12,7 +12,8 @@
 // dL/dtexel with float atomics; dL/d(foreground) and dL/d(opacity) of the blend come out of the same kernel.
 // HBM-bound by construction: 3 planar image reads/writes per pixel + 4 x 12 B texel gathers that hit L2.
 // The lookup restates the published nvdiffrast algorithm (oracle/sky_oracle.py; PARITY UNPINNED for that part).
-// The ray and tap arithmetic is sky_taps.h; the opt-in deterministic backward, which shares it and uses no atomics, is sky_det.hip.
+// The ray and tap arithmetic is sky_taps.h and the per-pixel half of the backward is sky_pixel_bwd_body.inc; the opt-in deterministic backward, which
+// shares both and uses no atomics, is sky_det.hip.
 #include "common.h"
 #include "device_utils.h"
 #include "sky_det.h"
@@ -89,60 +90,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_sky_backward(EmdSkyBwdArgs b) {
         valid = p < P;
         px = (int)p; py = 0;
     }
-    float acc = 0.f, gs[3] = {0.f, 0.f, 0.f};
-    bool sampled = false;
-    Tap tp;
-    const bool il = (a.flags & EMD_SKY_INTERLEAVED) != 0;
-    // the pixel's inputs first, unconditionally (an absent input reads the cube map's first texel and is not used; a pixel outside the image reads
-    // pixel 0): with the loads inside the branches that use them the thread made a trip to memory per input, one after the other
-    const size_t pcl = valid ? p : 0;
-    const bool blend = b.dL_dout && a.fg;
-    const float acc_raw = *(a.acc ? a.acc + pcl : a.cube);
-    float gsky_raw[3], gout_raw[3], fg_raw[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const size_t q = il ? 3 * pcl + c : (size_t)c * P + pcl;
-        gsky_raw[c] = *(b.dL_dsky ? b.dL_dsky + q : a.cube);
-        gout_raw[c] = *(blend ? b.dL_dout + q : a.cube);
-        fg_raw[c] = *(blend ? a.fg + q : a.cube);
-    }
-    if (valid) {
-        acc = a.acc ? acc_raw : 0.f;
-        sampled = !(a.acc && a.mask_threshold >= 0.f) || (1.f - acc) > a.mask_threshold;
-        float s[3] = {a.fill, a.fill, a.fill};
-        bool pass[3] = {false, false, false};
-        if (sampled) {
-            float dx, dy, dz;
-            pixel_ray(a, px, py, p, dx, dy, dz);
-            cube_taps(dx, dy, dz, res, tp);
-            s[0] = s[1] = s[2] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float* t = a.cube + (size_t)tp.idx[k] * 3;
-                s[0] += tp.w[k] * t[0]; s[1] += tp.w[k] * t[1]; s[2] += tp.w[k] * t[2];
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) pass[c] = !(a.flags & EMD_SKY_CLAMP01) || (s[c] >= 0.f && s[c] <= 1.f);   // torch.clamp backward
-        }
-        if (a.flags & EMD_SKY_CLAMP01) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) s[c] = fminf(fmaxf(s[c], 0.f), 1.f);
-        }
-        float dacc = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const size_t q = il ? 3 * p + c : (size_t)c * P + p;
-            gs[c] = b.dL_dsky ? gsky_raw[c] : 0.f;
-            if (blend) {
-                const float g = gout_raw[c], f = fg_raw[c];
-                gs[c] += g * (1.f - acc);
-                if (a.flags & EMD_SKY_BLEND_S3G) { dacc += g * (f - s[c]); if (b.dL_dfg) b.dL_dfg[q] = g * acc; }
-                else { dacc -= g * s[c]; if (b.dL_dfg) b.dL_dfg[q] = g; }
-            }
-            if (!pass[c]) gs[c] = 0.f;
-        }
-        if (b.dL_dacc) b.dL_dacc[p] = dacc;
-    }
+#include "sky_pixel_bwd_body.inc"
     if (!b.dL_dcube) return;
     // window origin: centred on the first tap of the lowest contributing lane of the workgroup
     __shared__ int s_leader;

@@ -2,8 +2,9 @@
 // The default backward (sky.hip) adds every tap's weighted colour gradient to its texel through fp64 LDS windows and global float atomics, in
 // whatever order the workgroups run.  Here every contribution is STORED once, a stable sort lists the contributions per texel in a fixed order, and
 // the segmented row sum adds each list with its pinned association (segsum.h) -- the construction of the deterministic render backward (section 8.8):
-//   k_sky_det_rows           lane = pixel: dL_dfg / dL_dacc as the default kernel writes them (the same arithmetic: sky_taps.h, sky_pixel_backward), the four weighted
-//                            rows to slots k P + p, the texels as keys (0xFFFFFFFF: not sampled, or a tap of weight zero)
+//   k_sky_det_rows           lane = pixel: dL_dfg / dL_dacc as the default kernel writes them (the same text: sky_taps.h and sky_pixel_bwd_body.inc,
+//                            which k_sky_backward includes too), the four weighted rows to slots k P + p, the texels as keys (0xFFFFFFFF: not
+//                            sampled, or a tap of weight zero)
 //   emd_det_sort_and_sum     (det_reduce.h) the compacting, stable sort: slots per texel in ascending slot order = ascending (tap, pixel);
 //                            the segmented row sum -> dL_dcube
 // No atomics and no device-scope fences anywhere.
@@ -14,81 +15,15 @@
 
 namespace {
 
-// The per-pixel half of the backward for pixel p = (px, py) of P (`valid`: the lane has a pixel): writes dL_dfg and dL_dacc of the pixel and leaves what
-// the cube-map gradient is made of -- `sampled`, the taps, and gs[c] = dL/d(sky colour c) behind the clamp (tap k adds tp.w[k] * gs[c] to its texel).
-// tp is set only when `sampled`.  This RESTATES the per-pixel half of k_sky_backward (sky.hip) statement for statement -- the same expressions in the
-// same order, hence the same bits, which tests/test_sky_det_gpu.py pins for dL_dfg and dL_dacc.  It is not called from there: with the statements
-// behind a function the default kernel's registers are allocated differently, and that kernel keeps its instructions (profiles/sky_motion_det_isa.txt).
-__device__ __forceinline__ void sky_pixel_backward(const EmdSkyBwdArgs& b, size_t P, size_t p, int px, int py, bool valid, bool& sampled, Tap& tp,
-                                                   float gs[3]) {
-    const EmdSkyArgs& a = b.f;
-    const int res = a.resolution;
-    float acc = 0.f;
-    gs[0] = gs[1] = gs[2] = 0.f;
-    sampled = false;
-    const bool il = (a.flags & EMD_SKY_INTERLEAVED) != 0;
-    // the pixel's inputs first, unconditionally (an absent input reads the cube map's first texel and is not used; a pixel outside the image reads
-    // pixel 0): with the loads inside the branches that use them the thread made a trip to memory per input, one after the other
-    const size_t pcl = valid ? p : 0;
-    const bool blend = b.dL_dout && a.fg;
-    const float acc_raw = *(a.acc ? a.acc + pcl : a.cube);
-    float gsky_raw[3], gout_raw[3], fg_raw[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const size_t q = il ? 3 * pcl + c : (size_t)c * P + pcl;
-        gsky_raw[c] = *(b.dL_dsky ? b.dL_dsky + q : a.cube);
-        gout_raw[c] = *(blend ? b.dL_dout + q : a.cube);
-        fg_raw[c] = *(blend ? a.fg + q : a.cube);
-    }
-    if (valid) {
-        acc = a.acc ? acc_raw : 0.f;
-        sampled = !(a.acc && a.mask_threshold >= 0.f) || (1.f - acc) > a.mask_threshold;
-        float s[3] = {a.fill, a.fill, a.fill};
-        bool pass[3] = {false, false, false};
-        if (sampled) {
-            float dx, dy, dz;
-            pixel_ray(a, px, py, p, dx, dy, dz);
-            cube_taps(dx, dy, dz, res, tp);
-            s[0] = s[1] = s[2] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float* t = a.cube + (size_t)tp.idx[k] * 3;
-                s[0] += tp.w[k] * t[0]; s[1] += tp.w[k] * t[1]; s[2] += tp.w[k] * t[2];
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) pass[c] = !(a.flags & EMD_SKY_CLAMP01) || (s[c] >= 0.f && s[c] <= 1.f);   // torch.clamp backward
-        }
-        if (a.flags & EMD_SKY_CLAMP01) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) s[c] = fminf(fmaxf(s[c], 0.f), 1.f);
-        }
-        float dacc = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const size_t q = il ? 3 * p + c : (size_t)c * P + p;
-            gs[c] = b.dL_dsky ? gsky_raw[c] : 0.f;
-            if (blend) {
-                const float g = gout_raw[c], f = fg_raw[c];
-                gs[c] += g * (1.f - acc);
-                if (a.flags & EMD_SKY_BLEND_S3G) { dacc += g * (f - s[c]); if (b.dL_dfg) b.dL_dfg[q] = g * acc; }
-                else { dacc -= g * s[c]; if (b.dL_dfg) b.dL_dfg[q] = g; }
-            }
-            if (!pass[c]) gs[c] = 0.f;
-        }
-        if (b.dL_dacc) b.dL_dacc[p] = dacc;
-    }
-}
-
 // Flat indexing: the 16 x 16 tiles of k_sky_backward serve its LDS window alone.  rows == NULL: no cube-map gradient is asked for.
 __global__ void __launch_bounds__(EMD_BLOCK) k_sky_det_rows(EmdSkyBwdArgs b, float4* __restrict__ rows, uint32_t* __restrict__ keys_in) {
     const EmdSkyArgs& a = b.f;
     const size_t P = (size_t)a.height * a.width;
     const size_t p = (size_t)blockIdx.x * EMD_BLOCK + threadIdx.x;
     const bool valid = p < P;
-    float gs[3];
-    bool sampled;
-    Tap tp;
-    sky_pixel_backward(b, P, p, (int)(p % (size_t)a.width), (int)(p / (size_t)a.width), valid, sampled, tp, gs);
+    const int px = (int)(p % (size_t)a.width), py = (int)(p / (size_t)a.width);
+    const int res = a.resolution;
+#include "sky_pixel_bwd_body.inc"
     if (!rows || !valid) return;
 #pragma unroll
     for (int k = 0; k < 4; k++) {

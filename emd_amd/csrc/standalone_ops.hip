@@ -53,30 +53,12 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_motion_backward(int n, const floa
                                                                const float* g_wq, const float* g_wo, float* d_means,
                                                                float* d_quats, float* d_opac, float* d_pose,
                                                                float* d_rdx, float* d_rdq) {
-    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
-    int a_id = -1;
-    float pose_g[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) pose_g[k] = 0.f;
-    if (i < n) {
-        float dm[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f}, dop = 0.f;
-        if (g_wm) { dm[0] = g_wm[3 * i]; dm[1] = g_wm[3 * i + 1]; dm[2] = g_wm[3 * i + 2]; }
-        if (g_wq) { const float4 t = *(const float4*)(g_wq + 4 * i); dq[0] = t.x; dq[1] = t.y; dq[2] = t.z; dq[3] = t.w; }
-        if (g_wo) dop = g_wo[i];
-        a_id = mo.actor_id ? mo.actor_id[i] : -1;
-        float dl[3] = {dm[0], dm[1], dm[2]}, dql[4] = {dq[0], dq[1], dq[2], dq[3]}, dopl = dop;
-        if (a_id >= 0) motion_point_backward(i, a_id, means, quats, opac, mo, dm, dq, dop, dl, dql, &dopl, pose_g);
-        if (d_means) { d_means[3 * i] = dl[0]; d_means[3 * i + 1] = dl[1]; d_means[3 * i + 2] = dl[2]; }
-        if (d_rdx) { d_rdx[3 * i] = dl[0]; d_rdx[3 * i + 1] = dl[1]; d_rdx[3 * i + 2] = dl[2]; }
-        if (d_quats) *(float4*)(d_quats + 4 * i) = make_float4(dql[0], dql[1], dql[2], dql[3]);
-        if (d_rdq) *(float4*)(d_rdq + 4 * i) = a_id >= 0 ? make_float4(dql[0], dql[1], dql[2], dql[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d_opac) d_opac[i] = dopl;
-    }
+#include "motion_point_bwd_body.inc"
     if (d_pose) reduce_pose_grad(a_id, pose_g, d_pose);
 }
 
-// The deterministic form (emd_motion_backward_det), k_motion_backward up to its last statement (the per-point arithmetic of both
-// is motion_point_backward, gaussian_math.h; k_motion_backward itself keeps its source and instructions: profiles/sky_motion_det_isa.txt): a bound point stores its twelve floats as row i of pose_rows, as K8 does
+// The deterministic form (emd_motion_backward_det), k_motion_backward up to its last statement: the per-point half of both is
+// one text, motion_point_bwd_body.inc (k_motion_backward kept its instructions: profiles/shared_source_isa.txt).  A bound point stores its twelve floats as row i of pose_rows, as K8 does
 // under EMD_FLAG_DETERMINISTIC (preprocess.hip), and its actor as the row's destination; the sort drops the static points (0xFFFFFFFF) and the
 // segmented row sum adds every actor's rows in ascending point index (api.hip).  No atomics.  pose_rows == NULL: no pose gradient is asked for.
 __global__ void __launch_bounds__(EMD_BLOCK) k_motion_backward_det(int n, const float* means, const float* quats,
@@ -84,25 +66,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_motion_backward_det(int n, const 
                                                                    const float* g_wq, const float* g_wo, float* d_means,
                                                                    float* d_quats, float* d_opac, float* d_rdx, float* d_rdq,
                                                                    float* __restrict__ pose_rows, uint32_t* __restrict__ keys_in) {
-    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
-    int a_id = -1;
-    float pose_g[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) pose_g[k] = 0.f;
-    if (i < n) {
-        float dm[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f}, dop = 0.f;
-        if (g_wm) { dm[0] = g_wm[3 * i]; dm[1] = g_wm[3 * i + 1]; dm[2] = g_wm[3 * i + 2]; }
-        if (g_wq) { const float4 t = *(const float4*)(g_wq + 4 * i); dq[0] = t.x; dq[1] = t.y; dq[2] = t.z; dq[3] = t.w; }
-        if (g_wo) dop = g_wo[i];
-        a_id = mo.actor_id ? mo.actor_id[i] : -1;
-        float dl[3] = {dm[0], dm[1], dm[2]}, dql[4] = {dq[0], dq[1], dq[2], dq[3]}, dopl = dop;
-        if (a_id >= 0) motion_point_backward(i, a_id, means, quats, opac, mo, dm, dq, dop, dl, dql, &dopl, pose_g);
-        if (d_means) { d_means[3 * i] = dl[0]; d_means[3 * i + 1] = dl[1]; d_means[3 * i + 2] = dl[2]; }
-        if (d_rdx) { d_rdx[3 * i] = dl[0]; d_rdx[3 * i + 1] = dl[1]; d_rdx[3 * i + 2] = dl[2]; }
-        if (d_quats) *(float4*)(d_quats + 4 * i) = make_float4(dql[0], dql[1], dql[2], dql[3]);
-        if (d_rdq) *(float4*)(d_rdq + 4 * i) = a_id >= 0 ? make_float4(dql[0], dql[1], dql[2], dql[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d_opac) d_opac[i] = dopl;
-    }
+#include "motion_point_bwd_body.inc"
     if (!pose_rows || i >= n) return;
     if (a_id >= 0) {
         float4* pr = reinterpret_cast<float4*>(pose_rows + (size_t)i * EMD_ACTOR_STRIDE);

@@ -1,5 +1,6 @@
 // temporal_sample.h -- the sampling set-up of the coarse-to-fine temporal embedding (rows, columns, taps) and the argument check of its entry points:
-// shared by embed.hip and embed_det.hip (the backward without atomics).  The text is embed.hip's own, moved here unchanged.
+// shared by embed.hip, embed_det.hip and track_det.hip (the backwards without atomics, DESIGN.md sections 8.14 and 8.15).  The sampling text is
+// embed.hip's own, moved here unchanged.  (The accumulation the two backwards without atomics share is te_gather_body.inc.)
 #pragma once
 #include "common.h"
 

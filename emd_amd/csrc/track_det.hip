@@ -1,65 +1,24 @@
 // track_det.hip -- the per-actor chain of embed.hip (embedding sums -> track heads -> pose row) and the gradient of the DeformableNodes encoder input
 // without float atomics.  A unit of its own: embed.hip's kernels are pinned instruction for instruction
 // (profiles/track_det_isa.txt), and a further kernel inside that unit changed the code of its neighbours (section 8.14).  The per-actor helpers the
-// two units share -- te_eval / te_column2, wave_sum_all, head_of / head_row / head_coarse, heads_eval -- are RESTATED here, text unchanged: embed.hip
-// keeps its source and so its instructions.
+// two units share -- te_eval / te_column2, wave_sum_all, head_of / head_row / head_coarse, heads_eval -- and the argument checks are ONE text,
+// track_heads.h, which both include (embed.hip kept its instructions across the move: profiles/shared_source_isa.txt).  That header holds no atomic.
 //
 //   emd_actor_row_sum_det            out[a] = the pinned segmented sum (segsum.h) of the rows i with ids[i] == a, in ascending i
 //   emd_track_heads_forward_det      the embedding sums by that row sum when the ids are not sorted by actor (or E > 8), then embed.hip's heads
-//   emd_track_heads_backward_det     k_track_heads<true> + k_track_embed_bwd without atomics
+//   emd_track_heads_backward_det     k_track_heads<true> without atomics, then embed.hip's own k_track_embed_bwd (per point, no reduction)
 //   emd_tracked_pose_backward_det    k_tracked_pose<true> without atomics
 // Head gradients: every actor STORES its share of the eight head tensors to its own slot of a slab [A][pitch]; one launch adds the slots per element in
-// ascending actor index in fp64 from 0.0 and rounds once.  Temporal table: the gather form of embed_det.hip over the two levels.
+// ascending actor index in fp64 from 0.0 and rounds once.  Temporal table: the gather form of embed_det.hip over the two levels (te_gather_body.inc).
 #include <string.h>
 
 #include "common.h"
 #include "det_reduce.h"
 #include "quat_math.h"
 #include "temporal_sample.h"
+#include "track_heads.h"
 
 namespace {
-
-// ---- restated from embed.hip (text unchanged) ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float te_eval(const TeSample& s, const float (&wv)[2][4], const TeCol& c) {
-#pragma clang fp contract(off)
-    float out = 0.f;
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const float wy = r ? s.wy1 : s.wy0;
-        const float v0 = s.la[r] * wv[r][0] + s.lb[r] * wv[r][1];
-        const float v1 = c.inx1 ? s.la[r] * wv[r][2] + s.lb[r] * wv[r][3] : 0.f;
-        const float term = v0 * (c.wx0 * wy) + v1 * (c.wx1 * wy);
-        out = (r == 1 && !s.in1) ? out : out + term;
-    }
-    return out;
-}
-
-__device__ __forceinline__ void te_column2(const float* __restrict__ weight, int dim, const TeSample& sa, const TeSample& sb, int j, float* oa, float* ob) {
-    const TeCol c = te_col(j, dim);
-    float wa[2][4], wb[2][4];
-    te_taps(weight, dim, sa, c, wa);
-    te_taps(weight, dim, sb, c, wb);
-    *oa = te_eval(sa, wa, c);
-    *ob = te_eval(sb, wb, c);
-}
-
-__device__ __forceinline__ float wave_sum_all(float v) {
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// the eight head rows: o = 0-2 trans_c, 3-5 trans_f, 6 rot_c, 7 rot_f -> head tensor, its row, and whether it reads h_c or h_f
-__device__ __forceinline__ constexpr int head_of(int o) { return o < 3 ? 0 : o < 6 ? 1 : o - 4; }
-__device__ __forceinline__ constexpr int head_row(int o) { return o < 3 ? o : o < 6 ? o - 3 : 0; }
-__device__ __forceinline__ constexpr bool head_coarse(int o) { return o < 3 || o == 6; }
-
-__device__ __forceinline__ void heads_eval(const float (&wrow)[8], const float (&hbias)[8], float hc, float hf, float (&out)[8], float* ow, float* oz) {
-#pragma unroll
-    for (int o = 0; o < 8; o++) out[o] = wave_sum_all(wrow[o] * (head_coarse(o) ? hc : hf)) + hbias[o];
-    const float cc = cosf(out[6]), scn = sinf(out[6]), cf = cosf(out[7]), sfn = sinf(out[7]);
-    *ow = fmaf(cc, cf, -(scn * sfn)); *oz = fmaf(scn, cf, cc * sfn);
-}
-// ---------------------------------------------------------------------------------------------------------------------------------------------------
 
 // The slot of one actor in the slab: the eight head tensors back to back, as EmdTrackedPoseArgs.head_acc has them -- w_tc [3 w], b_tc [3], w_tf [3 w],
 // b_tf [3], w_rc [w], b_rc [1], w_rf [w], b_rf [1]: 8 w + 8 floats, w = dim + embed_dim.
@@ -275,19 +234,7 @@ __global__ void __launch_bounds__(TRK_THREADS) k_track_chain_bwd_det(ChainBwd b)
                 for (int lvl = 0; lvl < 2; lvl++) {
                     const TeSample& s = lvl ? sf : sc;
                     const float g = s_dh[lvl][j];
-#pragma unroll
-                    for (int r = 0; r < 2; r++) {
-                        if (r == 1 && !s.in1) continue;
-                        const float wy = r ? s.wy1 : s.wy0;
-                        if (m0) {
-                            if (s.ha[r] == R) acc += (double)(g * wx0 * wy * s.la[r]);
-                            if (s.hb[r] == R) acc += (double)(g * wx0 * wy * s.lb[r]);
-                        }
-                        if (m1) {
-                            if (s.ha[r] == R) acc += (double)(g * wx1 * wy * s.la[r]);
-                            if (s.hb[r] == R) acc += (double)(g * wx1 * wy * s.lb[r]);
-                        }
-                    }
+#include "te_gather_body.inc"
                 }
             }
             G[(size_t)R * dim + c] = (float)acc;
@@ -314,40 +261,6 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_head_slab_reduce(SlabReduce r) {
         if (e >= slot_b(h, w) && e < slot_b(h, w) + rows_h) dst = r.dst_b[h] + (e - slot_b(h, w));
     }
     *dst = (float)acc;
-}
-
-// k_track_embed_bwd of embed.hip, restated: per point, no reduction
-__global__ void __launch_bounds__(EMD_BLOCK) k_track_embed_bwd_det(int n, int E, const int32_t* __restrict__ ids, const float* __restrict__ count,
-                                                                   const float* __restrict__ d_mean, float* __restrict__ d_emb) {
-    const size_t idx = (size_t)blockIdx.x * EMD_BLOCK + threadIdx.x;
-    if (idx >= (size_t)n * E) return;
-    const int i = (int)(idx / E), e = (int)(idx % E), id = ids[i];
-    d_emb[idx] = id >= 0 ? d_mean[(size_t)id * E + e] / count[id] : 0.f;
-}
-
-// the refusals of embed.hip's check_track / check_tracked
-int check_track(const EmdTrackArgs* a, const char* who) {
-    if (!a) { emd_set_error("%s: null args", who); return EMD_ERR_INVALID; }
-    if (a->num_actors < 0 || a->rows < 1 || a->dim < 1 || a->embed_dim < 0 || a->dim + a->embed_dim > EMD_WAVE || a->k_coarse < 1 || a->k_fine < 1 ||
-        a->num_points < 0) { emd_set_error("%s: bad sizes (dim + embed_dim <= 64)", who); return EMD_ERR_INVALID; }
-    if (a->num_actors == 0) return EMD_OK;
-    if (!a->weight || !a->count || !a->emb_sum || (a->embed_dim > 0 && a->num_points > 0 && (!a->embeddings || !a->point_ids))) {
-        emd_set_error("%s: null pointer", who); return EMD_ERR_INVALID;
-    }
-    for (int h = 0; h < 4; h++) if (!a->head_w[h] || !a->head_b[h]) { emd_set_error("%s: null head parameter %d", who, h); return EMD_ERR_INVALID; }
-    return EMD_OK;
-}
-int check_tracked(const EmdTrackedPoseArgs* p, const char* who) {
-    if (!p) { emd_set_error("%s: null args", who); return EMD_ERR_INVALID; }
-    int rc = check_track(&p->track, who);
-    if (rc) return rc;
-    const EmdTrackArgs& a = p->track;
-    if (a.num_actors == 0) return EMD_OK;
-    if (!a.segment_start || a.embed_dim > 8) { emd_set_error("%s: needs segment_start (points sorted by actor) and embed_dim <= 8", who); return EMD_ERR_INVALID; }
-    if (!p->q_all || !p->t_all || p->num_frames < 1 || (!p->frame_dev && (p->frame < 0 || p->frame >= p->num_frames))) {
-        emd_set_error("%s: bad pose tables / frame", who); return EMD_ERR_INVALID;
-    }
-    return EMD_OK;
 }
 
 int reduce_slab(const TrackDetWs& w, int A, int width, float* const (&d_w)[4], float* const (&d_b)[4], hipStream_t st) {
@@ -441,10 +354,7 @@ extern "C" int emd_track_heads_backward_det(const EmdTrackArgs* a, const EmdTrac
     rc = reduce_slab(w, A, width, g->d_head_w, g->d_head_b, st);
     if (rc) return rc;
     if (g->d_embeddings && E > 0 && a->num_points > 0) {
-        const size_t total = (size_t)a->num_points * E;
-        hipLaunchKernelGGL(k_track_embed_bwd_det, dim3((unsigned)((total + EMD_BLOCK - 1) / EMD_BLOCK)), dim3(EMD_BLOCK), 0, st, a->num_points, E, a->point_ids,
-                           a->count, (const float*)g->d_mean, g->d_embeddings);
-        EMD_LAUNCH_CHECK();
+        return emd_launch_track_embed_bwd(a->num_points, E, a->point_ids, a->count, g->d_mean, g->d_embeddings, st);
     }
     return EMD_OK;
 }

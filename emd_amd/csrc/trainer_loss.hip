@@ -19,6 +19,7 @@
 //   k_affine_forward / k_affine_backward / k_affine_finalize   the colour correction, dL/drgb, and the 12 sums of dL/dA by the same scheme
 // No atomics anywhere: every output is a fixed function of the inputs.
 #include "common.h"
+#include "fixed_sum.h"
 
 namespace {
 
@@ -45,25 +46,7 @@ struct Plan {
     int64_t chunks, tiles_x, tiles_y, map_rows, map_cols;
 };
 
-__device__ __forceinline__ double tl_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);          // a fixed tree; every lane ends with the same bits
-    return v;
-}
 __device__ __forceinline__ float tl_sign(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-
-// N per-lane doubles -> the workgroup's sums at out[0 .. N): lanes in a fixed tree, the four waves left to right
-template <int N>
-__device__ __forceinline__ void tl_block_store(const double (&v)[N], double* __restrict__ out) {
-    __shared__ double sm[EMD_BLOCK / EMD_WAVE][N];
-#pragma unroll
-    for (int q = 0; q < N; q++) {
-        const double s = tl_wave_sum(v[q]);
-        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][q] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) out[threadIdx.x] = (sm[0][threadIdx.x] + sm[1][threadIdx.x]) + (sm[2][threadIdx.x] + sm[3][threadIdx.x]);
-}
 
 // one wave: rows 0 .. n-1 of column q of a [n][stride] table of doubles.  Lane l owns the rows l, l + 64, ...: it adds them in ascending order into
 // four accumulators taken in turn (four loads in flight: one accumulator made the single workgroup of a finalize wait for ~80 dependent loads),
@@ -78,7 +61,7 @@ __device__ __forceinline__ double tl_column_sum(const double* __restrict__ tab, 
 #pragma unroll
     for (int k = 0; k < 3; k++)
         if (i + k * EMD_WAVE < n) a[k] += tab[(i + k * EMD_WAVE) * stride + q];
-    return tl_wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+    return fixed_wave_sum((a[0] + a[1]) + (a[2] + a[3]));
 }
 
 __device__ __forceinline__ float tl_inv_depth(float d) { return 1.f / (d + 1e-5f); }
@@ -187,7 +170,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_tl_pointwise(EmdTrainerLossArgs a
             if (below[it]) s[6] += (double)fabsf((iq - tl_inv_depth(q.dd)) * tl_edge_weight(q.y, q.yd));
         }
     }
-    tl_block_store<TL_NSUM>(s, partials + (size_t)blockIdx.x * TL_NSUM);
+    fixed_block_store<TL_NSUM>(s, partials + (size_t)blockIdx.x * TL_NSUM);
 }
 
 // stage the SS_HY x SS_HX halos of NIMG [rows][cols] matrices whose local (0, 0) is (y0, x0), zero outside the matrix.  All of a thread's loads are
@@ -290,7 +273,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_tl_ssim_forward(EmdTrainerLossArg
         }
     }
     const double v1[1] = {(double)val};
-    tl_block_store<1>(v1, tile_sums + blockIdx.x);
+    fixed_block_store<1>(v1, tile_sums + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(EMD_BLOCK) k_tl_ssim_backward(EmdTrainerLossArgs a, Plan pl, Win win, const float* __restrict__ dmaps) {
@@ -443,7 +426,7 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_affine_backward(int64_t P, const 
             }
         }
     }
-    if (partials) tl_block_store<AFF_NSUM>(s, partials + (size_t)blockIdx.x * AFF_NSUM);
+    if (partials) fixed_block_store<AFF_NSUM>(s, partials + (size_t)blockIdx.x * AFF_NSUM);
 }
 
 __global__ void __launch_bounds__(TL_FINAL_THREADS) k_affine_finalize(int64_t chunks, const double* __restrict__ partials, float* __restrict__ d_A) {

@@ -20,6 +20,7 @@
 // same way.  Every global load of a kernel is issued before the arithmetic starts.
 #include "common.h"
 #include "device_utils.h"
+#include "fixed_sum.h"
 #include "gaussian_math.h"
 
 #pragma clang fp contract(off)
@@ -274,12 +275,6 @@ __device__ __forceinline__ VrScales vr_scales(float l0, float l1, float l2) {
 __device__ __forceinline__ float vr_small_side(float a) { return 1.f / (1.f + expf(fabsf(a))); }
 #define VR_CLIP 1e-6f
 
-__device__ __forceinline__ double vr_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);          // a fixed tree; every lane ends with the same bits
-    return v;
-}
-
 // partials [chunks][4] doubles: the sums over the chunk of max(ratio, R) - R, min(smin, 30), the entropy over V, smax^2; counts [chunks]: |V| of the chunk
 __global__ void __launch_bounds__(EMD_BLOCK) k_vanilla_reg_forward(int n, const float* __restrict__ ls, const float* __restrict__ logits,
                                                                    const int32_t* __restrict__ radii, float R, int scale_terms, int sparse,
@@ -314,8 +309,10 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_vanilla_reg_forward(int n, const 
             vis++;
         }
     }
+    // (the four waves meet as in fixed_block_store, fixed_sum.h, with the integer count beside the doubles behind the same barrier: through the
+    //  template the kernel came out with other instructions, profiles/shared_source_isa.txt)
 #pragma unroll
-    for (int k = 0; k < 4; k++) acc[k] = vr_wave_sum(acc[k]);
+    for (int k = 0; k < 4; k++) acc[k] = fixed_wave_sum(acc[k]);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) vis += __shfl_xor(vis, m);
     if ((threadIdx.x & 63) == 0) {
@@ -343,7 +340,7 @@ __global__ void __launch_bounds__(VG_REG_FINAL_THREADS) k_vanilla_reg_finalize(i
         vis += counts[c];
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) acc[k] = vr_wave_sum(acc[k]);
+    for (int k = 0; k < 4; k++) acc[k] = fixed_wave_sum(acc[k]);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) vis += __shfl_xor(vis, m);
     if ((threadIdx.x & 63) == 0) {

@@ -210,9 +210,11 @@ def test_identical_bits_across_runs_streams_and_graph_replay(monkeypatch):
         assert same(first, captured)
 
 
-@pytest.mark.parametrize("n,sizes", [(1, (1,)), (1, (0,)), (255, (100, 60)), (513, (513,)), (513, (0, 0, 0))])
+@pytest.mark.parametrize("n,sizes", [(1, (1,)), (1, (0,)), (255, (100, 60)), (513, (513,)), (513, (0, 0, 0)), (257, (60, 57, 55))])
 def test_edges_of_the_chunk_and_the_block(n, sizes):
-    """One point (bound / static), a ragged block, one run of a chunk and one element, every point static."""
+    """One point (bound / static), a ragged block, one run of a chunk and one element, every point static, and one workgroup and one lane with three
+    actors and a third of the points static.  (_check_call: the per-point outputs are the default entry's, bit for bit -- both kernels include one
+    text.  The last case is appended, so the earlier cases keep their ids.)"""
     got = _check_call(_case(n, sizes, seed=n))
     if sum(sizes) == 0:
         assert (got["d_pose"].view(np.uint32) == 0).all()

@@ -31,8 +31,39 @@ def test_the_unit_is_built_by_the_makefile():
     assert re.search(r"^OBJS = .*\btrack_det\.o\b", mk, re.M)
     for header in ("temporal_sample.h", "quat_math.h", "det_reduce.h"):
         assert re.search(r"^[^#\n]*\btrack_det\.o\b[^\n]*: [^\n]*%s" % re.escape(header), mk, re.M), header
-    src = open(os.path.join(ROOT, "emd_amd", "csrc", "track_det.hip")).read()
-    assert "atomic" not in re.sub(r"//[^\n]*", "", src)          # no atomics anywhere in the unit's code
+    csrc = os.path.join(ROOT, "emd_amd", "csrc")
+    code = lambda name: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, name)).read())
+    assert "atomic" not in code("track_det.hip")                 # no atomics anywhere in the unit's code
+    # ... nor in the source text the units without atomics share with the default kernels: every project file they include, directly or through
+    # another, that holds such shared text is read the same way
+    shared = {"track_det.hip": ("track_heads.h", "temporal_sample.h", "te_gather_body.inc"), "sky_det.hip": ("sky_pixel_bwd_body.inc",),
+              "embed_det.hip": ("temporal_sample.h", "te_gather_body.inc")}
+
+    def included(name, seen):
+        for inc in re.findall(r'^\s*#include "([^"]+)"', open(os.path.join(csrc, name)).read(), re.M):
+            if inc not in seen and os.path.exists(os.path.join(csrc, inc)):
+                seen.add(inc)
+                included(inc, seen)
+        return seen
+
+    for unit, files in shared.items():
+        incs = included(unit, set())
+        for f in files:
+            assert f in incs, (unit, f)
+            assert "atomic" not in code(f), f
+    # a file named *_body.inc or track_heads.h that one of these units includes is in the list above: a new one is not missed
+    for unit in shared:
+        for f in included(unit, set()):
+            if f.endswith(".inc") or f == "track_heads.h":
+                assert f in shared[unit], (unit, f)
+    # the objects are rebuilt when the shared text changes
+    for objs, dep in ((("embed.o", "track_det.o"), "track_heads.h"), (("sky.o", "sky_det.o"), "sky_pixel_bwd_body.inc"),
+                      (("standalone_ops.o",), "motion_point_bwd_body.inc"), (("embed_det.o", "track_det.o"), "te_gather_body.inc"),
+                      (("plane_reg.o", "vanilla.o", "trainer_loss.o"), "fixed_sum.h")):
+        for obj in objs:
+            assert re.search(r"^[^#\n]*\b%s\b[^\n]*: [^\n]*\b%s\b" % (re.escape(obj), re.escape(dep)), mk, re.M), (obj, dep)
+        users = [u for u in os.listdir(csrc) if u.endswith(".hip") and re.search(r'#include "%s"' % re.escape(dep), open(os.path.join(csrc, u)).read())]
+        assert sorted(u[:-4] + ".o" for u in users) == sorted(objs), (dep, users)
 
 
 @pytest.mark.parametrize("A,w,n,g", [(1, 0, 1, 1), (32, 36, 0, 0), (32, 0, 160000, 10), (4, 64, 9221, 8), (5, 0, 4000, 64), (33, 3, 99, 40)])

@@ -383,6 +383,47 @@ def test_interleaved_ids_take_the_row_sum_in_the_forward(edim, fdim, form, monke
         assert d <= 1e-4 * m + 1e-7, (what, d, m)
 
 
+@pytest.mark.parametrize("order", ["sorted", "interleaved"])
+def test_embedding_gradient_of_the_heads_form_has_the_default_entrys_bits(order):
+    """emd_track_heads_backward_det against emd_track_heads_backward through ctypes on the same inputs (A = 3, dim = 4, E = 4, 130 points in more
+    than one workgroup of the per-point launch; the same forward sums): dL/d embeddings is per point, d_mean[id] / count[id] by embed.hip's own
+    k_track_embed_bwd in both, and d_mean is the same expressions in both units -- bit for bit."""
+    A, dim, E, n, rows = 3, 4, 4, 130, ROWS
+    g = torch.Generator().manual_seed(130)
+    ids = torch.repeat_interleave(torch.arange(A), torch.tensor([70, 1, 59]))
+    if order == "interleaved":
+        ids = ids[torch.randperm(n, generator=g)]
+        assert bool((ids[1:] < ids[:-1]).any())
+    width = dim + E
+    r = lambda *shape, s=1.0: (s * torch.randn(*shape, generator=g)).to(DEV)
+    weight, emb = r(A, rows, dim, s=0.5), r(n, E)
+    heads = [r(3, width, s=0.3), r(3, s=0.1), r(3, width, s=0.3), r(3, s=0.1), r(1, width, s=0.3), r(1, s=0.1), r(1, width, s=0.3), r(1, s=0.1)]
+    g_trans, g_rot = r(A, 3), r(A, 4)
+    ids32 = ids.to(torch.int32).to(DEV)
+    cnt = torch.bincount(ids, minlength=A).float().to(DEV)
+    emb_sum = torch.zeros(A, E, device=DEV).index_add_(0, ids.to(DEV), emb)
+    a = motion._TrackHeads._args(weight, emb, heads, ids32, cnt, None, 0.5, 30, ROWS, emb_sum, None, None)
+    got = {}
+    for det in (False, True):
+        bufs = dict(d_weight=torch.zeros(A, rows, dim, device=DEV), d_emb=torch.full((n, E), float("nan"), device=DEV), d_mean=torch.empty(A, E, device=DEV),
+                    d_heads=[torch.zeros_like(h) for h in heads])
+        gr = L.EmdTrackGrads()
+        gr.g_trans, gr.g_rot, gr.d_weight = g_trans.data_ptr(), g_rot.data_ptr(), bufs["d_weight"].data_ptr()
+        gr.d_embeddings, gr.d_mean = bufs["d_emb"].data_ptr(), bufs["d_mean"].data_ptr()
+        for h in range(4):
+            gr.d_head_w[h], gr.d_head_b[h] = bufs["d_heads"][2 * h].data_ptr(), bufs["d_heads"][2 * h + 1].data_ptr()
+        if det:
+            ws = torch.empty(L.track_det_workspace_size(A, width), dtype=torch.uint8, device=DEV)
+            L.check(L.load().emd_track_heads_backward_det(C.byref(a), C.byref(gr), ws.data_ptr(), ws.numel(), _stream()), "emd_track_heads_backward_det")
+        else:
+            L.check(L.load().emd_track_heads_backward(C.byref(a), C.byref(gr), _stream()), "emd_track_heads_backward")
+        torch.cuda.synchronize()
+        got[det] = bufs["d_emb"]
+    assert bool(torch.isfinite(got[True]).all()) and float(got[True].abs().min()) > 0
+    assert torch.equal(got[True], got[False])
+    assert torch.equal(got[True].view(torch.int32), got[False].view(torch.int32))
+
+
 # ---- 5. the same bits in every setting ----------------------------------------------------------------------------------------------------------------------
 def _same_bits_everywhere(step):
     """step() -> list of gradients: two eager runs, a run on a side stream behind a busy main stream, two replays of a captured graph."""
