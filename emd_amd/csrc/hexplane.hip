@@ -876,8 +876,8 @@ extern "C" int emd_hexplane_order_keys(const float* pts, const float* aabb, int6
 extern "C" int emd_hexplane_forward(const EmdHexArgs* a, void* hip_stream) {
     int rc = check_hex(a, "hexplane_forward");
     if (rc) return rc;
+    if (a->num_points == 0) return EMD_OK;            // (an empty output has no memory: its pointer is null)
     if (!a->out) { emd_set_error("hexplane_forward: null output"); return EMD_ERR_INVALID; }
-    if (a->num_points == 0) return EMD_OK;
     const unsigned chunks = (unsigned)((a->num_points + HEX_F4_POINTS - 1) / HEX_F4_POINTS), grid4 = (chunks + 7u) / 8u * 8u;
     if (a->time_tables) {
         if (a->channels != 32 && a->channels != 16) { emd_set_error("hexplane_forward: time_tables are served for 16 or 32 channels"); return EMD_ERR_INVALID; }
@@ -898,8 +898,9 @@ extern "C" int emd_hexplane_forward(const EmdHexArgs* a, void* hip_stream) {
 extern "C" int emd_hexplane_backward(const EmdHexArgs* a, const EmdHexGrads* g, void* hip_stream) {
     int rc = check_hex(a, "hexplane_backward");
     if (rc) return rc;
-    if (!g || !g->dL_dout) { emd_set_error("hexplane_backward: null gradient"); return EMD_ERR_INVALID; }
-    if (a->num_points == 0) return EMD_OK;
+    if (!g) { emd_set_error("hexplane_backward: null gradient"); return EMD_ERR_INVALID; }
+    if (a->num_points == 0) return EMD_OK;            // (an empty dL/dout has no memory either)
+    if (!g->dL_dout) { emd_set_error("hexplane_backward: null gradient"); return EMD_ERR_INVALID; }
     if (g->flags & EMD_HEX_FLAG_DETERMINISTIC) return emd_hexplane_backward_det(a, g, (hipStream_t)hip_stream);   // (hexplane_det.hip; ignores the orders and defer_*)
     if (g->defer_mask) {
         const bool agg = a->order && (a->channels == 32 || a->channels == 16);

@@ -59,3 +59,25 @@ def test_visiting_orders_are_permutations_with_inverses_and_defer_the_fine_scale
     assert big.defer_mask == 0b1110
     small = VisitingOrders.build(pts[:300], aabb, [[4, 4, 4, 2], [6, 6, 6, 2]])
     assert small.defer_mask == 0 and small.order2d is None
+
+
+def test_empty_lookup_needs_no_output_memory():
+    """Host side of emd_hexplane_forward / backward: a call over zero points returns before it asks for `out` / `dL_dout` -- an empty tensor has no
+    memory, its pointer is null (tests/test_hexplane_edges_gpu.py runs the empty lookup) --; with points the null pointers are still refused."""
+    import ctypes as C
+    from emd_amd import _lib as L
+    lib = L.load()
+    cell = (C.c_float * 8)()
+    a = L.EmdHexArgs()
+    a.num_points, a.channels, a.num_scales = 0, 8, 1
+    for k in range(4):
+        a.res[0][k] = 1
+    for p in range(6):
+        a.planes[0][p] = C.addressof(cell)
+    g = L.EmdHexGrads()
+    assert lib.emd_hexplane_forward(C.byref(a), None) == 0
+    assert lib.emd_hexplane_backward(C.byref(a), C.byref(g), None) == 0
+    assert lib.emd_hexplane_backward(C.byref(a), None, None) != 0 and b"null gradient" in lib.emd_last_error()
+    a.num_points, a.pts, a.times = 2, C.addressof(cell), C.addressof(cell)
+    assert lib.emd_hexplane_forward(C.byref(a), None) != 0 and b"null output" in lib.emd_last_error()
+    assert lib.emd_hexplane_backward(C.byref(a), C.byref(g), None) != 0 and b"null gradient" in lib.emd_last_error()
