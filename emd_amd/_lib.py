@@ -192,6 +192,13 @@ class EmdRefineArgs(C.Structure):
                 ("cull_size", C.c_float), ("cull_screen", C.c_float)]
 
 
+class EmdRefineNodesArgs(C.Structure):
+    """EmdRefineArgs's fields, then the actor part (include/emd_raster.h)."""
+    _fields_ = EmdRefineArgs._fields_ + [("means", _f), ("rotation", _f), ("ids", _f), ("instances_size", _f), ("num_actors", C.c_int32),
+                                         ("num_samples", C.c_int32), ("cull_out_of_bound", C.c_int32), ("group_by_actor", C.c_int32),
+                                         ("seed", C.c_uint64), ("samples", _f)]
+
+
 class EmdDensifyTensor(C.Structure):
     _fields_ = [("src", _f), ("dst", _f), ("width", C.c_int32), ("role", C.c_int32)]
 
@@ -323,6 +330,7 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_deform_input_backward", "emd_adam_step", "emd_track_heads_forward", "emd_track_heads_backward",
                     "emd_densify_decide", "emd_densify_index", "emd_densify_split_rank", "emd_densify_gather",
                     "emd_refine_decide", "emd_refine_index", "emd_after_train_stats", "emd_densify_scan",
+                    "emd_refine_nodes_decide", "emd_refine_nodes_index_workspace", "emd_refine_nodes_index",
                     "emd_mlp_trunk_forward", "emd_mlp_trunk_backward", "emd_mlp_branch_forward", "emd_mlp_branch_backward",
                     "emd_abs_mean_backward", "emd_residual_l1_backward", "emd_tracked_pose_forward", "emd_tracked_pose_backward",
                     "emd_select_step_inputs", "emd_compact_rows", "emd_scatter_rows", "emd_l1_loss_ws",
@@ -421,6 +429,9 @@ def load():
     lib.emd_densify_split_rank.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.emd_densify_gather.argtypes = [C.POINTER(EmdDensifyGather), C.c_void_p]
     lib.emd_refine_decide.argtypes = [C.POINTER(EmdRefineArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.emd_refine_nodes_decide.argtypes = [C.POINTER(EmdRefineNodesArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.emd_refine_nodes_index_workspace.argtypes, lib.emd_refine_nodes_index_workspace.restype = [C.c_int32], C.c_size_t
+    lib.emd_refine_nodes_index.argtypes = [C.POINTER(EmdRefineNodesArgs), C.c_int32] + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]
     lib.emd_refine_index.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emd_after_train_stats.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
     lib.emd_abs_mean_backward.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "radix_sort.h"
 
 namespace {
 
@@ -393,6 +394,229 @@ extern "C" int emd_densify_split_rank(int32_t num_out, int32_t n_keep, int32_t n
     if (num_out == 0) return EMD_OK;
     hipLaunchKernelGGL(k_densify_split_rank, dim3((num_out + EMD_BLOCK - 1) / EMD_BLOCK), dim3(EMD_BLOCK), 0, (hipStream_t)hip_stream, num_out, n_keep,
                        n_clone, n_split, rank);
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+// ---- Refinement of the OmniRe actor classes (EmdRefineNodesArgs in include/emd_raster.h restates the contract) -----------------------------------
+// Columns of a row's code (bit c = column c): 0 original kept, 1 duplicate kept, 2 source is split, 3 + r sample of replica r kept,
+// 3 + num_samples id outside [0, num_actors).  The column count is a run-time number here (5..17), so the flags of a thread travel as one mask.
+namespace {
+
+enum { NCOL_KEEP = 0, NCOL_DUP = 1, NCOL_SPLIT = 2, NCOL_SAMPLE0 = 3, NODES_MAX_COLS = 4 + 13 };
+
+// per-block counts of every column; every thread of the block calls it (threads past the end with mask 0)
+__device__ __forceinline__ void block_mask_counts(uint32_t m, int ncols, int32_t* __restrict__ counts, int nblocks) {
+    __shared__ uint32_t s_cnt[NODES_MAX_COLS][EMD_BLOCK / EMD_WAVE];
+    const int wave = threadIdx.x / EMD_WAVE, lane = threadIdx.x % EMD_WAVE;
+    for (int c = 0; c < ncols; c++) {
+        const unsigned long long b = __ballot((m >> c) & 1u);
+        if (lane == 0) s_cnt[c][wave] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < ncols) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < EMD_BLOCK / EMD_WAVE; w++) t += s_cnt[threadIdx.x][w];
+        counts[(size_t)threadIdx.x * nblocks + blockIdx.x] = (int32_t)t;
+    }
+}
+
+__global__ void __launch_bounds__(EMD_BLOCK) k_refine_nodes_decide(EmdRefineNodesArgs a, int32_t* __restrict__ code, int32_t* __restrict__ counts) {
+    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
+    const int ns = a.num_samples;
+    uint32_t m = 0;
+    if (i < a.num_points) {
+    const int id = a.ids[i];
+    if (id < 0 || id >= a.num_actors) m = 1u << (NCOL_SAMPLE0 + ns);
+    else {
+    // ---- the expressions of k_refine_decide -------------------------------------------------------------------------------------------------
+    const float l0 = a.scaling[3 * i], l1 = a.scaling[3 * i + 1], l2 = a.scaling[3 * i + 2];
+    float smax = fmaxf(expf(l0), fmaxf(expf(l1), expf(l2)));
+    const float m2d = a.max_2Dsize ? a.max_2Dsize[i] : 0.f;
+    bool dup = false, split = false;
+    float smax_new = smax;
+    if (a.do_densify) {
+        const bool high = a.grad_norm[i] / a.vis_counts[i] > a.grad_threshold;
+        split = (smax > a.size_threshold || (a.use_split_screen && m2d > a.split_screen)) && high;
+        if (split) {
+            smax_new = fmaxf(expf(logf(expf(l0) / 1.6f)), fmaxf(expf(logf(expf(l1) / 1.6f)), expf(logf(expf(l2) / 1.6f))));
+            smax = smax_new;
+        }
+        dup = smax <= a.size_threshold && high;
+    }
+    bool keep = true, keep_dup = dup, drop_new = false;
+    const bool box = a.do_cull && a.cull_out_of_bound;
+    if (a.do_cull) {
+        const float op = 1.f / (1.f + expf(-a.opacity[i]));
+        const bool faint = op < a.cull_alpha;
+        const bool big = a.cull_big && smax > a.cull_size;
+        const bool wide_old = a.cull_big && a.use_cull_screen && m2d > a.cull_screen;
+        const bool wide_new = a.cull_big && a.use_cull_screen && 0.f > a.cull_screen;
+        bool out = false;                                         // the row's own mean against its actor's box
+        if (box) {
+#pragma unroll 1
+            for (int c = 0; c < 3; c++) out = out || fabsf(a.means[3 * (size_t)i + c]) > a.instances_size[3 * (size_t)id + c] / 2.f;
+        }
+        keep = !(faint || big || wide_old || out);
+        drop_new = faint || big || wide_new;
+        keep_dup = dup && !(drop_new || out);
+    }
+    m = (keep ? 1u << NCOL_KEEP : 0u) | (keep_dup ? 1u << NCOL_DUP : 0u) | (split ? 1u << NCOL_SPLIT : 0u);
+    if (split && !drop_new) {
+        if (!box) m |= ((1u << ns) - 1u) << NCOL_SAMPLE0;
+        else {
+            // the gather's own position function on the gather's own inputs: samples by SOURCE ROW (num_split = N, the rank is the row)
+            EmdDensifyGather g;
+            int32_t row = i;
+            g.samples = a.samples; g.num_split = a.num_points; g.split_rank = &row;
+            g.seed = a.seed; g.scaling = a.scaling; g.rotation = a.rotation;
+            for (int r = 0; r < ns; r++) {
+                bool out = false;
+#pragma unroll 1
+                for (int c = 0; c < 3; c++) {
+                    const float p = split_sample_coord(g, i, r, 0, c, a.means[3 * (size_t)i + c]);
+                    out = out || fabsf(p) > a.instances_size[3 * (size_t)id + c] / 2.f;
+                }
+                if (!out) m |= 1u << (NCOL_SAMPLE0 + r);
+            }
+        }
+    }
+    }
+    code[i] = (int32_t)m;
+    }
+    block_mask_counts(m, 4 + ns, counts, (int)gridDim.x);
+}
+
+// Every output row of source i, in the reference's order (kept originals, kept samples of replica 0, 1, ..., kept duplicates, each in source order).
+// Ungrouped: straight into the outputs.  Grouped: `ids_out` is the sort's key buffer and `order` its value buffer (the row's own position).
+__global__ void __launch_bounds__(EMD_BLOCK) k_refine_nodes_index(int n, int ns, int num_out, const int32_t* __restrict__ code, const int32_t* __restrict__ ids,
+                                                                  const int32_t* __restrict__ offsets, const int32_t* __restrict__ totals, int32_t* __restrict__ src,
+                                                                  int32_t* __restrict__ kind, int32_t* __restrict__ ids_out, int32_t* __restrict__ split_rank,
+                                                                  uint32_t* __restrict__ order) {
+    __shared__ uint32_t s_cnt[NODES_MAX_COLS][EMD_BLOCK / EMD_WAVE];
+    const int i = blockIdx.x * EMD_BLOCK + threadIdx.x;
+    const int wave = threadIdx.x / EMD_WAVE, lane = threadIdx.x % EMD_WAVE, nblocks = (int)gridDim.x, ncols = 3 + ns;
+    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const uint32_t m = i < n ? (uint32_t)code[i] : 0u;
+    for (int c = 0; c < ncols; c++) {
+        const unsigned long long b = __ballot((m >> c) & 1u);
+        if (lane == 0) s_cnt[c][wave] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    const int id = i < n ? ids[i] : 0;
+    const int sp = (m >> NCOL_SPLIT) & 1u ? 16 : 0;
+    int base = 0;                                                  // first output row of the column's section
+    const auto emit = [&](int c, int kd, int rank) {
+        const unsigned long long b = __ballot((m >> c) & 1u);      // (every lane of the wave gets here: `c` is uniform)
+        if ((m >> c) & 1u) {
+            int j = base + offsets[(size_t)c * nblocks + blockIdx.x] + __popcll(b & lt);
+            for (int w = 0; w < wave; w++) j += (int)s_cnt[c][w];
+            if (j < num_out) {
+                src[j] = i; kind[j] = kd | sp; ids_out[j] = id;
+                if (split_rank) split_rank[j] = rank;
+                if (order) order[j] = (uint32_t)j;
+            }
+        }
+    };
+    emit(NCOL_KEEP, 0, 0);
+    base = totals[NCOL_KEEP];
+    for (int r = 0; r < ns; r++) { emit(NCOL_SAMPLE0 + r, 2 + r, i); base += totals[NCOL_SAMPLE0 + r]; }
+    emit(NCOL_DUP, 1, 0);
+}
+
+// grouped: output row k takes the row the stable sort put there; segment_start[a] = first k with actor >= a
+__global__ void __launch_bounds__(EMD_BLOCK) k_refine_nodes_group(int num_out, int num_actors, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
+                                                                  const int32_t* __restrict__ src_u, const int32_t* __restrict__ kind_u, int32_t* __restrict__ src,
+                                                                  int32_t* __restrict__ kind, int32_t* __restrict__ ids_out, int32_t* __restrict__ split_rank,
+                                                                  int32_t* __restrict__ segment_start) {
+    const int k = blockIdx.x * EMD_BLOCK + threadIdx.x;
+    if (k < num_out) {
+        const uint32_t j = order[k];
+        if (j < (uint32_t)num_out) {
+            const int s = src_u[j], kd = kind_u[j];
+            src[k] = s; kind[k] = kd; ids_out[k] = (int32_t)keys[k];
+            if (split_rank) split_rank[k] = (kd & 15) >= 2 ? s : 0;
+        }
+    }
+    if (k <= num_actors) {
+        int lo = 0, hi = num_out;
+        while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (keys[mid] < (uint32_t)k) lo = mid + 1; else hi = mid; }
+        segment_start[k] = lo;
+    }
+}
+
+size_t nodes_ws_align(size_t words) { return (words + 63) / 64 * 64; }          // sections start on 256-byte boundaries
+
+bool nodes_args_ok(const EmdRefineNodesArgs* a, const char* what) {
+    if (a->num_points < 0) { emd_set_error("%s: negative size", what); return false; }
+    if (a->num_actors < 1 || a->num_actors > 65536) { emd_set_error("%s: num_actors %d outside 1..65536", what, a->num_actors); return false; }
+    if (a->num_samples < 1 || a->num_samples > 13) { emd_set_error("%s: num_samples %d outside 1..13", what, a->num_samples); return false; }
+    if ((a->cull_out_of_bound | a->group_by_actor) & ~1) { emd_set_error("%s: cull_out_of_bound / group_by_actor must be 0 or 1", what); return false; }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int emd_refine_nodes_decide(const EmdRefineNodesArgs* a, int32_t* code, int32_t* columns, void* hip_stream) {
+    if (!a || !code || !columns) { emd_set_error("refine_nodes_decide: null argument"); return EMD_ERR_INVALID; }
+    if (!nodes_args_ok(a, "refine_nodes_decide")) return EMD_ERR_INVALID;
+    if (a->num_points == 0) return EMD_OK;
+    if (!a->scaling || !a->ids || (a->do_densify && (!a->grad_norm || !a->vis_counts)) || (a->do_cull && !a->opacity) ||
+        (((a->do_densify && a->use_split_screen) || (a->do_cull && a->cull_big && a->use_cull_screen)) && !a->max_2Dsize) ||
+        (a->do_cull && a->cull_out_of_bound && (!a->means || !a->rotation || !a->instances_size))) {
+        emd_set_error("refine_nodes_decide: null input"); return EMD_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(k_refine_nodes_decide, dim3((a->num_points + EMD_BLOCK - 1) / EMD_BLOCK), dim3(EMD_BLOCK), 0, (hipStream_t)hip_stream, *a, code, columns);
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+// scratch of a grouped index over num_out rows: two key and two value buffers of the sort, the ungrouped src / kind, the sort's histograms
+extern "C" size_t emd_refine_nodes_index_workspace(int32_t num_out) {
+    if (num_out <= 0) return 0;
+    const size_t m = nodes_ws_align((size_t)num_out), tiles = ((size_t)num_out + EMD_SORT_TILE - 1) / EMD_SORT_TILE;
+    return sizeof(uint32_t) * (6 * m + nodes_ws_align(512 * tiles));
+}
+
+extern "C" int emd_refine_nodes_index(const EmdRefineNodesArgs* a, int32_t num_out, const int32_t* code, const int32_t* block_offsets, const int32_t* totals,
+                                      int32_t* src, int32_t* kind, int32_t* ids_out, int32_t* segment_start, int32_t* split_rank, void* workspace,
+                                      size_t workspace_bytes, void* hip_stream) {
+    if (!a) { emd_set_error("refine_nodes_index: null argument"); return EMD_ERR_INVALID; }
+    if (!nodes_args_ok(a, "refine_nodes_index")) return EMD_ERR_INVALID;
+    const int n = a->num_points, ns = a->num_samples;
+    const bool grouped = a->group_by_actor != 0;
+    if (num_out < 0 || (grouped && !segment_start) || (n > 0 && (!code || !block_offsets || !totals || !a->ids)) || (num_out > 0 && (!src || !kind || !ids_out)) ||
+        (n > 0 && grouped && num_out > 0 && (!workspace || workspace_bytes < emd_refine_nodes_index_workspace(num_out)))) {
+        emd_set_error("refine_nodes_index: bad argument"); return EMD_ERR_INVALID;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (n == 0 || num_out == 0) return segment_start ? emd_zero_async(segment_start, sizeof(int32_t) * ((size_t)a->num_actors + 1), st) : EMD_OK;
+    const dim3 grid((n + EMD_BLOCK - 1) / EMD_BLOCK), block(EMD_BLOCK);
+    if (!grouped) {
+        hipLaunchKernelGGL(k_refine_nodes_index, grid, block, 0, st, n, ns, num_out, code, a->ids, block_offsets, totals, src, kind, ids_out, split_rank, (uint32_t*)nullptr);
+        EMD_LAUNCH_CHECK();
+        return EMD_OK;
+    }
+    const size_t m = nodes_ws_align((size_t)num_out);
+    uint32_t* w = (uint32_t*)workspace;
+    RadixSortArgs r;
+    r.keys[0] = w; r.keys[1] = w + m; r.vals[0] = w + 2 * m; r.vals[1] = w + 3 * m;
+    int32_t *src_u = (int32_t*)(w + 4 * m), *kind_u = (int32_t*)(w + 5 * m);
+    r.hist = w + 6 * m;
+    r.n_cap = (size_t)num_out;
+    int bits = 1;
+    while (bits < 32 && ((uint32_t)(a->num_actors - 1) >> bits)) bits++;
+    r.bits = 9;
+    r.passes = (bits + 8) / 9;                                    // 1 up to 512 actors, 2 up to 65 536
+    hipLaunchKernelGGL(k_refine_nodes_index, grid, block, 0, st, n, ns, num_out, code, a->ids, block_offsets, totals, src_u, kind_u, (int32_t*)r.keys[0], (int32_t*)nullptr,
+                       r.vals[0]);
+    EMD_LAUNCH_CHECK();
+    const int buf = emd_launch_radix_sort(r, st);
+    if (buf < 0) return buf;
+    const int threads = num_out > a->num_actors + 1 ? num_out : a->num_actors + 1;
+    hipLaunchKernelGGL(k_refine_nodes_group, dim3((threads + EMD_BLOCK - 1) / EMD_BLOCK), block, 0, st, num_out, a->num_actors, (const uint32_t*)r.keys[buf],
+                       (const uint32_t*)r.vals[buf], (const int32_t*)src_u, (const int32_t*)kind_u, src, kind, ids_out, split_rank, segment_start);
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }

@@ -3,7 +3,9 @@
 `restructure_rows` runs decide -> scan -> ONE host read of the totals -> index -> ONE gather over an arbitrary set of per-point tensors, for
 S3Gaussian's densify / prune (EmdDensifyArgs) and for OmniRe's refinement (EmdRefineArgs) alike; `hand_over` points an optimiser group at the
 leaf that replaces its parameter and attaches the Adam moments that travelled with the rows.  The three stores (GaussianModel,
-VanillaGaussians, model.density_control) build their jobs, install the outputs on their own attributes and keep their own bookkeeping."""
+VanillaGaussians, model.density_control) build their jobs, install the outputs on their own attributes and keep their own bookkeeping.
+`restructure_node_rows` is the sibling for OmniRe's actor classes (nodes.RigidNodes / DeformableNodes): the REFINE event on rows that carry an
+actor id, with the per-box cull and the output rows grouped by actor (EmdRefineNodesArgs)."""
 import ctypes as C
 
 import torch
@@ -90,6 +92,76 @@ def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, sc
     L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
     del keep_alive
     return outs, counts
+
+
+def restructure_node_rows(args, jobs, N, samples=None, front_rows=0):
+    """One refinement event of an OmniRe ACTOR class (RigidNodes / DeformableNodes) on `N` rows that carry an actor id: the sibling of
+    `restructure_rows(REFINE)` with the per-box cull on the positions the gather stores and, with `args.group_by_actor`, the output rows grouped by
+    actor (include/emd_raster.h at EmdRefineNodesArgs).  `args`: an EmdRefineNodesArgs with the decision inputs, `means`, `scaling`, `rotation`,
+    `ids` (int32 [N]), `instances_size`, `num_actors`, `num_samples`, the two switches and `seed` filled; `samples` [num_samples, N, 3]: standard
+    normals by SOURCE ROW to use instead of the Philox draw; `jobs`, `front_rows`: as restructure_rows.
+    -> (outs or None when nothing changes, ids_out int32 [M], segment_start int32 [A + 1] (None when not grouped), counts) with counts =
+    (n_keep, n_dup, n_split, [n_samp_r]).  An id outside [0, num_actors) raises before anything is gathered.  The single host read is the totals."""
+    lib = L.load()
+    ns, A = int(args.num_samples), int(args.num_actors)
+    if N == 0:
+        return None, None, None, (0, 0, 0, [0] * ns)
+    dev = jobs[0][0].device
+    cols = 4 + ns
+    code = torch.empty(N, dtype=torch.int32, device=dev)
+    inc = torch.empty(cols, (N + 255) // 256, dtype=torch.int32, device=dev)
+    totals = torch.empty(cols, dtype=torch.int32, device=dev)
+    args.num_points = N
+    keep_alive = [code, inc, totals]
+    if samples is not None:
+        samples = samples.to(dev).float().contiguous()
+        assert samples.shape == (ns, N, 3), (tuple(samples.shape), ns, N)
+        args.samples = samples.data_ptr()
+        keep_alive.append(samples)
+    L.check(lib.emd_refine_nodes_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_refine_nodes_decide")
+    for c0 in range(0, cols, 8):                                   # emd_densify_scan takes at most 8 columns a call; columns are independent
+        L.check(lib.emd_densify_scan(N, min(8, cols - c0), inc[c0:].data_ptr(), totals[c0:].data_ptr(), _stream()), "emd_densify_scan")
+    t = [int(v) for v in totals.tolist()]
+    n_keep, n_dup, n_split, n_samp, n_bad = t[0], t[1], t[2], t[3:3 + ns], t[3 + ns]
+    if n_bad:
+        raise ValueError(f"{n_bad} point ids outside [0, {A})")
+    counts = (n_keep, n_dup, n_split, n_samp)
+    M = n_keep + sum(n_samp) + n_dup
+    if M == N and n_keep == N and n_split == 0:
+        return None, None, None, counts
+    grouped = bool(args.group_by_actor)
+    new = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    src, kind, ids_out = new(max(M, 1)), new(max(M, 1)), new(max(M, 1))
+    rank = new(max(M, 1)) if samples is not None else None
+    seg = new(A + 1) if grouped else None
+    ws_bytes = int(lib.emd_refine_nodes_index_workspace(M)) if grouped else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    L.check(lib.emd_refine_nodes_index(C.byref(args), M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), ids_out.data_ptr(),
+                                       L.ptr(seg), L.ptr(rank), L.ptr(ws), ws_bytes, _stream()), "emd_refine_nodes_index")
+    g = L.EmdDensifyGather()
+    g.num_out, g.mode, g.num_split = M, L.DENSIFY_MODE_REFINE, N
+    g.src, g.kind = src.data_ptr(), kind.data_ptr()
+    g.seed = args.seed
+    g.scaling, g.rotation = args.scaling, args.rotation
+    if samples is not None:
+        g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
+    keep_alive += [src, kind, rank, ws]
+    assert len(jobs) <= L.DENSIFY_MAX_TENSORS
+    outs = []
+    for k, (t_, role) in enumerate(jobs):
+        if t_.dtype != torch.float32 or not t_.is_contiguous():
+            t_ = t_.detach().float().contiguous()
+        assert t_.shape[0] == N
+        width = t_.numel() // N
+        out = torch.empty((front_rows + M,) + tuple(t_.shape[1:]), dtype=torch.float32, device=dev)
+        g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width = t_.data_ptr(), out.data_ptr() + 4 * width * front_rows, width
+        g.tensors[k].role = role
+        keep_alive.append(t_)
+        outs.append(out)
+    g.num_tensors = len(jobs)
+    L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
+    del keep_alive
+    return outs, ids_out[:M], seg, counts
 
 
 def hand_over(optimizer, group, param, moments=None):

@@ -158,6 +158,15 @@ class TrackOffsetHeads(torch.nn.Module):
             self._ids_key, self._ids_ref, self._ids32, self._cnt, self._seg = key, point_ids, ids32, cnt, seg
         return self._ids32, self._cnt, self._seg
 
+    def adopt_layout(self, point_ids, ids32, segment_start):
+        """Prime the cache `_prepare_ids` fills from the outputs of a refinement event that grouped its rows by actor (`RigidNodes._refine`):
+        `point_ids` the [n] tensor later calls will pass, `ids32` its int32 form, `segment_start` int32 [A+1] the first row of every actor.  The
+        per-actor counts are the differences of `segment_start`; no host read."""
+        seg = segment_start.to(torch.int32).contiguous()
+        assert seg.numel() == self.weight.shape[0] + 1 and ids32.dtype == torch.int32 and ids32.numel() == point_ids.numel()
+        key = (id(point_ids), point_ids._version, point_ids.data_ptr(), point_ids.numel(), point_ids.dtype)
+        self._ids_key, self._ids_ref, self._ids32, self._cnt, self._seg = key, point_ids, ids32.contiguous(), (seg[1:] - seg[:-1]).float(), seg
+
     def _time_and_k(self, frame, num_frames, step):
         # (frame - start_frame) / (end_frame - start_frame), rigid.py:204,241; a device frame index keeps the time on the device
         if isinstance(step, DeviceStep) and step.t is not None:

@@ -13,14 +13,20 @@ fused into its projection kernel and none of this is needed: EMD_FLAG_MOTION.)
 
 `vanilla_gaussians` is VanillaGaussians.get_gaussians (models/gaussians/vanilla.py:378-414), the class without a transform -- the Background,
 the large majority of a scene's Gaussians: the three activations and the SH colour in ONE launch each way (`emd_vanilla_forward` /
-`emd_vanilla_backward`, csrc/vanilla.hip), with `features_dc` and `features_rest` read where they are (no `torch.cat`)."""
+`emd_vanilla_backward`, csrc/vanilla.hip), with `features_dc` and `features_rest` read where they are (no `torch.cat`).
+
+`RigidNodes` / `DeformableNodes` are the actor classes as stores (models/nodes/rigid.py, deformable.py): `VanillaGaussians` plus the actor tables,
+`point_ids`, per-point embeddings, `get_gaussians` through the functions above, and the refinement event with the per-box cull and the rows
+grouped by actor (`density.restructure_node_rows`, csrc/densify.hip)."""
 import ctypes as C
 
 import torch
+from torch.nn import Parameter
 
 from . import _lib as L
 from .gsplat_api import spherical_harmonics
 from .motion import transform_gaussians
+from .vanilla import VanillaGaussians, _get
 
 
 def _check_finite(gs, step):
@@ -101,6 +107,196 @@ def deformable_gaussians(network, means, quats, opacity_logits, log_scales, feat
     if check_finite:
         _check_finite(gs, step)
     return gs
+
+
+class RigidNodes(VanillaGaussians):
+    """OmniRe's RigidNodes (models/nodes/rigid.py) as a store: the parent's six per-point parameters in the ACTOR's frame, `point_ids` [N,1] int64
+    (the reference's attribute; `ids32` is the int32 form the kernels read), the per-frame actor poses `instances_quats` [F,A,4] / `instances_trans`
+    [F,A,3] (Parameters), `instances_size` [A,3], `instances_fv` [F,A] bool, `cur_frame`, and -- with ctrl `gaussian_embedding_dim` > 0 -- the
+    per-point `_embeddings` [N,E] behind the learned track offsets of an attached `motion.TrackOffsetHeads`.
+
+    `refinement_after` is the parent's (schedule, opacity reset); the event itself is `density.restructure_node_rows`: the parent's decisions plus
+    ctrl `cull_out_of_bound` (default False: a row, a split sample at its sampled position included, is culled when it leaves its actor's box) and
+    ctrl `group_by_actor` (default True: the output rows are grouped by actor, so an actor's points stay contiguous for the whole run and
+    `segment_start` [A+1] is their table; the reference appends new rows at the end).  All parameters, `_embeddings` and both Adam moments of each
+    travel through the one gather; `point_ids`, `ids32` and `segment_start` come from the event's index stage; an attached `track_heads` adopts the
+    new layout without a host read.  The pose-smoothness regulariser of rigid.py:636-706 acts on the [F,A,3] tables of a few dozen actors and is left
+    to the trainer's torch code; `after_train` and `compute_reg_loss` are the parent's."""
+    # optimiser group (after the class prefix) -> attribute, beside the parent's six.  The reference file is not at hand: the names are kept in this one
+    # table (INTEGRATION.md says how to change them).
+    NODE_PARAM_GROUPS = {"ins_rotation": "instances_quats", "ins_translation": "instances_trans", "embedding": "_embeddings"}
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.point_ids = torch.zeros(1, 1, dtype=torch.int64, device=self.device)
+        self.ids32 = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._ids_flat = self.point_ids.reshape(-1)
+        self.instances_quats = self.instances_trans = self.instances_size = self.instances_fv = None
+        self._embeddings = None
+        self.segment_start = None
+        self.cur_frame = 0
+        self.track_heads = None
+
+    num_actors = property(lambda self: self.instances_size.shape[0])
+    num_frames = property(lambda self: self.instances_quats.shape[0])
+    embedding_dim = property(lambda self: int(_get(self.ctrl_cfg, "gaussian_embedding_dim", 0) or 0))
+
+    def create_from_tensors(self, means, colors, log_scales, point_ids, instances_quats, instances_trans, instances_size, instances_fv, quats=None,
+                            embeddings=None):
+        """The parent's `create_from_tensors` on points in the actors' frames, plus the actor tables.  point_ids [N] or [N,1], any integer type;
+        embeddings [N,E] (default zeros) when ctrl `gaussian_embedding_dim` = E > 0."""
+        super().create_from_tensors(means, colors, log_scales, quats=quats)
+        dev, n = self.device, means.shape[0]
+        self._set_ids(point_ids.to(dev).reshape(n).to(torch.int32).contiguous(), None)
+        self.instances_quats = Parameter(instances_quats.to(dev).float().contiguous())
+        self.instances_trans = Parameter(instances_trans.to(dev).float().contiguous())
+        self.instances_size = instances_size.to(dev).float().contiguous()
+        self.instances_fv = instances_fv.to(dev).bool().contiguous()
+        E = self.embedding_dim
+        if E > 0:
+            self._embeddings = Parameter((torch.zeros(n, E) if embeddings is None else embeddings).to(dev).float().reshape(n, E).contiguous())
+        if self.track_heads is not None:
+            self.track_heads.invalidate()
+
+    def _set_ids(self, ids32, segment_start):
+        self.ids32 = ids32
+        self.point_ids = ids32.to(torch.int64)[:, None]
+        self._ids_flat = self.point_ids.reshape(-1)                 # ONE object: the key of the track heads' layout cache
+        self.segment_start = segment_start
+
+    def attach_track_heads(self, heads):
+        self.track_heads = heads
+        if heads is not None:
+            heads.invalidate()
+
+    def set_cur_frame(self, frame):
+        self.cur_frame = frame
+
+    def get_param_groups(self):
+        groups = self.get_gaussian_param_groups()
+        for short, attr in self.NODE_PARAM_GROUPS.items():
+            if getattr(self, attr, None) is not None:
+                groups[self.class_prefix + short] = [getattr(self, attr)]
+        return groups
+
+    def get_out_of_bound_mask(self):
+        """[N] bool: |mean_c| > instances_size[id]_c / 2 for any c (the rows `cull_out_of_bound` removes at the next event)."""
+        return (self._means.detach().abs() > self.instances_size[self._ids_flat] / 2).any(dim=-1)
+
+    def _actor_pose(self):
+        from .motion import build_actor_pose
+        h = self.track_heads
+        if h is None:
+            return build_actor_pose(self.instances_quats, self.instances_trans, self.instances_fv, self.cur_frame, in_test_set=self.in_test_set)
+        if not self.in_test_set:
+            return h.pose_table(self.instances_quats, self.instances_trans, self.instances_fv, self.cur_frame, self._embeddings, self._ids_flat, self.step)
+        tt, tr = h(self.cur_frame, self.num_frames, self._embeddings, self._ids_flat, self.step)
+        return build_actor_pose(self.instances_quats, self.instances_trans, self.instances_fv, self.cur_frame, tt, tr, in_test_set=True)
+
+    def _node_kwargs(self, check_finite):
+        c = self.ctrl_cfg
+        return dict(sh_degree=self.sh_degree, step=self.step, sh_degree_interval=_get(c, "sh_degree_interval", 1000),
+                    check_finite=bool(_get(c, "check_finite", True)) if check_finite is None else check_finite,
+                    deterministic=bool(_get(c, "deterministic", False)))
+
+    def get_gaussians(self, cam, check_finite=None):
+        """rigid.py:570-615 through `rigid_gaussians`; the frame's pose table is `motion.build_actor_pose`, or `track_heads.pose_table` when a
+        `TrackOffsetHeads` is attached."""
+        self.filter_mask = torch.ones(self.num_points, dtype=torch.bool, device=self._means.device)
+        return rigid_gaussians(self._means, self._quats, self._opacities, self._scales, self._features_dc, self._features_rest, self.point_ids,
+                               self._actor_pose(), cam.camtoworlds[..., :3, 3], **self._node_kwargs(check_finite))
+
+    # ---- the refinement event -----------------------------------------------------------------------------------------------------------------
+    def _refine(self, optimizer, do_densify, do_cull, samples):
+        from .density import hand_over, restructure_node_rows
+        dev, c = self._means.device, self.ctrl_cfg
+        if dev.type != "cuda":
+            raise L.EmdError("RigidNodes.refinement_after needs tensors on a ROCm device; there is no CPU path")
+        N, ns = self.num_points, int(_get(c, "n_split_samples", 2))
+        a = L.EmdRefineNodesArgs()
+        a.num_points, a.do_densify, a.do_cull = N, int(do_densify), int(do_cull)
+        screen_on = self.step < _get(c, "stop_screen_size_at")
+        a.use_split_screen, a.cull_big, a.use_cull_screen = int(screen_on), int(self.step > _get(c, "reset_alpha_interval")), int(screen_on)
+        keep = [self._scales.detach().contiguous(), self._opacities.detach().reshape(-1).contiguous(), self._means.detach().contiguous(),
+                self._quats.detach().contiguous(), self.ids32.contiguous(), self.instances_size.contiguous()]
+        a.scaling, a.opacity, a.means, a.rotation, a.ids, a.instances_size = (t.data_ptr() for t in keep)
+        if self.max_2Dsize is not None:
+            keep.append(self.max_2Dsize.reshape(-1).float().contiguous())
+            a.max_2Dsize = keep[-1].data_ptr()
+        if do_densify:
+            keep += [self.xys_grad_norm.reshape(-1).float().contiguous(), self.vis_counts.reshape(-1).float().contiguous()]
+            a.grad_norm, a.vis_counts = keep[-2].data_ptr(), keep[-1].data_ptr()
+        # the host's products, rounded to float once (the reference compares float tensors with Python scalars)
+        a.grad_threshold, a.size_threshold = float(_get(c, "densify_grad_thresh")), float(_get(c, "densify_size_thresh") * self.scene_scale)
+        a.split_screen, a.cull_alpha = float(_get(c, "split_screen_size")), float(_get(c, "cull_alpha_thresh"))
+        a.cull_size, a.cull_screen = float(_get(c, "cull_scale_thresh") * self.scene_scale), float(_get(c, "cull_screen_size"))
+        a.num_actors, a.num_samples = self.num_actors, ns
+        a.cull_out_of_bound, a.group_by_actor = int(bool(_get(c, "cull_out_of_bound", False))), int(bool(_get(c, "group_by_actor", True)))
+        a.seed = (self.refine_seed * 0x9E3779B97F4A7C15 + self.refine_events) & 0xFFFFFFFFFFFFFFFF
+        attrs = {"xyz": ("_means", L.DENSIFY_ROLE_XYZ), "sh_dc": ("_features_dc", L.DENSIFY_ROLE_COPY), "sh_rest": ("_features_rest", L.DENSIFY_ROLE_COPY),
+                 "opacity": ("_opacities", L.DENSIFY_ROLE_COPY), "scaling": ("_scales", L.DENSIFY_ROLE_SCALING), "rotation": ("_quats", L.DENSIFY_ROLE_COPY)}
+        if self._embeddings is not None:
+            attrs["embedding"] = ("_embeddings", L.DENSIFY_ROLE_COPY)
+        groups = {grp["name"]: grp for grp in (optimizer.param_groups if optimizer is not None else [])
+                  if grp["name"].startswith(self.class_prefix) and grp["name"][len(self.class_prefix):] in attrs}
+        jobs, keys = [], []          # (source tensor, role), what the output becomes
+        for short, (attr, role) in attrs.items():
+            jobs.append((getattr(self, attr), role))
+            keys.append(("param", short))
+            grp = groups.get(self.class_prefix + short)
+            st = optimizer.state.get(grp["params"][0]) if grp is not None else None
+            if st:
+                jobs += [(st["exp_avg"], L.DENSIFY_ROLE_STATE), (st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)]
+                keys += [("moment", short)] * 2
+        outs, ids_out, seg, (n_keep, n_dup, n_split, n_samp) = restructure_node_rows(a, jobs, N, samples=samples)
+        del keep
+        info = {"n_before": N, "n_after": n_keep + sum(n_samp) + n_dup, "split": n_split, "originals_kept": n_keep, "samples_kept": sum(n_samp),
+                "dups_kept": n_dup}
+        if outs is None:
+            return info                                             # nothing split, duplicated or culled: every tensor stays as it is
+        moments = {}          # short name -> [exp_avg, exp_avg_sq]
+        for (what, short), out in zip(keys, outs):
+            if what == "param":
+                setattr(self, attrs[short][0], Parameter(out))
+            else:
+                moments.setdefault(short, []).append(out)
+        for name, grp in groups.items():
+            short = name[len(self.class_prefix):]
+            hand_over(optimizer, grp, getattr(self, attrs[short][0]), moments.get(short))
+        self._set_ids(ids_out.contiguous(), seg)
+        if self.track_heads is not None:
+            if seg is not None:
+                self.track_heads.adopt_layout(self._ids_flat, self.ids32, seg)
+            else:
+                self.track_heads.invalidate()
+        if do_densify:
+            self.refine_events += 1
+        return info
+
+
+class DeformableNodes(RigidNodes):
+    """OmniRe's DeformableNodes (models/nodes/deformable.py): RigidNodes whose canonical points take the learned residual of a
+    `deformation.ConditionalDeformNetwork` first.  `set_deformation` supplies the network, the per-actor `instances_embedding` [A,D] and the
+    frames' `normalized_timestamps` [F]; ctrl `use_deformation` (default True) and `stop_optimizing_canonical_xyz` (default True) as in the
+    reference.  The refinement event is the parent's."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.deform_network = self.instances_embedding = self.normalized_timestamps = None
+
+    def set_deformation(self, network, instances_embedding, normalized_timestamps):
+        self.deform_network = network
+        self.instances_embedding = instances_embedding if isinstance(instances_embedding, Parameter) else Parameter(instances_embedding.to(self.device).float().contiguous())
+        self.normalized_timestamps = normalized_timestamps.to(self.device).float()
+
+    def get_gaussians(self, cam, check_finite=None):
+        """deformable.py:49-114 through `deformable_gaussians`, the pose table as in RigidNodes."""
+        c = self.ctrl_cfg
+        self.filter_mask = torch.ones(self.num_points, dtype=torch.bool, device=self._means.device)
+        return deformable_gaussians(self.deform_network, self._means, self._quats, self._opacities, self._scales, self._features_dc, self._features_rest,
+                                    self.point_ids, self._actor_pose(), cam.camtoworlds[..., :3, 3], self.instances_size, self.instances_embedding,
+                                    self.normalized_timestamps[self.cur_frame].reshape(1), use_deformation=bool(_get(c, "use_deformation", True)),
+                                    stop_optimizing_canonical_xyz=bool(_get(c, "stop_optimizing_canonical_xyz", True)), **self._node_kwargs(check_finite))
 
 
 class _VanillaGaussians(torch.autograd.Function):

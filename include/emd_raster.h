@@ -1103,6 +1103,61 @@ int emd_densify_index(int32_t num_points, int32_t num_out, const int32_t* code, 
 int emd_densify_split_rank(int32_t num_out, int32_t n_keep, int32_t n_clone, int32_t n_split, int32_t* rank, void* hip_stream);
 int emd_densify_gather(const EmdDensifyGather* args, void* hip_stream);
 
+/* ---- ABI 31 extension (new entry points and one struct only, so the number stays): refinement of the OmniRe ACTOR classes ------------------
+ * RigidNodes / DeformableNodes.refinement_after (models/nodes/rigid.py:278-465): the event of EmdRefineArgs above on rows that carry an actor id,
+ * plus `cull_out_of_bound`: a row is culled when it leaves its actor's box.  The reference tests every row of the GROWN arrays, so a split
+ * sample at its new, sampled position: each replica lives or dies on its own (emd_refine_decide keeps one flag per source for all replicas).
+ * Decision, per source row i with actor a = ids[i]:
+ *   high, split, the in-place reduced scale, dup, faint, big, wide_old, wide_new: exactly the expressions of emd_refine_decide (same float operations)
+ *   oob(p)     = any_c |p_c| > instances_size[a][c] / 2     (NaN compares false, as in torch); active only when do_cull && cull_out_of_bound
+ *   original   : kept unless faint | big | wide_old | oob(mean_i)
+ *   duplicate  : dup and not (faint | big | wide_new | oob(mean_i))
+ *   sample r   : split and not (faint | big | wide_new | oob(p_r)), p_r = R(q^)(exp(scale) * n_r) + mean_i evaluated by the SAME device function the
+ *                gather stores positions with, on the same Philox key (seed, source row, replica) or the same caller-supplied normal: the position
+ *                that was tested is, bit for bit, the position that is stored.
+ *   Caller-supplied normals of this event are `samples` [num_samples, N, 3], indexed by SOURCE ROW (the rank among split sources is not known when
+ *   the decision runs): emd_refine_nodes_index writes split_rank[j] = source row on sample rows (0 elsewhere) and the gather is given num_split = N.
+ * Sequence:
+ *   emd_refine_nodes_decide -> code[N] (bit c = column c) and per-block counts of 4 + num_samples 0/1 columns: 0 original kept, 1 duplicate kept,
+ *                              2 source is split, 3 + r sample of replica r kept, 3 + num_samples id outside [0, num_actors)
+ *   emd_densify_scan        -> on those columns, at most 8 per call (columns are independent: a caller with more scans them in slices); the totals
+ *                              are the event's single host read.  A non-zero bad-id total means: gather nothing.
+ *   emd_refine_nodes_index  -> src[M], kind[M] (as emd_refine_index), ids_out[M] = ids[src], split_rank[M], M = keep + sum_r samp_r + dup
+ *       group_by_actor = 0: the reference's order: kept originals, kept samples of replica 0, 1, ..., kept duplicates, each in source order;
+ *                           segment_start may be NULL and is not written (N == 0 or M == 0: zeroed when given)
+ *       group_by_actor = 1: the STABLE sort of that order by actor id (the library's radix sort on the ids, ceil(bits(A - 1) / 9) passes), and
+ *                           segment_start[a] = first output row of actor a, segment_start[A] = M.  An actor left with no rows keeps an empty segment.
+ *                           Input ids may come in any order.  `workspace`: emd_refine_nodes_index_workspace(M) bytes of scratch.
+ *       No atomics on global memory, no host read; every argument is checked before anything is launched (num_actors 1..65536, num_samples 1..13,
+ *       the two switches 0 / 1); N == 0 returns EMD_OK with segment_start all zero.
+ *   emd_densify_gather      -> as it is, with EMD_DENSIFY_MODE_REFINE. */
+typedef struct EmdRefineNodesArgs {
+    /* the fields of EmdRefineArgs, same meaning */
+    int32_t num_points, do_densify, do_cull, use_split_screen, cull_big, use_cull_screen;
+    const float* scaling;
+    const float* opacity;
+    const float* grad_norm;
+    const float* vis_counts;
+    const float* max_2Dsize;
+    float grad_threshold, size_threshold, split_screen, cull_alpha, cull_size, cull_screen;
+    /* the actor part */
+    const float* means;            /* [N,3] source positions in the actor's frame */
+    const float* rotation;         /* [N,4] source quaternions */
+    const int32_t* ids;            /* [N] actor of every row */
+    const float* instances_size;   /* [A,3] box extents */
+    int32_t num_actors;            /* 1..65536 */
+    int32_t num_samples;           /* 1..13 */
+    int32_t cull_out_of_bound;     /* 0 / 1 */
+    int32_t group_by_actor;        /* 0 / 1 */
+    uint64_t seed;                 /* the Philox key the gather will use */
+    const float* samples;          /* [num_samples, N, 3] normals by source row to use instead of Philox, or NULL */
+} EmdRefineNodesArgs;
+int emd_refine_nodes_decide(const EmdRefineNodesArgs* args, int32_t* code /*[N]*/, int32_t* block_counts /*[4 + num_samples, ceil(N / 256)]*/, void* hip_stream);
+size_t emd_refine_nodes_index_workspace(int32_t num_out);
+int emd_refine_nodes_index(const EmdRefineNodesArgs* args, int32_t num_out, const int32_t* code, const int32_t* block_offsets /*[4 + num_samples, ceil(N / 256)]*/,
+                           const int32_t* totals /*[4 + num_samples]*/, int32_t* src, int32_t* kind, int32_t* ids_out, int32_t* segment_start /*[A + 1]*/,
+                           int32_t* split_rank /*[M] or NULL*/, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- Adam over all parameter tensors in one launch ---------------------------------------
  * Replaces optimizer.step() of `torch.optim.Adam(l, lr=0.0, eps=1e-15)` (S3Gaussian/scene/gaussian_model.py:188-201,
  * train.py:428; OmniRe builds the same optimiser per class, models/trainers/base.py:213-253): per element
