@@ -315,6 +315,12 @@ class EmdSkinArgs(C.Structure):
                 ("chunks", _f), ("world_means", _f), ("world_quats", _f), ("opacities_out", _f)]
 
 
+class EmdNeighbourStdArgs(C.Structure):
+    _fields_ = [("num_points", C.c_int32), ("k", C.c_int32), ("num_blocks", C.c_int32), ("reserved", C.c_int32), ("idx", _f), ("rev_start", _f),
+                ("rev_slot", _f), ("x", _f * 8), ("cols", C.c_int32 * 8), ("act", C.c_int32 * 8), ("weight", C.c_float * 8), ("stash", _f),
+                ("terms", _f), ("g_terms", _f), ("dx", _f * 8)]
+
+
 class EmdSkinGrads(C.Structure):
     _fields_ = [("g_world_means", _f), ("g_world_quats", _f), ("g_opacities_out", _f), ("d_means", _f), ("d_quats", _f), ("d_opacities", _f),
                 ("d_weights", _f), ("partials", _f)]
@@ -347,10 +353,13 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_temporal_embed_backward_det",
                     "emd_track_det_workspace_size", "emd_track_det_workspace_offsets", "emd_actor_row_sum_det", "emd_track_heads_forward_det",
                     "emd_track_heads_backward_det", "emd_tracked_pose_backward_det",
-                    "emd_vanilla_forward", "emd_vanilla_backward", "emd_vanilla_reg_workspace_size", "emd_vanilla_reg_forward", "emd_vanilla_reg_backward")
+                    "emd_vanilla_forward", "emd_vanilla_backward", "emd_vanilla_reg_workspace_size", "emd_vanilla_reg_forward", "emd_vanilla_reg_backward",
+                    "emd_knn_segments", "emd_neighbour_std_workspace_size", "emd_neighbour_std_forward", "emd_neighbour_std_backward")
 CAMERA_GRAD_FLOATS = 35
 KNN_MAX_K = 32
 EMBED_REG_SCRATCH_WORDS = 2048
+NSTD_MAX_BLOCKS, NSTD_MAX_COLS = 8, 64                     # EMD_NSTD_MAX_BLOCKS, EMD_NSTD_MAX_COLS
+NSTD_ACT = {"identity": 0, "exp": 1, "sigmoid": 2}         # EMD_NSTD_ACT_*
 PROF_STAGES = 8
 
 _lib = None
@@ -474,6 +483,10 @@ def load():
     lib.emd_knn_reverse.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_embed_reg_forward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7
     lib.emd_embed_reg_backward.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_int32, C.c_void_p]
+    lib.emd_knn_segments.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.emd_neighbour_std_workspace_size.argtypes, lib.emd_neighbour_std_workspace_size.restype = [], C.c_size_t
+    lib.emd_neighbour_std_forward.argtypes = [C.POINTER(EmdNeighbourStdArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.emd_neighbour_std_backward.argtypes = [C.POINTER(EmdNeighbourStdArgs), C.c_void_p]
     lib.emd_radix_sort.argtypes = [C.POINTER(EmdRadixSortArgs), C.c_void_p]
     lib.emd_raster_binning.argtypes = [C.POINTER(EmdBinningArgs), C.c_void_p]
     lib.emd_camera_grad_workspace_size.argtypes = [C.c_int32, C.POINTER(C.c_size_t)]

@@ -2,6 +2,8 @@
 //
 //   emd_knn                 distCUDA2 of create_from_pcd (k = 3, S3Gaussian/scene/gaussian_model.py:152-181) and the 20-neighbour table of the
 //                           fine stage's regulariser (o3d_knn, train.py:326-337)
+//   emd_knn_segments        the same contract inside segments (the instances of SMPLNodes: a pedestrian's neighbours are its own points): brute
+//                           force per segment, k_knn_segments below; no workspace
 //   emd_knn_reverse         the table's transposed adjacency (CSR), so that the regulariser's backward is a gather
 //   emd_embed_reg_forward   weighted_l2_loss_v2(e[:, None], e[idx], w) = mean sqrt(w |e_n - e_m|^2 + 1e-20)
 //   emd_embed_reg_backward  its gradient with respect to e, bit-identical from run to run
@@ -252,6 +254,61 @@ __global__ void __launch_bounds__(EMD_BLOCK) k_knn_search(int k, const uint32_t*
         }
     }
     if (mean_d2) mean_d2[__float_as_int(me.w)] = sum / (float)k;
+}
+
+// ---- search inside segments ----------------------------------------------------------------------------------------------------------------------
+// emd_knn_segments: row n's candidates are the other rows of n's own segment [segment_start[s], segment_start[s+1]).  Segments are people (6 890
+// points) or actors: small enough for brute force, so there is no sort and no workspace.  A wave owns 64 consecutive rows; each lane finds its own
+// range by binary search in the table, the wave walks the union of its lanes' ranges in ascending row order at a wave-uniform address (scalar
+// loads, as knn_scan_leaf), and a lane skips the candidates outside its own range and itself.  The ascending walk with knn_insert's strict `<`
+// puts the lower row first among equidistant candidates.  A candidate with a non-finite coordinate gives d = NaN or +inf: never `<` anything.
+template <int K>
+__global__ void __launch_bounds__(EMD_BLOCK) k_knn_segments(int N, int S, int k, const float* __restrict__ pts, const int32_t* __restrict__ segment_start,
+                                                            int32_t* __restrict__ idx, float* __restrict__ d2) {
+    const int row0 = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (EMD_BLOCK / 64) + (threadIdx.x >> 6))) * 64;
+    if (row0 >= N) return;                            // (uniform over the wave; the kernel has no workgroup barrier)
+    const int n = row0 + (int)(threadIdx.x & 63);
+    const bool in = n < N;
+    int lo = 0, hi = 0;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    if (in) {
+        // the last s in [0, S] whose clamped start is <= n (the table ascends); s == S or none: the row lies outside every segment
+        int a = 0, b = S + 1;
+        while (a < b) {
+            const int mid = (a + b) >> 1;
+            if (min(max(segment_start[mid], 0), N) <= n) a = mid + 1; else b = mid;
+        }
+        const int s = a - 1;
+        if (s >= 0 && s < S) { lo = min(max(segment_start[s], 0), N); hi = min(max(segment_start[s + 1], 0), N); }
+        qx = pts[3 * (size_t)n]; qy = pts[3 * (size_t)n + 1]; qz = pts[3 * (size_t)n + 2];
+        if (!finite3(qx, qy, qz)) lo = hi = 0;
+    }
+    const bool active = in && n >= lo && n < hi;
+    float dl[K];
+    int il[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) { dl[j] = INFINITY; il[j] = -1; }
+    int wlo = active ? lo : N, whi = active ? hi : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { wlo = min(wlo, __shfl_xor(wlo, o)); whi = max(whi, __shfl_xor(whi, o)); }
+    wlo = __builtin_amdgcn_readfirstlane(wlo);
+    whi = __builtin_amdgcn_readfirstlane(whi);
+    const int mylo = active ? lo : 0, myhi = active ? hi : 0;
+#pragma unroll 8
+    for (int m = wlo; m < whi; m++) {
+        const float px = pts[3 * (size_t)m], py = pts[3 * (size_t)m + 1], pz = pts[3 * (size_t)m + 2];
+        const float d = knn_dist2(qx - px, qy - py, qz - pz);
+        if (d < dl[K - 1] && m >= mylo && m < myhi && m != n) knn_insert<K>(dl, il, d, m);
+    }
+    if (!in) return;
+    const size_t row = (size_t)n * k;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        if (j < k) {
+            if (idx) idx[row + j] = il[j];
+            if (d2) d2[row + j] = dl[j];
+        }
+    }
 }
 
 // ---- transposed adjacency -----------------------------------------------------------------------------------------------------------------------
@@ -506,6 +563,25 @@ extern "C" int emd_knn(int32_t num_points, int32_t k, const float* pts, int32_t*
     else if (k <= 20) KNN_SEARCH(20);
     else KNN_SEARCH(32);
 #undef KNN_SEARCH
+    EMD_LAUNCH_CHECK();
+    return EMD_OK;
+}
+
+extern "C" int emd_knn_segments(int32_t num_points, int32_t num_segments, int32_t k, const float* pts, const int32_t* segment_start, int32_t* idx,
+                                float* d2, void* hip_stream) {
+    if (!knn_sizes_ok(num_points, k)) { emd_set_error("knn_segments: bad sizes (num_points=%d, k=%d; 1 <= k <= %d)", num_points, k, EMD_KNN_MAX_K); return EMD_ERR_INVALID; }
+    if (num_segments < 0 || num_segments >= INT32_MAX - 1) { emd_set_error("knn_segments: bad num_segments %d", num_segments); return EMD_ERR_INVALID; }
+    if (num_points == 0) return EMD_OK;
+    if (!pts || (!idx && !d2)) { emd_set_error("knn_segments: null points / no output"); return EMD_ERR_INVALID; }
+    if (!segment_start) { emd_set_error("knn_segments: null segment_start (it holds num_segments + 1 entries)"); return EMD_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const unsigned blocks = (unsigned)(((size_t)num_points + EMD_BLOCK - 1) / EMD_BLOCK);       // a wave per 64 consecutive rows
+#define KNN_SEG(KK) hipLaunchKernelGGL((k_knn_segments<KK>), dim3(blocks), dim3(EMD_BLOCK), 0, st, (int)num_points, (int)num_segments, (int)k, pts, segment_start, idx, d2)
+    if (k <= 3) KNN_SEG(3);
+    else if (k <= 8) KNN_SEG(8);
+    else if (k <= 20) KNN_SEG(20);
+    else KNN_SEG(32);
+#undef KNN_SEG
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }

@@ -17,7 +17,9 @@ the large majority of a scene's Gaussians: the three activations and the SH colo
 
 `RigidNodes` / `DeformableNodes` are the actor classes as stores (models/nodes/rigid.py, deformable.py): `VanillaGaussians` plus the actor tables,
 `point_ids`, per-point embeddings, `get_gaussians` through the functions above, and the refinement event with the per-box cull and the rows
-grouped by actor (`density.restructure_node_rows`, csrc/densify.hip)."""
+grouped by actor (`density.restructure_node_rows`, csrc/densify.hip).  `SMPLNodes` is the pedestrian class as a store
+(models/nodes/smpl.py): the pose Parameters, `get_gaussians` through `smpl_gaussians`, the k-NN table inside each instance and the neighbour-std
+regulariser `knn_reg` on it (`knn.KnnTable(segment_start=)`, `knn.neighbour_std`, csrc/neighbour_reg.hip)."""
 import ctypes as C
 
 import torch
@@ -124,7 +126,8 @@ class RigidNodes(VanillaGaussians):
     to the trainer's torch code; `after_train` and `compute_reg_loss` are the parent's."""
     # optimiser group (after the class prefix) -> attribute, beside the parent's six.  The reference file is not at hand: the names are kept in this one
     # table (INTEGRATION.md says how to change them).
-    NODE_PARAM_GROUPS = {"ins_rotation": "instances_quats", "ins_translation": "instances_trans", "embedding": "_embeddings"}
+    NODE_PARAM_GROUPS = {"ins_rotation": "instances_quats", "ins_translation": "instances_trans", "embedding": "_embeddings",
+                         "smpl_rotation": "smpl_quats"}          # (the last: SMPLNodes only; a class without the attribute has no such group)
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -297,6 +300,110 @@ class DeformableNodes(RigidNodes):
                                     self.point_ids, self._actor_pose(), cam.camtoworlds[..., :3, 3], self.instances_size, self.instances_embedding,
                                     self.normalized_timestamps[self.cur_frame].reshape(1), use_deformation=bool(_get(c, "use_deformation", True)),
                                     stop_optimizing_canonical_xyz=bool(_get(c, "stop_optimizing_canonical_xyz", True)), **self._node_kwargs(check_finite))
+
+
+class SMPLNodes(RigidNodes):
+    """OmniRe's SMPLNodes (models/nodes/smpl.py) as a store, the fourth class of `collect_gaussians`: the parent's six per-point parameters in the
+    CANONICAL frame of each person, the per-frame pose Parameters `instances_quats` [F,P,4] (global orientation), `smpl_quats` [F,P,23,4] and
+    `instances_trans` [F,P,3], and the buffers `joints` [P,24,3] (rest joints), `weights` [N,24] (skinning weights), `instances_fv` [F,P],
+    `instances_size` [P,3] and optionally `canon_inv` [P,24,12].  Loading the SMPL template, betas -> joints and the voxel deformer stay with the
+    caller: `create_from_tensors` takes their results.
+
+    The rows are grouped by instance for the whole run (sorted once at creation, stable; `segment_start` [P+1] built on the device), because the
+    class never changes its point set: `refinement_after` is the k-NN refresh every ctrl `knn_update_interval` (default 100) steps and nothing
+    else -- the reading of the reference taken here, which replaces the densification hook by that refresh.  `compute_reg_loss` adds `knn_reg`
+    (reg_cfg key `knn_reg` with `lambda_std_q`, `lambda_std_s`, `lambda_std_o`, `lambda_std_shs_dc`, `lambda_std_shs_rest`) to the parent's dict:
+    the sum of the five terms of ONE `knn.neighbour_std` node over the table of each point's ctrl `knn_neighbors` - 1 (default 3 - 1) nearest points
+    of the same person.  The reference's `x_offset`, voxel-deformer and temporal-smoothness terms are not built."""
+    # reg_cfg weight -> (attribute, activation of the values the reference takes the std of).  Which blocks are activated is a reading: change it here.
+    KNN_REG_BLOCKS = {"lambda_std_q": ("_quats", "identity"), "lambda_std_s": ("_scales", "exp"), "lambda_std_o": ("_opacities", "sigmoid"),
+                      "lambda_std_shs_dc": ("_features_dc", "identity"), "lambda_std_shs_rest": ("_features_rest", "identity")}
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.knn_neighbors < 2:
+            raise ValueError(f"SMPLNodes: knn_neighbors counts the point itself and must be at least 2, got {self.knn_neighbors}")
+        self.smpl_quats = self.joints = self.weights = self.canon_inv = None
+        self.skin_layout = self.knn_table = None
+
+    knn_neighbors = property(lambda self: int(_get(self.ctrl_cfg, "knn_neighbors", 3)))
+    knn_update_interval = property(lambda self: int(_get(self.ctrl_cfg, "knn_update_interval", 100)))
+
+    def create_from_tensors(self, means, colors, log_scales, point_ids, instances_quats, smpl_quats, instances_trans, instances_size, instances_fv,
+                            joints, weights, quats=None, canon_inv=None):
+        """Points in the persons' canonical frames with their instance ids [N] or [N,1] and skinning weights [N,24]; the rows are sorted by
+        instance here (stable), ids < 0 -- points bound to nobody -- first, outside every segment."""
+        from .smpl import SkinLayout
+        dev, n, P = self.device, means.shape[0], instances_size.shape[0]
+        ids = point_ids.to(dev).reshape(n).to(torch.int64)
+        order = torch.argsort(ids, stable=True)
+        row = lambda t: t.to(dev)[order]
+        super().create_from_tensors(row(means), row(colors), row(log_scales.reshape(n, -1)), ids[order], instances_quats, instances_trans,
+                                    instances_size, instances_fv, quats=None if quats is None else row(quats))
+        seg = torch.searchsorted(ids[order].contiguous(), torch.arange(P + 1, device=dev)).to(torch.int32)
+        self._set_ids(self.ids32, seg)
+        self.smpl_quats = Parameter(smpl_quats.to(dev).float().contiguous())
+        self.joints = joints.to(dev).float().contiguous()
+        self.weights = row(weights).float().contiguous()
+        self.canon_inv = None if canon_inv is None else canon_inv.to(dev).float().contiguous()
+        if self.smpl_quats.shape[:2] != self.instances_quats.shape[:2] or self.smpl_quats.shape[2:] != (23, 4):
+            raise ValueError(f"SMPLNodes: smpl_quats must be [F,P,23,4] beside instances_quats [F,P,4], got {tuple(self.smpl_quats.shape)}")
+        self.skin_layout = SkinLayout(P)                 # one layout for the whole run: the point set never changes
+        self.knn_table = None
+
+    def get_gaussians(self, cam, check_finite=None):
+        """models/nodes/smpl.py through `smpl_gaussians`: theta = (global orientation, the 23 body joints) of the current frame."""
+        f = self.cur_frame
+        self.filter_mask = torch.ones(self.num_points, dtype=torch.bool, device=self._means.device)
+        kw = self._node_kwargs(check_finite)
+        kw.pop("deterministic")                          # (the skinning has no other mode)
+        theta = torch.cat((self.instances_quats[f][:, None, :], self.smpl_quats[f]), dim=1)
+        return smpl_gaussians(self._means, self._quats, self._opacities, self._scales, self._features_dc, self._features_rest, self._ids_flat,
+                              self.weights, theta, self.joints, self.instances_trans[f], self.instances_fv[f], cam.camtoworlds[..., :3, 3],
+                              canon_inv=self.canon_inv, layout=self.skin_layout, **kw)
+
+    def update_knn(self):
+        """(Re)build the table of each point's `knn_neighbors` - 1 nearest points of the same instance (`knn.KnnTable` over `segment_start`)."""
+        from .knn import KnnTable
+        k = self.knn_neighbors - 1
+        if self.knn_table is None or self.knn_table.k != k:
+            self.knn_table = KnnTable(self._means, k=k, segment_start=self.segment_start)
+        else:
+            self.knn_table.refresh(self._means, segment_start=self.segment_start)
+        return self.knn_table
+
+    def postprocess_per_train_step(self, step, optimizer, radii, xys_grad, last_size):
+        self.after_train(radii, xys_grad, last_size)
+        self.refinement_after(step, optimizer)           # (its own interval: ctrl `refine_interval` plays no part)
+
+    def refinement_after(self, step, optimizer, samples=None):
+        """The k-NN refresh at every `knn_update_interval`-th step; the point set, `point_ids` and the optimiser are left as they are."""
+        assert step == self.step
+        if step % self.knn_update_interval == 0:
+            self.update_knn()
+        self.xys_grad_norm = self.vis_counts = self.max_2Dsize = None
+        return None
+
+    def compute_reg_loss(self):
+        """The parent's dict plus `knn_reg` when reg_cfg names it: the sum of the terms of one `neighbour_std` node (a block without rows -- SH
+        degree 0 has no `_features_rest` -- is dropped).  The table is built on first use and whenever its point count is stale."""
+        from .knn import neighbour_std
+        out = super().compute_reg_loss()
+        cfg = _get(self.reg_cfg, "knn_reg") if self.reg_cfg else None
+        if not cfg:
+            return out
+        blocks, acts, weights = [], [], []
+        for key, (attr, act) in self.KNN_REG_BLOCKS.items():
+            x = getattr(self, attr)
+            if x.numel() == 0 and self.num_points > 0:
+                continue
+            blocks.append(x)
+            acts.append(act)
+            weights.append(float(_get(cfg, key, 0.0) or 0.0))
+        if self.knn_table is None or self.knn_table.N != self.num_points:
+            self.update_knn()
+        out["knn_reg"] = neighbour_std(blocks, self.knn_table, weights, acts).sum()
+        return out
 
 
 class _VanillaGaussians(torch.autograd.Function):

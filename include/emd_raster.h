@@ -1587,6 +1587,63 @@ size_t emd_vanilla_reg_workspace_size(int32_t num_points);
 int emd_vanilla_reg_forward(const EmdVanillaRegArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
 int emd_vanilla_reg_backward(const EmdVanillaRegArgs* args, const void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- (ABI 31, compatible extension) SMPLNodes: k-NN inside segments and the neighbour-std regulariser ----------------------------------------
+ * The reference's smpl.py is not at hand; what follows is the maintainers' reading of its k-NN regulariser (reg.knn_reg, after GART), stated as
+ * formulas and pinned by tests/neighbour_std_ref.py (DESIGN.md section 8.19 names the points where the reading could be wrong).
+ *
+ * emd_knn_segments: emd_knn restricted to segments.  Segment s owns the rows [segment_start[s], segment_start[s+1]) of pts [N,3]; the table
+ * [S+1] ascends, lives on the device and is read there (no host read); its entries are clamped to [0, N].
+ *   - row n holds the k smallest d2(n,m) over the OTHER rows m of n's own segment, ascending, as GLOBAL row numbers; d2 is emd_knn's fp32
+ *     expression; self is excluded by index.
+ *   - among equidistant candidates the LOWER row number comes first (stricter than emd_knn).
+ *   - missing slots hold idx = -1, d2 = +inf: a segment of fewer than k + 1 rows (sizes 1 and 2 included), a row outside every segment, and a
+ *     row with a non-finite coordinate, which is also nobody's neighbour.
+ *   - deterministic; idx or d2 may be NULL (not both); 1 <= k <= EMD_KNN_MAX_K; every argument is validated before anything is launched and
+ *     N == 0 launches nothing.  No workspace, no sort, no atomics: brute force per segment, one wave per 64 consecutive rows. */
+int emd_knn_segments(int32_t num_points, int32_t num_segments, int32_t k, const float* pts, const int32_t* segment_start, int32_t* idx, float* d2,
+                     void* hip_stream);
+
+/* emd_neighbour_std_forward / _backward.  idx [N,k] holds the k = K - 1 OTHERS of every point's group (the point itself is implicit:
+ * knn_points(x, x, K) returns it first); entries outside [0, N) are empty slots.  Up to EMD_NSTD_MAX_BLOCKS blocks x_b [N,C_b] fp32 contiguous,
+ * 1 <= C_b <= EMD_NSTD_MAX_COLS, each with an activation a_b and a weight w_b.
+ * Forward.  G(n) = {n} u {idx[n,j] valid}, g = |G(n)|.  Per column c of block b, in fp32 and in this order:
+ *     v_m = a_b(x_b[m,c]);  d_m = v_m - v_n for m in the order n (d = 0), then ascending j;  mu = (sum d_m) / g;
+ *     sigma = sqrt(sum (d_m - mu)^2 / (g - 1)), the sum starting with the point's own term;  sigma = 0 when g < 2
+ *     terms[b] = w_b / (N C_b) * sum_n sum_c sigma        (= (a_b(x_b)[cat(self, idx)].std(dim=1).mean() * w_b)
+ * The shift by the group's first member is part of the contract: a group whose members are bit-identical in a column gives sigma == 0 exactly and
+ * a gradient of exactly 0 (a mean-first form would not: (x + x + x) / 3 != x in fp32).  exp is expf, sigmoid is 1 / (1 + expf(-x)); no fused
+ * multiply-adds.  The sigmas are added in fp64: per workgroup one partial per block, the partials in workgroup order by the last workgroup to
+ * arrive (an integer ticket; nobody waits).  One launch, no float atomics, no zero fill.  A block with w_b == 0 is SKIPPED: terms[b] = 0, its
+ * x / dx are not touched.  The forward leaves (mu, 1 / ((g - 1) sigma)) -- 0 where sigma is 0 -- per point and active column in `stash`
+ * ([N][T][2] floats, T = the columns of the blocks with w_b != 0, 8-byte aligned).
+ * Backward (a gather, one launch; every element of the active blocks' dx written exactly once):
+ *     dx_b[j,c] = a_b'(x_b[j,c]) * (g_terms[b] w_b / (N C_b)) * sum over the groups n containing j of (d^n_j - mu_n) / ((g_n - 1) sigma_n)
+ * with terms of sigma_n == 0 equal to 0 and the groups in the order n = j, then the owners of rev(j)'s slots (emd_knn_reverse) ascending.
+ * Values and gradients are fixed functions of the inputs: bit-identical from run to run, across streams and under graph replay.
+ * `workspace`: emd_neighbour_std_workspace_size() bytes, 8-byte aligned, its first 16 bytes zero at the first call and left zero by every call
+ * (one stream at a time).  N == 0 or no active block: terms are zeroed, nothing else is launched. */
+#define EMD_NSTD_MAX_BLOCKS 8
+#define EMD_NSTD_MAX_COLS 64
+#define EMD_NSTD_ACT_IDENTITY 0
+#define EMD_NSTD_ACT_EXP 1
+#define EMD_NSTD_ACT_SIGMOID 2
+typedef struct EmdNeighbourStdArgs {
+    int32_t num_points, k, num_blocks, reserved;
+    const int32_t* idx;                          /* [N,k] */
+    const int32_t* rev_start;                    /* backward: [N+1] */
+    const int32_t* rev_slot;                     /* backward: [N*k] */
+    const float* x[EMD_NSTD_MAX_BLOCKS];         /* [N,C_b] */
+    int32_t cols[EMD_NSTD_MAX_BLOCKS], act[EMD_NSTD_MAX_BLOCKS];
+    float weight[EMD_NSTD_MAX_BLOCKS];
+    float* stash;                                /* forward: written; backward: read */
+    float* terms;                                /* forward: [num_blocks] */
+    const float* g_terms;                        /* backward: [num_blocks], the upstream scalar of each term, on the device */
+    float* dx[EMD_NSTD_MAX_BLOCKS];              /* backward: [N,C_b] */
+} EmdNeighbourStdArgs;
+size_t emd_neighbour_std_workspace_size(void);
+int emd_neighbour_std_forward(const EmdNeighbourStdArgs* args, void* workspace, size_t workspace_bytes, void* hip_stream);
+int emd_neighbour_std_backward(const EmdNeighbourStdArgs* args, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
