@@ -1,20 +1,68 @@
-"""The one driver of a density-control event and the one optimiser handoff behind it (csrc/densify.hip).
+"""The host side of a density-control event (csrc/densify.hip): the two drivers, the rows that travel, and the optimiser handoff.
 
 `restructure_rows` runs decide -> scan -> ONE host read of the totals -> index -> ONE gather over an arbitrary set of per-point tensors, for
-S3Gaussian's densify / prune (EmdDensifyArgs) and for OmniRe's refinement (EmdRefineArgs) alike; `hand_over` points an optimiser group at the
-leaf that replaces its parameter and attaches the Adam moments that travelled with the rows.  The three stores (GaussianModel,
-VanillaGaussians, model.density_control) build their jobs, install the outputs on their own attributes and keep their own bookkeeping.
-`restructure_node_rows` is the sibling for OmniRe's actor classes (nodes.RigidNodes / DeformableNodes): the REFINE event on rows that carry an
-actor id, with the per-box cull and the output rows grouped by actor (EmdRefineNodesArgs)."""
+S3Gaussian's densify / prune (EmdDensifyArgs) and for OmniRe's refinement (EmdRefineArgs) alike.  `restructure_node_rows` is the sibling for
+OmniRe's actor classes (nodes.RigidNodes / DeformableNodes): the REFINE event on rows that carry an actor id, with the per-box cull and the
+output rows grouped by actor (EmdRefineNodesArgs).  The two differ in their decide and index calls only: `_decide_scan` is the head of both
+(allocation, decide, scan, the host read) and `_gather` the tail (how a list of jobs becomes one `emd_densify_gather`).
+
+`EventRows` is the one place that says which rows travel for a parameter and how the outputs return: a store registers its parameters (with
+their optimiser groups) and its other per-point rows, hands `jobs` to a driver, and gets the outputs back by key -- a parameter as a fresh leaf
+that its group already points at, with the Adam moments that travelled (`hand_over`).  GaussianModel, VanillaGaussians, the actor classes and
+model.density_control (on the rows behind the actors': `front_rows`) go through it and keep their own attributes and bookkeeping."""
 import ctypes as C
 
 import torch
+from torch.nn import Parameter
 
 from . import _lib as L
 
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _decide_scan(decide, args, N, cols, dev):
+    """The head of both drivers: the code / per-block count / totals arrays, the decide call `decide` (the name of the entry point that takes
+    `args`), the scan of the `cols` columns and the event's single host read -> (code, inc, totals, the totals as ints)."""
+    lib = L.load()
+    code = torch.empty(N, dtype=torch.int32, device=dev)
+    inc = torch.empty(cols, (N + 255) // 256, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
+    totals = torch.empty(cols, dtype=torch.int32, device=dev)
+    args.num_points = N
+    L.check(getattr(lib, decide)(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), decide)
+    for c0 in range(0, cols, 8):                                   # emd_densify_scan takes at most 8 columns a call; columns are independent
+        L.check(lib.emd_densify_scan(N, min(8, cols - c0), inc[c0:].data_ptr(), totals[c0:].data_ptr(), _stream()), "emd_densify_scan")
+    return code, inc, totals, [int(v) for v in totals.tolist()]
+
+
+def _gather(mode, M, num_split, src, kind, seed, scaling, rotation, samples, rank, jobs, N, front_rows):
+    """The tail of both drivers: ONE `emd_densify_gather` of `M` output rows over `jobs`.  `scaling` / `rotation`: device addresses (or None);
+    `samples` with `rank`: the recorded normals and the row of each output's draw, already float32 contiguous.  A job that is not float32
+    contiguous is converted here, so only when rows move; every output has `front_rows` spare rows in front.  -> the outputs, in job order."""
+    dev = src.device
+    g = L.EmdDensifyGather()
+    g.num_out, g.mode, g.num_split = M, mode, num_split
+    g.src, g.kind = src.data_ptr(), kind.data_ptr()
+    g.seed = seed
+    g.scaling, g.rotation = scaling, rotation
+    if samples is not None:
+        g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
+    assert len(jobs) <= L.DENSIFY_MAX_TENSORS
+    outs, converted = [], []                                       # (a converted source lives until the launch)
+    for k, (t, role) in enumerate(jobs):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.detach().float().contiguous()
+            converted.append(t)
+        assert t.shape[0] == N
+        width = t.numel() // N
+        out = torch.empty((front_rows + M,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+        g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width = t.data_ptr(), out.data_ptr() + 4 * width * front_rows, width
+        g.tensors[k].role = role
+        outs.append(out)
+    g.num_tensors = len(jobs)
+    L.check(L.load().emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
+    return outs
 
 
 def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, scaling=None, rotation=None, num_samples=2):
@@ -34,17 +82,10 @@ def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, sc
     if N == 0:
         return None, (0,) * cols
     dev = jobs[0][0].device
-    code = torch.empty(N, dtype=torch.int32, device=dev)
-    inc = torch.empty(cols, (N + 255) // 256, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
-    totals = torch.empty(cols, dtype=torch.int32, device=dev)
-    args.num_points = N
-    if refine:
-        L.check(lib.emd_refine_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_refine_decide")
-    else:
+    if not refine:
         args.mode = mode
-        L.check(lib.emd_densify_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_densify_decide")
-    L.check(lib.emd_densify_scan(N, cols, inc.data_ptr(), totals.data_ptr(), _stream()), "emd_densify_scan")
-    counts = tuple(int(v) for v in totals.tolist())
+    code, inc, totals, counts = _decide_scan("emd_refine_decide" if refine else "emd_densify_decide", args, N, cols, dev)
+    counts = tuple(counts)
     if refine:
         n_keep, n_dup, n_samp, n_split = counts
         M = n_keep + num_samples * n_samp + n_dup
@@ -65,32 +106,10 @@ def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, sc
         L.check(lib.emd_densify_index(N, M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), _stream()), "emd_densify_index")
         if rank is not None:
             L.check(lib.emd_densify_split_rank(M, n_keep, n_clone, n_split, rank.data_ptr(), _stream()), "emd_densify_split_rank")
-    g = L.EmdDensifyGather()
-    g.num_out, g.mode, g.num_split = M, mode, n_split
-    g.src, g.kind = src.data_ptr(), kind.data_ptr()
-    g.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    g.scaling, g.rotation = L.ptr(scaling), L.ptr(rotation)
-    keep_alive = [src, kind, code, inc, totals, scaling, rotation, rank]
     if samples is not None:
         samples = samples.to(dev).float().contiguous()
         assert samples.shape == (num_samples, n_split, 3), (tuple(samples.shape), num_samples, n_split)
-        g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
-        keep_alive.append(samples)
-    assert len(jobs) <= L.DENSIFY_MAX_TENSORS
-    outs = []
-    for k, (t, role) in enumerate(jobs):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            t = t.detach().float().contiguous()
-        assert t.shape[0] == N
-        width = t.numel() // N
-        out = torch.empty((front_rows + M,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
-        g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width = t.data_ptr(), out.data_ptr() + 4 * width * front_rows, width
-        g.tensors[k].role = role
-        keep_alive.append(t)
-        outs.append(out)
-    g.num_tensors = len(jobs)
-    L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
-    del keep_alive
+    outs = _gather(mode, M, n_split, src, kind, int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(scaling), L.ptr(rotation), samples, rank, jobs, N, front_rows)
     return outs, counts
 
 
@@ -107,21 +126,11 @@ def restructure_node_rows(args, jobs, N, samples=None, front_rows=0):
     if N == 0:
         return None, None, None, (0, 0, 0, [0] * ns)
     dev = jobs[0][0].device
-    cols = 4 + ns
-    code = torch.empty(N, dtype=torch.int32, device=dev)
-    inc = torch.empty(cols, (N + 255) // 256, dtype=torch.int32, device=dev)
-    totals = torch.empty(cols, dtype=torch.int32, device=dev)
-    args.num_points = N
-    keep_alive = [code, inc, totals]
-    if samples is not None:
+    if samples is not None:                                        # the decide stage applies the box test to the sampled positions
         samples = samples.to(dev).float().contiguous()
         assert samples.shape == (ns, N, 3), (tuple(samples.shape), ns, N)
         args.samples = samples.data_ptr()
-        keep_alive.append(samples)
-    L.check(lib.emd_refine_nodes_decide(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), "emd_refine_nodes_decide")
-    for c0 in range(0, cols, 8):                                   # emd_densify_scan takes at most 8 columns a call; columns are independent
-        L.check(lib.emd_densify_scan(N, min(8, cols - c0), inc[c0:].data_ptr(), totals[c0:].data_ptr(), _stream()), "emd_densify_scan")
-    t = [int(v) for v in totals.tolist()]
+    code, inc, totals, t = _decide_scan("emd_refine_nodes_decide", args, N, 4 + ns, dev)
     n_keep, n_dup, n_split, n_samp, n_bad = t[0], t[1], t[2], t[3:3 + ns], t[3 + ns]
     if n_bad:
         raise ValueError(f"{n_bad} point ids outside [0, {A})")
@@ -138,30 +147,52 @@ def restructure_node_rows(args, jobs, N, samples=None, front_rows=0):
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     L.check(lib.emd_refine_nodes_index(C.byref(args), M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), ids_out.data_ptr(),
                                        L.ptr(seg), L.ptr(rank), L.ptr(ws), ws_bytes, _stream()), "emd_refine_nodes_index")
-    g = L.EmdDensifyGather()
-    g.num_out, g.mode, g.num_split = M, L.DENSIFY_MODE_REFINE, N
-    g.src, g.kind = src.data_ptr(), kind.data_ptr()
-    g.seed = args.seed
-    g.scaling, g.rotation = args.scaling, args.rotation
-    if samples is not None:
-        g.samples, g.split_rank = samples.data_ptr(), rank.data_ptr()
-    keep_alive += [src, kind, rank, ws]
-    assert len(jobs) <= L.DENSIFY_MAX_TENSORS
-    outs = []
-    for k, (t_, role) in enumerate(jobs):
-        if t_.dtype != torch.float32 or not t_.is_contiguous():
-            t_ = t_.detach().float().contiguous()
-        assert t_.shape[0] == N
-        width = t_.numel() // N
-        out = torch.empty((front_rows + M,) + tuple(t_.shape[1:]), dtype=torch.float32, device=dev)
-        g.tensors[k].src, g.tensors[k].dst, g.tensors[k].width = t_.data_ptr(), out.data_ptr() + 4 * width * front_rows, width
-        g.tensors[k].role = role
-        keep_alive.append(t_)
-        outs.append(out)
-    g.num_tensors = len(jobs)
-    L.check(lib.emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
-    del keep_alive
+    outs = _gather(L.DENSIFY_MODE_REFINE, M, N, src, kind, args.seed, args.scaling, args.rotation, samples, rank, jobs, N, front_rows)
     return outs, ids_out[:M], seg, counts
+
+
+class EventRows:
+    """The rows of ONE store that travel through an event, and their way back.  `add_param(key, tensor, role, group)` registers a parameter and
+    its single-parameter optimiser group (None: it has none); `add(key, tensor, role)` any other per-point rows (statistics: ROLE_ZERO, tables:
+    ROLE_COPY).  `jobs` is the list a driver takes.  `install(outs)` returns {key: output}: a parameter comes back as a fresh leaf, and its group
+    has been pointed at it (`hand_over`).  The rule this class owns: the `exp_avg` / `exp_avg_sq` of a group travel right behind their parameter
+    as ROLE_STATE jobs when, and only when, the optimiser's state holds them, and return attached to the new leaf.  `front_rows`: as the
+    drivers' -- that many rows in front of every registered tensor take no part; `jobs` holds the rows behind them and `install` copies the
+    front rows over into the outputs."""
+
+    def __init__(self, optimizer=None, front_rows=0):
+        self.optimizer, self.front_rows, self.jobs = optimizer, front_rows, []
+        self._whole = []             # beside `jobs`: each tensor with its front rows
+        self._entries = []           # (key, index of the entry's first job, is a parameter, group, its moments travel)
+
+    def _job(self, tensor, role):
+        self._whole.append(tensor)
+        self.jobs.append((tensor.detach()[self.front_rows:] if self.front_rows else tensor, role))
+
+    def add(self, key, tensor, role):
+        self._entries.append((key, len(self.jobs), False, None, False))
+        self._job(tensor, role)
+
+    def add_param(self, key, tensor, role, group=None):
+        st = self.optimizer.state.get(group["params"][0]) if group is not None else None
+        travels = bool(st) and "exp_avg" in st
+        self._entries.append((key, len(self.jobs), True, group, travels))
+        self._job(tensor, role)
+        if travels:
+            self._job(st["exp_avg"], L.DENSIFY_ROLE_STATE)
+            self._job(st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)
+
+    def install(self, outs):
+        assert len(outs) == len(self.jobs)
+        if self.front_rows:
+            for out, whole in zip(outs, self._whole):
+                out[:self.front_rows].copy_(whole.detach()[:self.front_rows])
+        got = {}
+        for key, k, is_param, group, travels in self._entries:
+            got[key] = Parameter(outs[k]) if is_param else outs[k]
+            if group is not None:
+                hand_over(self.optimizer, group, got[key], (outs[k + 1], outs[k + 2]) if travels else None)
+        return got
 
 
 def hand_over(optimizer, group, param, moments=None):

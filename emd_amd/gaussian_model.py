@@ -35,7 +35,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .density import hand_over, restructure_rows
+from .density import EventRows, hand_over, restructure_rows
 from .optim import Adam, expon_lr
 
 SH_C0 = 0.28209479177387814
@@ -323,10 +323,6 @@ class GaussianModel:
         dp.add_densification_stats(viewspace_point_tensor_grad, radii, self.xyz_gradient_accum, self.denom, self.max_radii2D)
 
     # ---- device-side surgery ---------------------------------------------------------------------------------------------------------
-    def _state(self, group):
-        st = self.optimizer.state.get(group["params"][0], None) if self.optimizer is not None else None
-        return st if st else None
-
     def _point_groups(self):
         if self.optimizer is None:
             return {}
@@ -337,25 +333,18 @@ class GaussianModel:
         N = self._xyz.shape[0]
         if N == 0:
             return 0, 0, 0
-        jobs, keys = [], []          # (source tensor, role), what the output becomes
+        rows = EventRows(self.optimizer)          # keyed by attribute
         roles = {"xyz": L.DENSIFY_ROLE_XYZ, "scaling": L.DENSIFY_ROLE_SCALING}
         groups = self._point_groups()
         for name in self.GROUPS:
-            jobs.append((getattr(self, self._ATTR[name]), roles.get(name, L.DENSIFY_ROLE_COPY)))
-            keys.append(("param", name))
-            st = self._state(groups[name]) if name in groups else None
-            if st is not None:
-                jobs += [(st["exp_avg"], L.DENSIFY_ROLE_STATE), (st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)]
-                keys += [("moment", name)] * 2
+            rows.add_param(self._ATTR[name], getattr(self, self._ATTR[name]), roles.get(name, L.DENSIFY_ROLE_COPY), groups.get(name))
         for attr in ("xyz_gradient_accum", "denom", "max_radii2D"):
             t = getattr(self, attr)
             if t.dim() >= 1 and t.shape[0] == N:
-                jobs.append((t, L.DENSIFY_ROLE_ZERO))
-                keys.append(("stat", attr))
-        jobs.append((self._deformation_table, L.DENSIFY_ROLE_COPY))          # travels as float (the driver converts it once rows do move)
-        keys.append(("table", None))
+                rows.add(attr, t, L.DENSIFY_ROLE_ZERO)
+        rows.add("_deformation_table", self._deformation_table, L.DENSIFY_ROLE_COPY)          # travels as float (the driver converts it once rows do move)
         seed = self.densify_seed * 0x9E3779B97F4A7C15 + self.densify_events
-        outs, (n_keep, n_clone, n_split) = restructure_rows(mode, args, jobs, N, seed=seed, samples=samples, scaling=self._scaling.detach(),
+        outs, (n_keep, n_clone, n_split) = restructure_rows(mode, args, rows.jobs, N, seed=seed, samples=samples, scaling=self._scaling.detach(),
                                                             rotation=self._rotation.detach())
         if outs is None:
             if mode == L.DENSIFY_MODE_DENSIFY:
@@ -366,18 +355,8 @@ class GaussianModel:
                         t.zero_()
             return n_keep, 0, 0
         # install the new tensors: parameters become fresh leaves, the optimiser keeps its groups and per-parameter state
-        moments = {}          # group name -> [exp_avg, exp_avg_sq]
-        for (what, name), out in zip(keys, outs):
-            if what == "param":
-                setattr(self, self._ATTR[name], nn.Parameter(out.requires_grad_(True)))
-            elif what == "moment":
-                moments.setdefault(name, []).append(out)
-            elif what == "stat":
-                setattr(self, name, out)
-            else:
-                self._deformation_table = out > 0.5
-        for name, grp in groups.items():
-            hand_over(self.optimizer, grp, getattr(self, self._ATTR[name]), moments.get(name))
+        for attr, out in rows.install(outs).items():
+            setattr(self, attr, out > 0.5 if attr == "_deformation_table" else out)
         if mode == L.DENSIFY_MODE_DENSIFY:
             self.densify_events += 1
         self._knn_table = None                     # the rows moved: the cached neighbour table describes another point set

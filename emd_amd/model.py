@@ -94,7 +94,7 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
     `cat_tensors_to_optimizer` / `_prune_optimizer` do (gaussian_model.py:454-500); the actors' rows keep theirs.  WITHOUT it a caller's optimizer
     still points at the old tensors and must be rebuilt (its state for these five parameters is lost)."""
     from . import _lib as L
-    from .density import hand_over, restructure_rows
+    from .density import EventRows, restructure_rows
     dev, N = model._xyz.device, model._xyz.shape[0]
     if dev.type != "cuda":
         raise L.EmdError("density_control needs the store on a ROCm device; there is no CPU path")
@@ -110,38 +110,30 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
             for nm in names:
                 if len(grp["params"]) == 1 and grp["params"][0] is getattr(model, nm):
                     groups[nm] = grp
-    state = {nm: optimizer.state.get(getattr(model, nm)) for nm in groups}
-    # the rows that take part: views of the background rows (a dim-0 slice of a contiguous tensor is contiguous: no copy)
-    cur = {nm: getattr(model, nm).detach() for nm in names}
-    mom = {(nm, k): state[nm][k].detach() for nm in groups if state[nm] and "exp_avg" in state[nm] for k in ("exp_avg", "exp_avg_sq")}
     stats = [xyz_gradient_accum.reshape(N, 1), denom.reshape(N, 1), max_radii2D.reshape(N)]
-    full = {k: v for k, v in cur.items()}
     counts = {"cloned": 0, "split": 0, "pruned": 0}
     seed_word = (int(seed) * 0x9E3779B97F4A7C15 + int(event)) & 0xFFFFFFFFFFFFFFFF
     with torch.no_grad():
         for mode in (L.DENSIFY_MODE_DENSIFY, L.DENSIFY_MODE_PRUNE):
-            n_rows = full["_xyz"].shape[0]
-            nb = n_rows - n_dyn
-            bg = lambda t: t[n_dyn:]
+            nb = model._xyz.shape[0] - n_dyn
+            # the rows that take part: views of the background rows (a dim-0 slice of a contiguous tensor is contiguous: no copy)
+            bg = lambda t: t.detach()[n_dyn:]
             a = L.EmdDensifyArgs()
-            a.scaling = bg(full["_scaling"]).data_ptr()
+            a.scaling = bg(model._scaling).data_ptr()
             if mode == L.DENSIFY_MODE_DENSIFY:
                 a.grad_accum, a.denom = bg(stats[0]).data_ptr(), bg(stats[1]).data_ptr()
                 a.grad_threshold, a.size_threshold = float(max_grad), float(percent_dense * extent)       # the double product, rounded to float once
             else:
-                a.opacity, a.max_radii2D = bg(full["_opacity"]).data_ptr(), bg(stats[2]).data_ptr()
+                a.opacity, a.max_radii2D = bg(model._opacity).data_ptr(), bg(stats[2]).data_ptr()
                 a.min_opacity, a.size_threshold = float(min_opacity), float(0.1 * extent)
                 a.max_screen_size = float(max_screen_size) if max_screen_size else 0.0
-            jobs = [(bg(full[nm]), roles[nm]) for nm in names]
-            keys = [("param", nm) for nm in names]
-            for (nm, k), t in mom.items():
-                jobs.append((bg(t), L.DENSIFY_ROLE_STATE))
-                keys.append(("mom", (nm, k)))
-            for i_, t in enumerate(stats):
-                jobs.append((bg(t), L.DENSIFY_ROLE_ZERO))
-                keys.append(("stat", i_))
-            outs, (n_keep, n_clone, n_split) = restructure_rows(mode, a, jobs, nb, seed=seed_word, front_rows=n_dyn, scaling=bg(full["_scaling"]),
-                                                                rotation=bg(full["_rotation"]))
+            rows = EventRows(optimizer, front_rows=n_dyn)          # keyed by attribute, a statistic by its place in `stats`
+            for nm in names:
+                rows.add_param(nm, getattr(model, nm), roles[nm], groups.get(nm))
+            for k, t in enumerate(stats):
+                rows.add(k, t, L.DENSIFY_ROLE_ZERO)
+            outs, (n_keep, n_clone, n_split) = restructure_rows(mode, a, rows.jobs, nb, seed=seed_word, front_rows=n_dyn, scaling=bg(model._scaling),
+                                                                rotation=bg(model._rotation))
             if mode == L.DENSIFY_MODE_DENSIFY:
                 counts["cloned"], counts["split"] = n_clone, n_split
                 if outs is None:          # nothing selected: the reference's densification_postfix still clears the statistics (gaussian_model.py:526-530)
@@ -150,24 +142,13 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
             else:
                 counts["pruned"] = nb - n_keep
             if outs is None:
-                continue
-            for (what, key), (t_old, _), out in zip(keys, jobs, outs):
-                if what == "param":
-                    out[:n_dyn].copy_(full[key][:n_dyn])
-                    full[key] = out
-                elif what == "mom":
-                    out[:n_dyn].copy_(mom[key][:n_dyn])
-                    mom[key] = out
+                continue                  # (no parameter object is replaced)
+            for key, out in rows.install(outs).items():          # the actors' rows in front are copied over from the old tensors
+                if key in roles:
+                    setattr(model, key, out)
                 else:
-                    out[:n_dyn].copy_(stats[key][:n_dyn])
                     stats[key] = out
-        n_new = full["_xyz"].shape[0] - n_dyn
-        for nm in names:
-            old = getattr(model, nm)
-            new = torch.nn.Parameter(full[nm]) if full[nm] is not cur[nm] else old
-            if nm in groups and new is not old:
-                hand_over(optimizer, groups[nm], new, (mom[(nm, "exp_avg")], mom[(nm, "exp_avg_sq")]) if (nm, "exp_avg") in mom else None)
-            setattr(model, nm, new)
+        n_new = model._xyz.shape[0] - n_dyn
         if model.has_actors:
             model.actor_id = torch.cat([model.actor_id[:n_dyn], torch.full((n_new,), -1, dtype=model.actor_id.dtype, device=dev)])
     model._zero_xyz = None

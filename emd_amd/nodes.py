@@ -117,8 +117,10 @@ class RigidNodes(VanillaGaussians):
     [F,A,3] (Parameters), `instances_size` [A,3], `instances_fv` [F,A] bool, `cur_frame`, and -- with ctrl `gaussian_embedding_dim` > 0 -- the
     per-point `_embeddings` [N,E] behind the learned track offsets of an attached `motion.TrackOffsetHeads`.
 
-    `refinement_after` is the parent's (schedule, opacity reset); the event itself is `density.restructure_node_rows`: the parent's decisions plus
-    ctrl `cull_out_of_bound` (default False: a row, a split sample at its sampled position included, is culled when it leaves its actor's box) and
+    `refinement_after` and the event's body `_refine` are the parent's (schedule, opacity reset, the rows that travel, their install); the class
+    overrides the four hooks of that body -- `_refine_args` (the actor part of an EmdRefineNodesArgs behind the parent's fill), `_refine_attrs`
+    (`_embeddings`), `_refine_rows` and `_after_refine` (ids, segment table, track heads).  The driver is `density.restructure_node_rows`: the
+    parent's decisions plus ctrl `cull_out_of_bound` (default False: a row, a split sample at its sampled position included, is culled when it leaves its actor's box) and
     ctrl `group_by_actor` (default True: the output rows are grouped by actor, so an actor's points stay contiguous for the whole run and
     `segment_start` [A+1] is their table; the reference appends new rows at the end).  All parameters, `_embeddings` and both Adam moments of each
     travel through the one gather; `point_ids`, `ids32` and `segment_start` come from the event's index stage; an attached `track_heads` adopts the
@@ -210,71 +212,36 @@ class RigidNodes(VanillaGaussians):
                                self._actor_pose(), cam.camtoworlds[..., :3, 3], **self._node_kwargs(check_finite))
 
     # ---- the refinement event -----------------------------------------------------------------------------------------------------------------
-    def _refine(self, optimizer, do_densify, do_cull, samples):
-        from .density import hand_over, restructure_node_rows
-        dev, c = self._means.device, self.ctrl_cfg
-        if dev.type != "cuda":
-            raise L.EmdError("RigidNodes.refinement_after needs tensors on a ROCm device; there is no CPU path")
-        N, ns = self.num_points, int(_get(c, "n_split_samples", 2))
-        a = L.EmdRefineNodesArgs()
-        a.num_points, a.do_densify, a.do_cull = N, int(do_densify), int(do_cull)
-        screen_on = self.step < _get(c, "stop_screen_size_at")
-        a.use_split_screen, a.cull_big, a.use_cull_screen = int(screen_on), int(self.step > _get(c, "reset_alpha_interval")), int(screen_on)
-        keep = [self._scales.detach().contiguous(), self._opacities.detach().reshape(-1).contiguous(), self._means.detach().contiguous(),
-                self._quats.detach().contiguous(), self.ids32.contiguous(), self.instances_size.contiguous()]
-        a.scaling, a.opacity, a.means, a.rotation, a.ids, a.instances_size = (t.data_ptr() for t in keep)
-        if self.max_2Dsize is not None:
-            keep.append(self.max_2Dsize.reshape(-1).float().contiguous())
-            a.max_2Dsize = keep[-1].data_ptr()
-        if do_densify:
-            keep += [self.xys_grad_norm.reshape(-1).float().contiguous(), self.vis_counts.reshape(-1).float().contiguous()]
-            a.grad_norm, a.vis_counts = keep[-2].data_ptr(), keep[-1].data_ptr()
-        # the host's products, rounded to float once (the reference compares float tensors with Python scalars)
-        a.grad_threshold, a.size_threshold = float(_get(c, "densify_grad_thresh")), float(_get(c, "densify_size_thresh") * self.scene_scale)
-        a.split_screen, a.cull_alpha = float(_get(c, "split_screen_size")), float(_get(c, "cull_alpha_thresh"))
-        a.cull_size, a.cull_screen = float(_get(c, "cull_scale_thresh") * self.scene_scale), float(_get(c, "cull_screen_size"))
-        a.num_actors, a.num_samples = self.num_actors, ns
+    # (the body is the parent's `_refine`; these four say what an actor class adds)
+    def _refine_args(self, do_densify, do_cull):
+        c = self.ctrl_cfg
+        a, keep = super()._refine_args(do_densify, do_cull, L.EmdRefineNodesArgs())          # (its first fields are EmdRefineArgs's)
+        actor = [self._means.detach().contiguous(), self._quats.detach().contiguous(), self.ids32.contiguous(), self.instances_size.contiguous()]
+        a.means, a.rotation, a.ids, a.instances_size = (t.data_ptr() for t in actor)
+        a.num_actors, a.num_samples = self.num_actors, int(_get(c, "n_split_samples", 2))
         a.cull_out_of_bound, a.group_by_actor = int(bool(_get(c, "cull_out_of_bound", False))), int(bool(_get(c, "group_by_actor", True)))
         a.seed = (self.refine_seed * 0x9E3779B97F4A7C15 + self.refine_events) & 0xFFFFFFFFFFFFFFFF
-        attrs = {"xyz": ("_means", L.DENSIFY_ROLE_XYZ), "sh_dc": ("_features_dc", L.DENSIFY_ROLE_COPY), "sh_rest": ("_features_rest", L.DENSIFY_ROLE_COPY),
-                 "opacity": ("_opacities", L.DENSIFY_ROLE_COPY), "scaling": ("_scales", L.DENSIFY_ROLE_SCALING), "rotation": ("_quats", L.DENSIFY_ROLE_COPY)}
+        return a, keep + actor
+
+    def _refine_attrs(self):
+        attrs = super()._refine_attrs()
         if self._embeddings is not None:
             attrs["embedding"] = ("_embeddings", L.DENSIFY_ROLE_COPY)
-        groups = {grp["name"]: grp for grp in (optimizer.param_groups if optimizer is not None else [])
-                  if grp["name"].startswith(self.class_prefix) and grp["name"][len(self.class_prefix):] in attrs}
-        jobs, keys = [], []          # (source tensor, role), what the output becomes
-        for short, (attr, role) in attrs.items():
-            jobs.append((getattr(self, attr), role))
-            keys.append(("param", short))
-            grp = groups.get(self.class_prefix + short)
-            st = optimizer.state.get(grp["params"][0]) if grp is not None else None
-            if st:
-                jobs += [(st["exp_avg"], L.DENSIFY_ROLE_STATE), (st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)]
-                keys += [("moment", short)] * 2
+        return attrs
+
+    def _refine_rows(self, a, keep, jobs, N, samples):
+        from .density import restructure_node_rows
         outs, ids_out, seg, (n_keep, n_dup, n_split, n_samp) = restructure_node_rows(a, jobs, N, samples=samples)
-        del keep
-        info = {"n_before": N, "n_after": n_keep + sum(n_samp) + n_dup, "split": n_split, "originals_kept": n_keep, "samples_kept": sum(n_samp),
-                "dups_kept": n_dup}
-        if outs is None:
-            return info                                             # nothing split, duplicated or culled: every tensor stays as it is
-        moments = {}          # short name -> [exp_avg, exp_avg_sq]
-        for (what, short), out in zip(keys, outs):
-            if what == "param":
-                setattr(self, attrs[short][0], Parameter(out))
-            else:
-                moments.setdefault(short, []).append(out)
-        for name, grp in groups.items():
-            short = name[len(self.class_prefix):]
-            hand_over(optimizer, grp, getattr(self, attrs[short][0]), moments.get(short))
+        return outs, (n_keep, n_dup, sum(n_samp), n_split), (ids_out, seg)
+
+    def _after_refine(self, layout):
+        ids_out, seg = layout
         self._set_ids(ids_out.contiguous(), seg)
         if self.track_heads is not None:
             if seg is not None:
                 self.track_heads.adopt_layout(self._ids_flat, self.ids32, seg)
             else:
                 self.track_heads.invalidate()
-        if do_densify:
-            self.refine_events += 1
-        return info
 
 
 class DeformableNodes(RigidNodes):

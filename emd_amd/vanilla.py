@@ -32,7 +32,7 @@ import torch
 from torch.nn import Parameter
 
 from . import _lib as L
-from .density import hand_over, restructure_rows
+from .density import EventRows, restructure_rows
 
 SH_C0 = 0.28209479177387814
 
@@ -266,12 +266,32 @@ class VanillaGaussians(torch.nn.Module):
         return info
 
     def _refine(self, optimizer, do_densify, do_cull, samples):
-        dev, c = self._means.device, self.ctrl_cfg
-        if dev.type != "cuda":
-            raise L.EmdError("VanillaGaussians.refinement_after needs tensors on a ROCm device; there is no CPU path")
-        N, ns = self.num_points, int(_get(c, "n_split_samples", 2))
-        a = L.EmdRefineArgs()
-        a.num_points, a.do_densify, a.do_cull = N, int(do_densify), int(do_cull)
+        """The event's body, once for every class: args -> the rows that travel (`density.EventRows`) -> the driver -> install.  A class states what
+        differs in `_refine_args`, `_refine_attrs`, `_refine_rows` and `_after_refine`."""
+        if self._means.device.type != "cuda":
+            raise L.EmdError(f"{type(self).__name__}.refinement_after needs tensors on a ROCm device; there is no CPU path")
+        N, prefix = self.num_points, self.class_prefix
+        a, keep = self._refine_args(do_densify, do_cull)
+        groups = {grp["name"]: grp for grp in (optimizer.param_groups if optimizer is not None else [])}
+        rows = EventRows(optimizer)
+        for short, (attr, role) in self._refine_attrs().items():
+            rows.add_param(attr, getattr(self, attr), role, groups.get(prefix + short))
+        outs, (n_keep, n_dup, n_samp, n_split), layout = self._refine_rows(a, keep, rows.jobs, N, samples)
+        info = {"n_before": N, "n_after": n_keep + n_samp + n_dup, "split": n_split, "originals_kept": n_keep, "samples_kept": n_samp, "dups_kept": n_dup}
+        if outs is None:
+            return info                                             # nothing split, duplicated or culled: every tensor stays as it is
+        for attr, param in rows.install(outs).items():
+            setattr(self, attr, param)
+        self._after_refine(layout)
+        if do_densify:
+            self.refine_events += 1
+        return info
+
+    def _refine_args(self, do_densify, do_cull, a=None):
+        """-> (the decision inputs on `a`, default a new EmdRefineArgs; the tensors its pointers need alive, the contiguous log-scales first)"""
+        c = self.ctrl_cfg
+        a = L.EmdRefineArgs() if a is None else a
+        a.num_points, a.do_densify, a.do_cull = self.num_points, int(do_densify), int(do_cull)
         screen_on = self.step < _get(c, "stop_screen_size_at")
         a.use_split_screen, a.cull_big, a.use_cull_screen = int(screen_on), int(self.step > _get(c, "reset_alpha_interval")), int(screen_on)
         keep = [self._scales.detach().contiguous(), self._opacities.detach().reshape(-1).contiguous()]
@@ -286,35 +306,20 @@ class VanillaGaussians(torch.nn.Module):
         a.grad_threshold, a.size_threshold = float(_get(c, "densify_grad_thresh")), float(_get(c, "densify_size_thresh") * self.scene_scale)
         a.split_screen, a.cull_alpha = float(_get(c, "split_screen_size")), float(_get(c, "cull_alpha_thresh"))
         a.cull_size, a.cull_screen = float(_get(c, "cull_scale_thresh") * self.scene_scale), float(_get(c, "cull_screen_size"))
-        attrs = {"xyz": ("_means", L.DENSIFY_ROLE_XYZ), "sh_dc": ("_features_dc", L.DENSIFY_ROLE_COPY), "sh_rest": ("_features_rest", L.DENSIFY_ROLE_COPY),
-                 "opacity": ("_opacities", L.DENSIFY_ROLE_COPY), "scaling": ("_scales", L.DENSIFY_ROLE_SCALING), "rotation": ("_quats", L.DENSIFY_ROLE_COPY)}
-        groups = {grp["name"]: grp for grp in (optimizer.param_groups if optimizer is not None else [])
-                  if grp["name"].startswith(self.class_prefix) and grp["name"][len(self.class_prefix):] in attrs}
-        jobs, keys = [], []          # (source tensor, role), what the output becomes
-        for short, (attr, role) in attrs.items():
-            jobs.append((getattr(self, attr), role))
-            keys.append(("param", short))
-            grp = groups.get(self.class_prefix + short)
-            st = optimizer.state.get(grp["params"][0]) if grp is not None else None
-            if st:
-                jobs += [(st["exp_avg"], L.DENSIFY_ROLE_STATE), (st["exp_avg_sq"], L.DENSIFY_ROLE_STATE)]
-                keys += [("moment", short)] * 2
+        return a, keep
+
+    def _refine_attrs(self):
+        """optimiser group (after the class prefix) -> (attribute, role) of every per-point parameter, in the order they travel"""
+        return {"xyz": ("_means", L.DENSIFY_ROLE_XYZ), "sh_dc": ("_features_dc", L.DENSIFY_ROLE_COPY), "sh_rest": ("_features_rest", L.DENSIFY_ROLE_COPY),
+                "opacity": ("_opacities", L.DENSIFY_ROLE_COPY), "scaling": ("_scales", L.DENSIFY_ROLE_SCALING), "rotation": ("_quats", L.DENSIFY_ROLE_COPY)}
+
+    def _refine_rows(self, a, keep, jobs, N, samples):
+        """The driver call -> (outs or None, (originals kept, duplicates kept, samples kept, split sources), what `_after_refine` takes)"""
+        ns = int(_get(self.ctrl_cfg, "n_split_samples", 2))
         seed = self.refine_seed * 0x9E3779B97F4A7C15 + self.refine_events
         outs, (n_keep, n_dup, n_samp, n_split) = restructure_rows(L.DENSIFY_MODE_REFINE, a, jobs, N, seed=seed, samples=samples, scaling=keep[0],
                                                                   rotation=self._quats.detach().contiguous(), num_samples=ns)
-        info = {"n_before": N, "n_after": n_keep + ns * n_samp + n_dup, "split": n_split, "originals_kept": n_keep, "samples_kept": ns * n_samp,
-                "dups_kept": n_dup}
-        if outs is None:
-            return info                                             # nothing split, duplicated or culled: every tensor stays as it is
-        moments = {}          # short name -> [exp_avg, exp_avg_sq]
-        for (what, short), out in zip(keys, outs):
-            if what == "param":
-                setattr(self, attrs[short][0], Parameter(out))
-            else:
-                moments.setdefault(short, []).append(out)
-        for name, grp in groups.items():
-            short = name[len(self.class_prefix):]
-            hand_over(optimizer, grp, getattr(self, attrs[short][0]), moments.get(short))
-        if do_densify:
-            self.refine_events += 1
-        return info
+        return outs, (n_keep, n_dup, ns * n_samp, n_split), None
+
+    def _after_refine(self, layout):
+        """Rows moved and the new parameters are installed: what else describes the point set (nothing here)."""
