@@ -598,12 +598,25 @@ def _det_offsets(o):
     return dict(rows=o[0], raw_keys=o[1], keys=o[2], slots=o[3], counts=o[4], bytes=o[5])
 
 
+def det_reduction_views(ws, offsets, n, pitch):
+    """Typed views of one deterministic reduction inside the uint8 workspace tensor `ws`: rows float32 [n, pitch]; keys, slots, raw_keys int32 [n]
+    (views of uint32); counts int32 [16].  `offsets`: the byte offset of each, under these names."""
+    import torch
+    i32 = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32)
+    return dict(rows=ws[offsets["rows"]:offsets["rows"] + 4 * n * pitch].view(torch.float32).view(n, pitch), keys=i32(offsets["keys"], n),
+                slots=i32(offsets["slots"], n), raw_keys=i32(offsets["raw_keys"], n), counts=i32(offsets["counts"], 16))
+
+
+def _served(nbytes, what):
+    """A size entry reports 0 bytes for sizes its mode does not serve."""
+    if nbytes == 0:
+        raise EmdError(f"the deterministic {what}")
+    return int(nbytes)
+
+
 def sky_det_workspace_size(num_pixels):
     """Bytes of the workspace of emd_sky_backward_det for a call of `num_pixels` pixels (or directions)."""
-    n = int(load().emd_sky_det_workspace_size(int(num_pixels)))
-    if n == 0:
-        raise EmdError(f"the deterministic sky backward does not serve {num_pixels} pixels (4 P slots are numbered in 32 bits)")
-    return n
+    return _served(load().emd_sky_det_workspace_size(int(num_pixels)), f"sky backward does not serve {num_pixels} pixels (4 P slots are numbered in 32 bits)")
 
 
 def sky_det_layout(num_pixels, resolution):
@@ -615,10 +628,7 @@ def sky_det_layout(num_pixels, resolution):
 
 def motion_det_workspace_size(n):
     """Bytes of the workspace of emd_motion_backward_det for `n` points."""
-    b = int(load().emd_motion_det_workspace_size(int(n)))
-    if b == 0:
-        raise EmdError(f"the deterministic motion backward does not serve {n} points")
-    return b
+    return _served(load().emd_motion_det_workspace_size(int(n)), f"motion backward does not serve {n} points")
 
 
 def motion_det_layout(n, num_actors):
@@ -630,10 +640,8 @@ def motion_det_layout(n, num_actors):
 def track_det_workspace_size(num_actors, head_width=0, num_points=0, row_width=0):
     """Bytes of the workspace of the deterministic actor chain (emd_track_det_workspace_size): (A, dim + E, 0, 0) for the chain's backward,
     (A, 0, n, width) for emd_actor_row_sum_det."""
-    b = int(load().emd_track_det_workspace_size(int(num_actors), int(head_width), int(num_points), int(row_width)))
-    if b == 0:
-        raise EmdError(f"the deterministic actor chain does not serve {num_actors} actors, width {head_width}, {num_points} points, rows of {row_width}")
-    return b
+    return _served(load().emd_track_det_workspace_size(int(num_actors), int(head_width), int(num_points), int(row_width)),
+                   f"actor chain does not serve {num_actors} actors, width {head_width}, {num_points} points, rows of {row_width}")
 
 
 def track_det_layout(num_actors, head_width=0, num_points=0, row_width=0):

@@ -352,13 +352,10 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     memset(&dw, 0, sizeof(dw));
     if (det) {
         if (a->pair_stats) { emd_set_error("backward: pair_stats (diagnostic counters of the float atomics) cannot be combined with EMD_FLAG_DETERMINISTIC"); return EMD_ERR_INVALID; }
-        if (det_slots > (size_t)0xFFFFFFFFu - EMD_SORT_TILE) { emd_set_error("backward: EMD_FLAG_DETERMINISTIC: 4 x bin_capacity %lld exceeds 32-bit slot numbers", (long long)a->bin_capacity); return EMD_ERR_INVALID; }
+        if (!emd_det_slots_fit((int64_t)det_slots)) { emd_set_error("backward: EMD_FLAG_DETERMINISTIC: 4 x bin_capacity %lld exceeds 32-bit slot numbers", (long long)a->bin_capacity); return EMD_ERR_INVALID; }
         emd_carve_det(a->det_ws, N, a->bin_capacity, a->num_extra, &dw);
-        if (!a->det_ws || a->det_bytes < dw.bytes) {
-            emd_set_error("backward: EMD_FLAG_DETERMINISTIC needs det_ws of %zu bytes (emd_raster_det_workspace_size), got %zu", dw.bytes, a->det_ws ? a->det_bytes : (size_t)0);
-            return EMD_ERR_WORKSPACE;
-        }
-        if ((uintptr_t)a->det_ws & 63) { emd_set_error("backward: det_ws must be 64-byte aligned"); return EMD_ERR_INVALID; }
+        rc = emd_det_check_ws("backward: EMD_FLAG_DETERMINISTIC", a->det_ws, a->det_bytes, dw.bytes, 64, EMD_ERR_INVALID, "emd_raster_det_workspace_size");
+        if (rc) return rc;
     }
     const bool dbg = a->s.debug != 0;
     // the two halves of the pass may arrive as two calls (EMD_FLAG_BWD_RENDER_ONLY, then EMD_FLAG_BWD_PROJECT_ONLY on the same workspaces)
@@ -387,15 +384,14 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
         }
         rc = emd_launch_render_backward(a->s, a->settings_dev, a->flags, g, b, im, a->out_color, a->out_depth, a->out_normal, a->dL_dcolor,
                                         a->dL_ddepth, a->dL_dalpha, a->dL_dnormal, &ex, (float*)a->bwd_ws, pose_grad, pose_grad_n,
-                                        (unsigned long long*)a->pair_stats, det ? dw.part : nullptr, st);
+                                        (unsigned long long*)a->pair_stats, det ? dw.r.rows : nullptr, st);
         if (rc) return rc;
         if (det) {
             // every contribution row sits in its survivor's slot: list the slots per Gaussian (a stable sort: ascending slot order inside a Gaussian,
             // a function of the bit-exact binning alone) and sum each list in the pinned order into the accumulator rows K8 expects
-            rc = emd_launch_det_render_keys(gx * gy, b, a->status, dw.r.keys_in, dw.counts, st);
+            rc = emd_launch_det_render_keys(gx * gy, b, a->status, dw.r.s.keys_in, dw.counts, st);
             if (rc) return rc;
-            rc = emd_det_sort_and_sum(dw.r, det_slots, N, dw.counts, dw.counts + 1, dw.part, emd_bwd_stride(a->num_extra), EMD_BWD_PAYLOAD + 4 * a->num_extra,
-                                      (float*)a->bwd_ws, emd_bwd_stride(a->num_extra), st);
+            rc = emd_det_sort_and_sum(dw.r, N, dw.counts, dw.counts + 1, (float*)a->bwd_ws, emd_bwd_stride(a->num_extra), st);
             if (rc) return rc;
         }
         if (!do_project && a->dL_dsh_color) {      // the SH factor right behind K7: a view-parallel step starts gathering it under K8
@@ -414,16 +410,15 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     pb.dL_dsh_color = a->dL_dsh_color;
     for (int k = 0; k < EMD_MAX_EXTRA; k++) pb.dL_dextra[k] = k < a->num_extra ? a->dL_dcolors_extra[k] : nullptr;
     const bool det_pose = det && (a->flags & EMD_FLAG_MOTION) && a->dL_dactor_pose && a->motion.num_actors > 0;
-    pb.pose_rows = det_pose ? dw.pose_rows : nullptr;
+    pb.pose_rows = det_pose ? dw.p.rows : nullptr;
     if (do_render) emd_prof_switch(PROF_RENDER_BWD, PROF_PREPROCESS_BWD, st); else emd_prof_begin(PROF_PREPROCESS_BWD, st);
     rc = emd_launch_preprocess_backward(pb, st);
     if (!rc && det_pose && a->motion.actor_id && N > 0) {
         // K8 stored the pose gradient of every visible actor-bound point: the points by actor (stable: ascending point index), the rows summed in the
         // pinned order.  Actors without a visible point keep the zeros K7's first workgroup wrote.
-        rc = emd_launch_det_pose_keys(N, a->radii, a->motion.actor_id, dw.p.keys_in, st);
+        rc = emd_launch_det_pose_keys(N, a->radii, a->motion.actor_id, dw.p.s.keys_in, st);
         if (rc) return rc;
-        rc = emd_det_sort_and_sum(dw.p, (size_t)N, a->motion.num_actors, nullptr, dw.counts + 2, dw.pose_rows, EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, a->dL_dactor_pose,
-                                  EMD_ACTOR_STRIDE, st);
+        rc = emd_det_sort_and_sum(dw.p, a->motion.num_actors, nullptr, dw.counts + 2, a->dL_dactor_pose, EMD_ACTOR_STRIDE, st);
     }
     emd_prof_end(PROF_PREPROCESS_BWD, st);
     if (rc) return rc;
@@ -455,14 +450,12 @@ int emd_raster_det_layout(const EmdDims* dims, int32_t num_actors, size_t out[15
     if (!out) { emd_set_error("det_layout: null argument"); return EMD_ERR_INVALID; }
     DetWs w;
     emd_carve_det(nullptr, dims->num_gaussians, dims->bin_capacity, dims->num_extra, &w);
-    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
-    out[0] = off(w.part);
-    out[1] = off(w.r.keys[0]); out[2] = off(w.r.keys[1]); out[3] = off(w.r.vals[0]); out[4] = off(w.r.vals[1]);
-    out[5] = off(w.counts); out[6] = off(w.pose_rows);
-    out[7] = off(w.p.keys[0]); out[8] = off(w.p.keys[1]); out[9] = off(w.p.vals[0]); out[10] = off(w.p.vals[1]);
-    out[11] = (size_t)emd_radix_result_buf(true, emd_det_sort_passes(dims->num_gaussians));
-    out[12] = (size_t)emd_radix_result_buf(true, emd_det_sort_passes(num_actors));
-    out[13] = off(w.r.keys_in); out[14] = off(w.p.keys_in);
+    const DetSortWs &r = w.r.s, &p = w.p.s;
+    const void* at[15] = {w.r.rows, r.keys[0], r.keys[1], r.vals[0], r.vals[1], w.counts, w.p.rows, p.keys[0], p.keys[1], p.vals[0], p.vals[1],
+                          nullptr, nullptr, r.keys_in, p.keys_in};
+    for (int i = 0; i < 15; i++) out[i] = emd_det_offset(at[i]);
+    out[11] = (size_t)emd_det_sorted_buf(dims->num_gaussians);
+    out[12] = (size_t)emd_det_sorted_buf(num_actors);
     return EMD_OK;
 }
 
@@ -593,23 +586,23 @@ int emd_motion_backward(int32_t n, const float* means, const float* quats, const
                                       dL_dresidual_dx, dL_dresidual_dq, st);
 }
 
-// the points are numbered in 32 bits, and the sort rounds its launch up to whole tiles
-static bool motion_det_fits(int64_t n) { return n >= 0 && 4 * n <= (int64_t)0xFFFFFFFFu - EMD_SORT_TILE; }
+// The workspace of the stand-alone motion backward's deterministic form: the pose half of DetWs alone -- the [n][EMD_ACTOR_STRIDE] pose gradient of
+// every actor-bound point (k_motion_backward_det) and the sort of the points by actor id.  The mode serves the n whose 4 n fit the slot numbers.
+static bool motion_det_fits(int64_t n) { return emd_det_slots_fit(4 * n); }
+static void carve_motion_det(void* base, int64_t n, DetUnitWs* w) { emd_carve_det_unit(base, (size_t)(n > 0 ? n : 1), EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, w); }
 
 size_t emd_motion_det_workspace_size(int32_t n) {
     if (!motion_det_fits(n)) return 0;
-    MotionDetWs w;
-    emd_carve_motion_det(nullptr, n, &w);
+    DetUnitWs w;
+    carve_motion_det(nullptr, n, &w);
     return w.bytes;
 }
 
 int emd_motion_det_workspace_offsets(int32_t n, int32_t num_actors, size_t out[6]) {
     if (!out || !motion_det_fits(n) || num_actors < 1) { emd_set_error("motion_det_workspace_offsets: bad argument (n = %d, num_actors = %d)", n, num_actors); return EMD_ERR_INVALID; }
-    MotionDetWs w;
-    emd_carve_motion_det(nullptr, n, &w);
-    const int buf = emd_radix_result_buf(true, emd_det_sort_passes(num_actors));
-    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
-    out[0] = off(w.pose_rows); out[1] = off(w.p.keys_in); out[2] = off(w.p.keys[buf]); out[3] = off(w.p.vals[buf]); out[4] = off(w.counts); out[5] = w.bytes;
+    DetUnitWs w;
+    carve_motion_det(nullptr, n, &w);
+    emd_det_unit_offsets(w, num_actors, out);
     return EMD_OK;
 }
 
@@ -625,23 +618,19 @@ int emd_motion_backward_det(int32_t n, const float* means, const float* quats, c
     if (!motion_det_fits(n)) { emd_set_error("motion_backward_det: the deterministic mode serves 4 n <= 2^32 - 1 - %d (n = %d)", EMD_SORT_TILE, n); return EMD_ERR_INVALID; }
     // everything is decided here, before the first launch
     const bool pose = dL_dactor_pose && motion->num_actors > 0;
-    MotionDetWs w;
+    DetUnitWs w;
     memset(&w, 0, sizeof(w));
     if (pose) {
-        emd_carve_motion_det(nullptr, n, &w);
-        if (!det_ws || det_bytes < w.bytes || ((uintptr_t)det_ws & 255)) {
-            emd_set_error("motion_backward_det: needs a 256-byte aligned det_ws of %zu bytes (emd_motion_det_workspace_size), got %zu at %p", w.bytes, det_ws ? det_bytes : (size_t)0, det_ws);
-            return EMD_ERR_WORKSPACE;
-        }
-        emd_carve_motion_det(det_ws, n, &w);
+        carve_motion_det(det_ws, n, &w);
+        const int wrc = emd_det_check_ws("motion_backward_det", det_ws, det_bytes, w.bytes, 256, EMD_ERR_WORKSPACE, "emd_motion_det_workspace_size");
+        if (wrc) return wrc;
     }
     hipStream_t st = (hipStream_t)hip_stream;
     if (pose) { int zrc = emd_zero_async(dL_dactor_pose, (size_t)motion->num_actors * EMD_ACTOR_STRIDE * sizeof(float), st); if (zrc) return zrc; }
     int rc = emd_launch_motion_backward_det(n, means, quats, opacities, *motion, dL_dworld_means, dL_dworld_quats, dL_dopacities_out, dL_dmeans, dL_dquats,
-                                            dL_dopacities, dL_dresidual_dx, dL_dresidual_dq, w.pose_rows, w.p.keys_in, st);
+                                            dL_dopacities, dL_dresidual_dx, dL_dresidual_dq, w.r.rows, w.r.s.keys_in, st);
     if (rc || !pose || n == 0) return rc;
-    return emd_det_sort_and_sum(w.p, (size_t)n, motion->num_actors, nullptr, w.counts, w.pose_rows, EMD_ACTOR_STRIDE, EMD_ACTOR_STRIDE, dL_dactor_pose,
-                                EMD_ACTOR_STRIDE, st);
+    return emd_det_sort_and_sum(w.r, motion->num_actors, nullptr, w.counts, dL_dactor_pose, EMD_ACTOR_STRIDE, st);
 }
 
 int emd_sh_forward(int32_t n, int32_t degree, int32_t sh_coeffs, const float* dirs, const float* coeffs, float* rgb,

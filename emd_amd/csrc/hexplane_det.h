@@ -5,22 +5,16 @@
 #pragma once
 #include "det_reduce.h"
 
-struct HexDetWs {
-    float* rows;             // [4 N][C] rows of the plane in flight: slot e = k N + n holds tap k of point n
-    DetSortWs r;             // n = 4 N slots -> texels
-    uint32_t* counts;        // [16] device-side counts: [0] slots the sort kept (= 4 N: every slot has a texel)
+struct HexDetWs : DetUnitWs {   // r: the [4 N][C] rows of the plane in flight (slot e = k N + n holds tap k of point n) and the sort of the slots by texel
+                                // counts: [0] slots the sort kept (= 4 N: every slot has a texel)
     float* tcol;             // [N] dL/dtimes of every point, when only its sum is asked for (EmdHexGrads.dL_dtime_sum)
     uint32_t *tkeys, *tslots;   // [N] each: one run under key 0, slots 0 .. N - 1
     double* tpartials;       // chunk sums of that run
-    size_t bytes;
 };
 static inline void emd_carve_hex_det(void* base, int64_t N, int C, HexDetWs* w) {
     char* p = (char*)base;
-    size_t off = 0;
     const size_t n = (size_t)(N > 0 ? N : 1);
-    w->rows = (float*)(p + off); off = emd_align_up(off + 4 * n * (size_t)C * sizeof(float), 256);
-    emd_carve_det_sort(p, off, 4 * n, C, &w->r);
-    w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
+    size_t off = emd_carve_det_unit(base, 4 * n, C, C, w);
     w->tcol = (float*)(p + off); off = emd_align_up(off + n * 4, 256);
     w->tkeys = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);
     w->tslots = (uint32_t*)(p + off); off = emd_align_up(off + n * 4, 256);

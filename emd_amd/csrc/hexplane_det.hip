@@ -126,11 +126,10 @@ int det_plane(const EmdHexArgs* a, const EmdHexGrads* g, int s, int p, const Hex
     const int per_block = EMD_BLOCK / a->channels;
     with_int<0, 5>(p, [&](auto pc) {
         hipLaunchKernelGGL(k_hexplane_det_rows<decltype(pc)::value>, dim3((unsigned)((a->num_points + per_block - 1) / per_block)), dim3(EMD_BLOCK), 0, st, *a,
-                           g->dL_dout, s, w.rows, w.r.keys_in);
+                           g->dL_dout, s, w.r.rows, w.r.s.keys_in);
     });
     EMD_LAUNCH_CHECK();
-    return emd_det_sort_and_sum(w.r, 4 * (size_t)a->num_points, emd_hex_plane_texels(a, s, p), nullptr, w.counts, w.rows, a->channels, a->channels,
-                                g->dL_dplanes[s][p], a->channels, st);
+    return emd_det_sort_and_sum(w.r, emd_hex_plane_texels(a, s, p), nullptr, w.counts, g->dL_dplanes[s][p], a->channels, st);
 }
 
 }  // namespace
@@ -139,7 +138,7 @@ int emd_hexplane_backward_det(const EmdHexArgs* a, const EmdHexGrads* g, hipStre
     const int C = a->channels, S = a->num_scales;
     // everything is decided here, before the first launch
     if (C > 32) { emd_set_error("hexplane_backward: the deterministic mode serves up to 32 channels (the row width of the segmented sum), got %d", C); return EMD_ERR_INVALID; }
-    if ((int64_t)a->num_points >= ((int64_t)1 << 30) - EMD_SORT_TILE) { emd_set_error("hexplane_backward: the deterministic mode numbers 4 N slots in 32 bits"); return EMD_ERR_INVALID; }
+    if (!emd_det_hex_points_fit(a->num_points)) { emd_set_error("hexplane_backward: the deterministic mode numbers 4 N slots in 32 bits"); return EMD_ERR_INVALID; }
     if (g->det_keep_plane > (uint32_t)(6 * S)) { emd_set_error("hexplane_backward: det_keep_plane %u names no plane of %d scales", g->det_keep_plane, S); return EMD_ERR_INVALID; }
     bool any_plane = false;
     for (int s = 0; s < S; s++)
@@ -148,13 +147,9 @@ int emd_hexplane_backward_det(const EmdHexArgs* a, const EmdHexGrads* g, hipStre
     HexDetWs w;
     memset(&w, 0, sizeof(w));
     if (any_plane || time_sum) {
-        emd_carve_hex_det(nullptr, a->num_points, C, &w);
-        if (!g->det_ws || g->det_bytes < w.bytes) {
-            emd_set_error("hexplane_backward: the deterministic mode needs det_ws of %zu bytes (emd_hexplane_det_workspace_size), got %zu", w.bytes, g->det_ws ? g->det_bytes : (size_t)0);
-            return EMD_ERR_WORKSPACE;
-        }
-        if ((uintptr_t)g->det_ws & 255) { emd_set_error("hexplane_backward: det_ws must be 256-byte aligned"); return EMD_ERR_INVALID; }
         emd_carve_hex_det(g->det_ws, a->num_points, C, &w);
+        const int rc = emd_det_check_ws("hexplane_backward: the deterministic mode", g->det_ws, g->det_bytes, w.bytes, 256, EMD_ERR_INVALID, "emd_hexplane_det_workspace_size");
+        if (rc) return rc;
     }
     if (g->dL_dpts || g->dL_dtimes || time_sum) {
         const int per_block = EMD_BLOCK / C;
@@ -200,9 +195,9 @@ extern "C" int emd_hexplane_det_workspace_offsets(const EmdHexArgs* a, int32_t p
     }
     HexDetWs w;
     emd_carve_hex_det(nullptr, a->num_points, a->channels, &w);
-    const int passes = emd_det_sort_passes(emd_hex_plane_texels(a, (plane - 1) / 6, (plane - 1) % 6)), buf = emd_radix_result_buf(true, passes);
-    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
-    out[0] = off(w.rows); out[1] = off(w.r.keys[buf]); out[2] = off(w.r.vals[buf]); out[3] = off(w.tcol);
-    out[4] = off(w.r.keys_in); out[5] = off(w.counts); out[6] = (size_t)passes; out[7] = w.bytes;
+    const int64_t texels = emd_hex_plane_texels(a, (plane - 1) / 6, (plane - 1) % 6);
+    const int buf = emd_det_sorted_buf(texels);
+    out[0] = emd_det_offset(w.r.rows); out[1] = emd_det_offset(w.r.s.keys[buf]); out[2] = emd_det_offset(w.r.s.vals[buf]); out[3] = emd_det_offset(w.tcol);
+    out[4] = emd_det_offset(w.r.s.keys_in); out[5] = emd_det_offset(w.counts); out[6] = (size_t)emd_det_sort_passes(texels); out[7] = w.bytes;
     return EMD_OK;
 }

@@ -367,7 +367,7 @@ __global__ void __launch_bounds__(EMD_WAVE) k_render_forward_q(RenderDims d, con
 #define BQ_QUEUE 128
 
 // The body of both K7 kernels.  DET (EMD_FLAG_DETERMINISTIC): everything in front of the flush is the same; the flush STORES each staged row, all
-// STRIDE floats, to the survivor's own slot of `grad_rec` (then the contribution rows DetWs::part, laid out as `surv` is) instead of adding its
+// STRIDE floats, to the survivor's own slot of `grad_rec` (then the contribution rows DetWs::r.rows, laid out as `surv` is) instead of adding its
 // non-zero floats to the Gaussian's accumulator row: no atomics, every slot the key build of emd_launch_det_render_keys keeps is written exactly once.
 template <bool NORMAL, bool ABS, int NX, bool STATS, bool DET>
 __device__ __forceinline__ void render_backward_body(const RenderDims& d, const uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ ranges,

@@ -47,7 +47,7 @@ int check_sizes(int64_t P, int32_t res, const char* who) {
 
 extern "C" size_t emd_sky_det_workspace_size(int64_t num_pixels) {
     if (num_pixels < 0 || !emd_det_slots_fit(4 * num_pixels)) return 0;
-    SkyDetWs w;
+    DetUnitWs w;
     emd_carve_sky_det(nullptr, num_pixels, &w);
     return w.bytes;
 }
@@ -56,11 +56,9 @@ extern "C" int emd_sky_det_workspace_offsets(int64_t num_pixels, int32_t resolut
     if (!out) { emd_set_error("sky_det_workspace_offsets: null argument"); return EMD_ERR_INVALID; }
     const int rc = check_sizes(num_pixels, resolution, "sky_det_workspace_offsets");
     if (rc) return rc;
-    SkyDetWs w;
+    DetUnitWs w;
     emd_carve_sky_det(nullptr, num_pixels, &w);
-    const int buf = emd_radix_result_buf(true, emd_det_sort_passes(sky_texels(resolution)));
-    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
-    out[0] = off(w.rows); out[1] = off(w.r.keys_in); out[2] = off(w.r.keys[buf]); out[3] = off(w.r.vals[buf]); out[4] = off(w.counts); out[5] = w.bytes;
+    emd_det_unit_offsets(w, sky_texels(resolution), out);
     return EMD_OK;
 }
 
@@ -71,21 +69,18 @@ extern "C" int emd_sky_backward_det(const EmdSkyBwdArgs* b, void* det_ws, size_t
     const int64_t P = (int64_t)b->f.height * b->f.width;
     rc = check_sizes(P, b->f.resolution, "sky_backward_det");
     if (rc) return rc;
-    SkyDetWs w;
+    DetUnitWs w;
     memset(&w, 0, sizeof(w));
     if (b->dL_dcube) {
-        emd_carve_sky_det(nullptr, P, &w);
-        if (!det_ws || det_bytes < w.bytes || ((uintptr_t)det_ws & 255)) {
-            emd_set_error("sky_backward_det: needs a 256-byte aligned det_ws of %zu bytes (emd_sky_det_workspace_size), got %zu at %p", w.bytes, det_ws ? det_bytes : (size_t)0, det_ws);
-            return EMD_ERR_WORKSPACE;
-        }
         emd_carve_sky_det(det_ws, P, &w);
+        rc = emd_det_check_ws("sky_backward_det", det_ws, det_bytes, w.bytes, 256, EMD_ERR_WORKSPACE, "emd_sky_det_workspace_size");
+        if (rc) return rc;
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const int64_t texels = sky_texels(b->f.resolution);
     if (b->dL_dcube) { rc = emd_zero_async(b->dL_dcube, (size_t)texels * 3 * sizeof(float), st); if (rc) return rc; }
-    hipLaunchKernelGGL(k_sky_det_rows, dim3((unsigned)(((size_t)P + EMD_BLOCK - 1) / EMD_BLOCK)), dim3(EMD_BLOCK), 0, st, *b, (float4*)w.rows, w.r.keys_in);
+    hipLaunchKernelGGL(k_sky_det_rows, dim3((unsigned)(((size_t)P + EMD_BLOCK - 1) / EMD_BLOCK)), dim3(EMD_BLOCK), 0, st, *b, (float4*)w.r.rows, w.r.s.keys_in);
     EMD_LAUNCH_CHECK();
     if (!b->dL_dcube) return EMD_OK;
-    return emd_det_sort_and_sum(w.r, 4 * (size_t)P, texels, nullptr, w.counts, w.rows, EMD_SKY_DET_ROW_PITCH, 3, b->dL_dcube, 3, st);
+    return emd_det_sort_and_sum(w.r, texels, nullptr, w.counts, b->dL_dcube, 3, st);
 }

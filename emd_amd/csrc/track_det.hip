@@ -30,7 +30,7 @@ inline int slab_pitch(int w) { return (slot_floats(w) + 15) / 16 * 16; }
 struct TrackDetWs {
     float* slab;             // [A][pitch] every actor's share of the head gradients
     float* dh;               // [A][2][64] every actor's per-lane dL/dh_c, dL/dh_f
-    DetSortWs s;             // n points -> actor ids (the row sum)
+    DetSortWs s;             // n points -> actor ids (the row sum, whose rows are the caller's)
     uint32_t* counts;        // [16] device-side counts: [0] points the sort kept
     size_t bytes;
 };
@@ -43,18 +43,16 @@ void carve_track_det(void* base, int num_actors, int head_width, int64_t n_point
     w->dh = (float*)(p + off); off = emd_align_up(off + (chain ? A * 2 * EMD_WAVE * sizeof(float) : 0), 256);
     if (sum) emd_carve_det_sort(p, off, n, row_width < 32 ? row_width : 32, &w->s);
     else memset(&w->s, 0, sizeof(w->s));
-    w->counts = (uint32_t*)(p + off); off = emd_align_up(off + 64, 256);
+    w->counts = emd_carve_det_counts(p, off);
     w->bytes = off + 256;
 }
 bool track_det_sizes_ok(int num_actors, int head_width, int64_t n, int row_width) {
-    return num_actors >= 0 && head_width >= 0 && head_width <= EMD_WAVE && n >= 0 && n <= (int64_t)0x7FFFFFFF - EMD_SORT_TILE && row_width >= 0 && row_width <= 64;
+    return num_actors >= 0 && head_width >= 0 && head_width <= EMD_WAVE && emd_det_track_points_fit(n) && row_width >= 0 && row_width <= 64;
 }
-int check_ws(const void* ws, size_t have, size_t need, const char* who) {
-    if (!ws || have < need || ((uintptr_t)ws & 255)) {
-        emd_set_error("%s: needs a 256-byte aligned workspace of %zu bytes (emd_track_det_workspace_size), got %zu at %p", who, need, ws ? have : (size_t)0, ws);
-        return EMD_ERR_WORKSPACE;
-    }
-    return EMD_OK;
+// the workspace of a call with these sizes, carved at ws and checked (missing, short or misaligned: EMD_ERR_WORKSPACE)
+int carve_checked(const char* who, void* ws, size_t have, int num_actors, int head_width, int64_t n_points, int row_width, TrackDetWs* w) {
+    carve_track_det(ws, num_actors, head_width, n_points, row_width, w);
+    return emd_det_check_ws(who, ws, have, w->bytes, 256, EMD_ERR_WORKSPACE, "emd_track_det_workspace_size");
 }
 
 // ---- (a) per-actor row sum ------------------------------------------------------------------------------------------------------------------------
@@ -96,9 +94,10 @@ int row_sum(int n, int width, const float* rows, int row_pitch, const int32_t* i
     } else {
         hipLaunchKernelGGL(k_row_sum_keys, dim3(blocks), dim3(EMD_BLOCK), 0, st, n, A, ids, w.s.keys_in, out, width, out_pitch);
         EMD_LAUNCH_CHECK();
-        int rc = emd_det_sort_and_sum(w.s, (size_t)n, A, nullptr, w.counts, rows, row_pitch, w0, out, out_pitch, st);
+        const DetReduction r = {const_cast<float*>(rows), w.s, (size_t)n, row_pitch, w0};      // the caller's rows: read, never written
+        int rc = emd_det_sort_and_sum(r, A, nullptr, w.counts, out, out_pitch, st);
         if (rc) return rc;
-        const int buf = emd_radix_result_buf(true, emd_det_sort_passes(A));
+        const int buf = emd_det_sorted_buf(A);
         ss.keys = w.s.keys[buf]; ss.slots = w.s.vals[buf]; ss.n_dev = w.counts;
     }
     if (width > 32) {                                            // the second column band over the same sorted list
@@ -289,16 +288,16 @@ extern "C" int emd_track_det_workspace_offsets(int32_t num_actors, int32_t head_
     }
     TrackDetWs w;
     carve_track_det(nullptr, num_actors, head_width, num_points, row_width, &w);
-    const int buf = emd_radix_result_buf(true, emd_det_sort_passes(num_actors));
-    auto off = [](const void* p) { return (size_t)(uintptr_t)p; };
-    out[0] = off(w.slab); out[1] = head_width > 0 ? (size_t)slab_pitch(head_width) : 0; out[2] = off(w.dh);
-    out[3] = off(w.s.keys_in); out[4] = off(w.s.keys[buf]); out[5] = off(w.s.vals[buf]); out[6] = off(w.counts); out[7] = w.bytes;
+    const int buf = emd_det_sorted_buf(num_actors);
+    out[0] = emd_det_offset(w.slab); out[1] = head_width > 0 ? (size_t)slab_pitch(head_width) : 0; out[2] = emd_det_offset(w.dh);
+    out[3] = emd_det_offset(w.s.keys_in); out[4] = emd_det_offset(w.s.keys[buf]); out[5] = emd_det_offset(w.s.vals[buf]);
+    out[6] = emd_det_offset(w.counts); out[7] = w.bytes;
     return EMD_OK;
 }
 
 extern "C" int emd_actor_row_sum_det(int32_t n, int32_t width, const float* rows, int32_t row_pitch, const int32_t* ids, int32_t num_actors,
                                      const int32_t* segment_start, float* out, int32_t out_pitch, void* ws, size_t ws_bytes, void* hip_stream) {
-    if (n < 0 || num_actors < 0 || width < 1 || width > 64 || row_pitch < width || out_pitch < width || (int64_t)n > (int64_t)0x7FFFFFFF - EMD_SORT_TILE) {
+    if (n < 0 || num_actors < 0 || width < 1 || width > 64 || row_pitch < width || out_pitch < width || !emd_det_track_points_fit(n)) {
         emd_set_error("actor_row_sum_det: need 1 <= width <= 64 and width <= row_pitch, out_pitch (n %d, actors %d, width %d, pitches %d / %d)", n, num_actors, width,
                       row_pitch, out_pitch);
         return EMD_ERR_INVALID;
@@ -306,10 +305,8 @@ extern "C" int emd_actor_row_sum_det(int32_t n, int32_t width, const float* rows
     if (n == 0 || num_actors == 0) return EMD_OK;
     if (!rows || !out || (!ids && !segment_start)) { emd_set_error("actor_row_sum_det: null rows / ids / out pointer"); return EMD_ERR_INVALID; }
     TrackDetWs w;
-    carve_track_det(nullptr, num_actors, 0, n, width, &w);
-    int rc = check_ws(ws, ws_bytes, w.bytes, "actor_row_sum_det");
+    const int rc = carve_checked("actor_row_sum_det", ws, ws_bytes, num_actors, 0, n, width, &w);
     if (rc) return rc;
-    carve_track_det(ws, num_actors, 0, n, width, &w);
     return row_sum(n, width, rows, row_pitch, ids, num_actors, segment_start, out, out_pitch, w, (hipStream_t)hip_stream);
 }
 
@@ -321,10 +318,8 @@ extern "C" int emd_track_heads_forward_det(const EmdTrackArgs* a, void* ws, size
     // sorted ids and a narrow embedding: the default forward has no atomics (k_track_embed_sum_seg) and is used as it is
     if (!(E > 0 && a->num_points > 0) || (a->segment_start && E <= 8)) return emd_track_heads_forward(a, hip_stream);
     TrackDetWs w;
-    carve_track_det(nullptr, a->num_actors, 0, a->num_points, E, &w);
-    rc = check_ws(ws, ws_bytes, w.bytes, "track_heads_forward_det");
+    rc = carve_checked("track_heads_forward_det", ws, ws_bytes, a->num_actors, 0, a->num_points, E, &w);
     if (rc) return rc;
-    carve_track_det(ws, a->num_actors, 0, a->num_points, E, &w);
     rc = row_sum(a->num_points, E, a->embeddings, E, a->point_ids, a->num_actors, a->segment_start, a->emb_sum, E, w, (hipStream_t)hip_stream);
     if (rc) return rc;
     EmdTrackArgs heads = *a;                     // the sums are there: without points the default entry launches k_track_heads<false> alone
@@ -339,10 +334,8 @@ extern "C" int emd_track_heads_backward_det(const EmdTrackArgs* a, const EmdTrac
     for (int h = 0; h < 4; h++) if (!g->d_head_w[h] || !g->d_head_b[h]) { emd_set_error("track_heads_backward_det: null head gradient %d", h); return EMD_ERR_INVALID; }
     const int A = a->num_actors, E = a->embed_dim, width = a->dim + E;
     TrackDetWs w;
-    carve_track_det(nullptr, A, width, 0, 0, &w);
-    rc = check_ws(ws, ws_bytes, w.bytes, "track_heads_backward_det");
+    rc = carve_checked("track_heads_backward_det", ws, ws_bytes, A, width, 0, 0, &w);
     if (rc) return rc;
-    carve_track_det(ws, A, width, 0, 0, &w);
     hipStream_t st = (hipStream_t)hip_stream;
     ChainBwd b;
     memset(&b, 0, sizeof(b));
@@ -366,10 +359,8 @@ extern "C" int emd_tracked_pose_backward_det(const EmdTrackedPoseArgs* p, const 
     for (int h = 0; h < 4; h++) if (!g->d_head_w[h] || !g->d_head_b[h]) { emd_set_error("tracked_pose_backward_det: null head gradient %d", h); return EMD_ERR_INVALID; }
     const int A = p->track.num_actors, width = p->track.dim + p->track.embed_dim;
     TrackDetWs w;
-    carve_track_det(nullptr, A, width, 0, 0, &w);
-    rc = check_ws(ws, ws_bytes, w.bytes, "tracked_pose_backward_det");
+    rc = carve_checked("tracked_pose_backward_det", ws, ws_bytes, A, width, 0, 0, &w);
     if (rc) return rc;
-    carve_track_det(ws, A, width, 0, 0, &w);
     hipStream_t st = (hipStream_t)hip_stream;
     ChainBwd b;
     memset(&b, 0, sizeof(b));

@@ -32,10 +32,7 @@ class DeterministicSum:
 def _hex_det_views(ws, args, plane):
     lay = L.hex_det_layout(args, plane)
     N, Cc = args.num_points, args.channels
-    i32 = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32)
-    return dict(rows=ws[lay["rows"]:lay["rows"] + 16 * N * Cc].view(torch.float32).view(4 * N, Cc), keys=i32(lay["keys"], 4 * N), slots=i32(lay["slots"], 4 * N),
-                raw_keys=i32(lay["raw_keys"], 4 * N), counts=i32(lay["counts"], 16),
-                time_column=ws[lay["time_column"]:lay["time_column"] + 4 * N].view(torch.float32), passes=lay["passes"])
+    return dict(L.det_reduction_views(ws, lay, 4 * N, Cc), time_column=ws[lay["time_column"]:lay["time_column"] + 4 * N].view(torch.float32), passes=lay["passes"])
 
 
 class _HexLookup(torch.autograd.Function):

@@ -336,12 +336,11 @@ def camera_inputs(rs):
 def _det_views(ws, N, capacity, num_extra, num_actors):
     """Typed views into the workspace of a deterministic backward (RasterCall.det_state)."""
     lay = L.det_layout(N, capacity, num_extra, num_actors)
-    R, n, pitch = 4 * max(int(capacity), 1), max(int(N), 1), L.bwd_stride(num_extra)
-    i32 = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32)
-    return dict(rows=ws[lay["rows"]:lay["rows"] + 4 * R * pitch].view(torch.float32).view(R, pitch),
-                keys=i32(lay["keys"][lay["sorted_buf"]], R), slots=i32(lay["slots"][lay["sorted_buf"]], R), counts=i32(lay["counts"], 16),
-                pose_rows=ws[lay["pose_rows"]:lay["pose_rows"] + 4 * n * L.ACTOR_STRIDE].view(torch.float32).view(n, L.ACTOR_STRIDE),
-                pose_keys=i32(lay["pose_keys"][lay["pose_sorted_buf"]], n), pose_points=i32(lay["pose_points"][lay["pose_sorted_buf"]], n))
+    rb, pb = lay["sorted_buf"], lay["pose_sorted_buf"]
+    r = L.det_reduction_views(ws, dict(lay, keys=lay["keys"][rb], slots=lay["slots"][rb]), 4 * max(int(capacity), 1), L.bwd_stride(num_extra))
+    p = L.det_reduction_views(ws, dict(rows=lay["pose_rows"], keys=lay["pose_keys"][pb], slots=lay["pose_points"][pb], raw_keys=lay["pose_raw_keys"],
+                                       counts=lay["counts"]), max(int(N), 1), L.ACTOR_STRIDE)
+    return dict(rows=r["rows"], keys=r["keys"], slots=r["slots"], counts=r["counts"], pose_rows=p["rows"], pose_keys=p["keys"], pose_points=p["slots"])
 
 
 class _Rasterize(torch.autograd.Function):

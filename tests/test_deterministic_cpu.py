@@ -94,6 +94,40 @@ def test_flag_without_workspace_is_refused_on_the_host():
     assert b"pair_stats" in lib.emd_last_error()
 
 
+def _fake_det_backward(capacity):
+    b = L.EmdBwdArgs()
+    b.num_gaussians, b.flags, b.bin_capacity = 0, L.FLAG_DETERMINISTIC, capacity
+    b.s.image_height = b.s.image_width = 32
+    b.s.tanfovx = b.s.tanfovy = 1.0
+    fake = 1 << 20             # never dereferenced: the call is refused first
+    b.radii = b.geom_ws = b.bin_ws = b.img_ws = b.bwd_ws = b.status = b.out_color = b.out_depth = fake
+    b.geom_bytes = b.bin_bytes = b.img_bytes = b.bwd_bytes = 1 << 62
+    return b
+
+
+def test_misaligned_workspace_is_refused_on_the_host():
+    """det_ws is 64-byte aligned: a large enough workspace at another address is an invalid argument, not a short workspace."""
+    lib = L.load()
+    b = _fake_det_backward(100)
+    b.det_ws, b.det_bytes = (1 << 20) + 32, 1 << 40
+    assert lib.emd_raster_backward(C.byref(b), None) == L.EMD_ERR_INVALID
+    assert b"det_ws" in lib.emd_last_error() and b"aligned" in lib.emd_last_error()
+
+
+def test_slot_numbers_past_32_bits_are_refused_on_the_host():
+    """4 x bin_capacity contribution slots are numbered in 32 bits, less one sort tile (2048 keys) that the sort rounds its launch up by."""
+    lib = L.load()
+    last = (2 ** 32 - 1 - 2048) // 4                         # the largest capacity the mode serves
+    b = _fake_det_backward(last + 1)
+    b.det_ws, b.det_bytes = 1 << 20, 1 << 62
+    assert lib.emd_raster_backward(C.byref(b), None) == L.EMD_ERR_INVALID
+    assert b"bin_capacity" in lib.emd_last_error()
+    # the capacity below gets past that check: it is refused for its workspace (none given) instead
+    b = _fake_det_backward(last)
+    assert lib.emd_raster_backward(C.byref(b), None) == L.EMD_ERR_WORKSPACE
+    assert b"det_ws" in lib.emd_last_error() and b"bin_capacity" not in lib.emd_last_error()
+
+
 # ---- the restatement itself, on cases typed out by hand -------------------------------------------------------------------------------------
 def _one_run(values, chunk):
     v = np.asarray(values, np.float32).reshape(-1, 1)

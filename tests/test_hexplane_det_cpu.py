@@ -115,6 +115,19 @@ def test_flag_with_64_channels_is_refused_on_the_host():
     assert b"32 channels" in lib.emd_last_error()
 
 
+def test_slot_numbers_past_32_bits_are_refused_on_the_host():
+    """4 N slots are numbered in 32 bits, less one sort tile (2048 keys) per tap: num_points < 2^30 - 2048."""
+    lib = L.load()
+    a, g = _fake_call(32)
+    a.num_points = 2 ** 30 - 2048
+    assert lib.emd_hexplane_backward(C.byref(a), C.byref(g), None) == L.EMD_ERR_INVALID
+    assert b"32 bits" in lib.emd_last_error()
+    # one point less gets past that check: the call is refused for its workspace (none given) instead
+    a.num_points -= 1
+    assert lib.emd_hexplane_backward(C.byref(a), C.byref(g), None) == L.EMD_ERR_WORKSPACE
+    assert b"det_ws" in lib.emd_last_error()
+
+
 def test_python_switches_default_off():
     from emd_amd.deformation import DeformOptions
     from emd_amd.hexplane import DeterministicSum, HexPlaneField

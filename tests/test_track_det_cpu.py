@@ -90,6 +90,9 @@ def test_workspace_size_refuses_sizes_outside_the_limits():
     assert lib.emd_track_det_workspace_size(4, 0, 10, 65) == 0
     assert lib.emd_track_det_workspace_size(-1, 0, 10, 4) == 0
     assert lib.emd_track_det_workspace_size(4, 0, 2 ** 31, 4) == 0
+    # the points are numbered in an int, less one sort tile (2048 keys) that the sort rounds its launch up by
+    last = 0x7FFFFFFF - 2048
+    assert lib.emd_track_det_workspace_size(4, 0, last, 4) > 0 and lib.emd_track_det_workspace_size(4, 0, last + 1, 4) == 0
     out = (C.c_size_t * 8)()
     assert lib.emd_track_det_workspace_offsets(4, 65, 0, 0, out) == -1       # EMD_ERR_INVALID
 
