@@ -7,6 +7,8 @@ would void the parity claims of this package.
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libemd_raster.so")
 
@@ -548,6 +550,22 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def stream():
+    """The current torch stream as the `hipStream_t` argument of an entry point, read at call time (under graph capture: the capturing stream)."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def launch(name, *args, what=None):
+    """Call entry point `name`, one of those whose last parameter is the stream, on the current stream and check its return code."""
+    check(getattr(load(), name)(*args, stream()), what or name)
+
+
+def need_device(what, *tensors):
+    """Refuse what is not a tensor on a ROCm device (None entries are skipped)."""
+    if any(t is not None and not (isinstance(t, torch.Tensor) and t.device.type == "cuda") for t in tensors):
+        raise EmdError(f"{what} needs tensors on a ROCm device; there is no CPU path")
+
+
 def workspace_sizes(N, H, W, capacity, flags=0, num_extra=0):
     d = EmdDims(int(N), int(H), int(W), int(capacity), int(flags), int(num_extra))
     out = (C.c_size_t * 4)()
@@ -601,7 +619,6 @@ def _det_offsets(o):
 def det_reduction_views(ws, offsets, n, pitch):
     """Typed views of one deterministic reduction inside the uint8 workspace tensor `ws`: rows float32 [n, pitch]; keys, slots, raw_keys int32 [n]
     (views of uint32); counts int32 [16].  `offsets`: the byte offset of each, under these names."""
-    import torch
     i32 = lambda off, cnt: ws[off:off + 4 * cnt].view(torch.int32)
     return dict(rows=ws[offsets["rows"]:offsets["rows"] + 4 * n * pitch].view(torch.float32).view(n, pitch), keys=i32(offsets["keys"], n),
                 slots=i32(offsets["slots"], n), raw_keys=i32(offsets["raw_keys"], n), counts=i32(offsets["counts"], 16))
@@ -655,14 +672,13 @@ def track_det_layout(num_actors, head_width=0, num_points=0, row_width=0):
 def actor_row_sum_det(rows, width, ids, num_actors, segment_start=None, col0=0):
     """[num_actors, width]: per actor the pinned segmented sum of rows[i, col0 : col0 + width] over the points with ids[i] == a, in ascending i
     (emd_actor_row_sum_det).  rows: contiguous fp32 [n, pitch]; ids: int32 [n]; segment_start: int32 [A + 1] when the ids are sorted by actor."""
-    import torch
     n, pitch = rows.shape
     out = torch.empty(int(num_actors), int(width), device=rows.device, dtype=torch.float32)
     if n == 0 or num_actors == 0 or width == 0:
         return out.zero_()
     ws = torch.empty(track_det_workspace_size(num_actors, 0, n, width), device=rows.device, dtype=torch.uint8)
-    check(load().emd_actor_row_sum_det(n, int(width), rows.data_ptr() + 4 * int(col0), pitch, ptr(ids), int(num_actors), ptr(segment_start), out.data_ptr(),
-                                       int(width), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_actor_row_sum_det")
+    launch("emd_actor_row_sum_det", n, int(width), rows.data_ptr() + 4 * int(col0), pitch, ptr(ids), int(num_actors), ptr(segment_start), out.data_ptr(),
+           int(width), ws.data_ptr(), ws.numel())
     return out
 
 

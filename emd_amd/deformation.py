@@ -31,10 +31,6 @@ from . import _lib as L
 from .hexplane import HexPlaneField
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class DeformOptions:
     """The option fields the deformation network reads, with S3Gaussian/arguments/gaussian_options.py:128-196 defaults and the
     three flags scripts/dynamic/run_dynamic_nvs.sh sets.  Any object with these attributes (the reference's BaseOptions) works."""
@@ -67,8 +63,7 @@ class _TemporalEmbed(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, t, k, deterministic=False):
-        if weight.device.type != "cuda":
-            raise L.EmdError("temporal_embed needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("temporal_embed", weight)
         w = weight.detach().contiguous().float()
         tt = t.detach().reshape(-1)[:1].contiguous().float()
         if tt.numel() == 0:
@@ -76,8 +71,7 @@ class _TemporalEmbed(torch.autograd.Function):
         tables = 1 if w.dim() == 2 else w.shape[0]
         rows, dim = w.shape[-2:]
         out = torch.empty(w.shape[:-2] + (dim,), device=w.device, dtype=torch.float32)
-        L.check(L.load().emd_temporal_embed_forward(w.data_ptr(), tables, rows, dim, int(k), tt.data_ptr(), out.data_ptr(), _stream()),
-                "emd_temporal_embed_forward")
+        L.launch("emd_temporal_embed_forward", w.data_ptr(), tables, rows, dim, int(k), tt.data_ptr(), out.data_ptr())
         ctx.save_for_backward(w, tt)
         ctx.k, ctx.t_shape, ctx.deterministic = int(k), tuple(t.shape), bool(deterministic)
         return out
@@ -92,11 +86,9 @@ class _TemporalEmbed(torch.autograd.Function):
         g = g_out.contiguous().float()
         if ctx.deterministic:      # the gather form: no atomics (csrc/embed_det.hip); several tables leave one dL/dt partial each
             parts = torch.empty(tables, device=w.device, dtype=torch.float32) if g_t is not None and tables > 1 else None
-            L.check(L.load().emd_temporal_embed_backward_det(w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(), g.data_ptr(), L.ptr(g_w), L.ptr(g_t),
-                                                             L.ptr(parts), _stream()), "emd_temporal_embed_backward_det")
+            L.launch("emd_temporal_embed_backward_det", w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(), g.data_ptr(), L.ptr(g_w), L.ptr(g_t), L.ptr(parts))
         else:
-            L.check(L.load().emd_temporal_embed_backward(w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(), g.data_ptr(), L.ptr(g_w), L.ptr(g_t),
-                                                         _stream()), "emd_temporal_embed_backward")
+            L.launch("emd_temporal_embed_backward", w.data_ptr(), tables, rows, dim, ctx.k, tt.data_ptr(), g.data_ptr(), L.ptr(g_w), L.ptr(g_t))
         return g_w, (g_t.reshape(ctx.t_shape) if g_t is not None else None), None, None
 
 
@@ -526,20 +518,18 @@ DeformNetwork = deform_network
 class _DeformInput(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, point_ids, inst_size, inst_embed, t, num_freqs_x, num_freqs_t, deterministic=False):
-        if means.device.type != "cuda":
-            raise L.EmdError("deform_input needs tensors on a ROCm device; there is no CPU path")
-        lib = L.load()
+        L.need_device("deform_input", means)
         a = L.EmdDeformInArgs()
         N, E = means.shape[0], inst_embed.shape[1]
         keep = [means.detach().contiguous().float(), None if point_ids is None else point_ids.to(torch.int32).contiguous(),
                 None if inst_size is None else inst_size.detach().contiguous().float(), inst_embed.detach().contiguous().float(),
                 t.detach().reshape(-1)[:1].contiguous().float()]
-        width = lib.emd_deform_input_width(num_freqs_x, num_freqs_t, E)
+        width = L.load().emd_deform_input_width(num_freqs_x, num_freqs_t, E)
         out = torch.empty(N, width, device=means.device, dtype=torch.float32)
         a.num_points, a.num_freqs_x, a.num_freqs_t, a.embed_dim, a.ld = N, num_freqs_x, num_freqs_t, E, width
         a.means, a.point_ids, a.inst_size, a.inst_embed, a.t, a.out = (keep[0].data_ptr(), L.ptr(keep[1]), L.ptr(keep[2]), keep[3].data_ptr(),
                                                                        keep[4].data_ptr(), out.data_ptr())
-        L.check(lib.emd_deform_input_forward(C.byref(a), _stream()), "emd_deform_input_forward")
+        L.launch("emd_deform_input_forward", C.byref(a))
         ctx.ids, ctx.embed_shape, ctx.col0, ctx.deterministic = keep[1], tuple(inst_embed.shape), width - E, bool(deterministic)
         return out
 
@@ -556,8 +546,7 @@ class _DeformInput(torch.autograd.Function):
             else:
                 g = g.contiguous().float()
                 g_embed = torch.zeros(A, E, device=g.device, dtype=torch.float32)
-                L.check(L.load().emd_deform_input_backward(g.shape[0], E, g.shape[1], ctx.col0, ctx.ids.data_ptr(), g.data_ptr(),
-                                                           g_embed.data_ptr(), _stream()), "emd_deform_input_backward")
+                L.launch("emd_deform_input_backward", g.shape[0], E, g.shape[1], ctx.col0, ctx.ids.data_ptr(), g.data_ptr(), g_embed.data_ptr())
         return None, None, None, g_embed, None, None, None, None    # positions and time are detached in the reference
 
 

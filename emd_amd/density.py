@@ -18,21 +18,16 @@ from torch.nn import Parameter
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _decide_scan(decide, args, N, cols, dev):
     """The head of both drivers: the code / per-block count / totals arrays, the decide call `decide` (the name of the entry point that takes
     `args`), the scan of the `cols` columns and the event's single host read -> (code, inc, totals, the totals as ints)."""
-    lib = L.load()
     code = torch.empty(N, dtype=torch.int32, device=dev)
     inc = torch.empty(cols, (N + 255) // 256, dtype=torch.int32, device=dev)          # per-block counts, then exclusive block offsets
     totals = torch.empty(cols, dtype=torch.int32, device=dev)
     args.num_points = N
-    L.check(getattr(lib, decide)(C.byref(args), code.data_ptr(), inc.data_ptr(), _stream()), decide)
+    L.launch(decide, C.byref(args), code.data_ptr(), inc.data_ptr())
     for c0 in range(0, cols, 8):                                   # emd_densify_scan takes at most 8 columns a call; columns are independent
-        L.check(lib.emd_densify_scan(N, min(8, cols - c0), inc[c0:].data_ptr(), totals[c0:].data_ptr(), _stream()), "emd_densify_scan")
+        L.launch("emd_densify_scan", N, min(8, cols - c0), inc[c0:].data_ptr(), totals[c0:].data_ptr())
     return code, inc, totals, [int(v) for v in totals.tolist()]
 
 
@@ -61,7 +56,7 @@ def _gather(mode, M, num_split, src, kind, seed, scaling, rotation, samples, ran
         g.tensors[k].role = role
         outs.append(out)
     g.num_tensors = len(jobs)
-    L.check(L.load().emd_densify_gather(C.byref(g), _stream()), "emd_densify_gather")
+    L.launch("emd_densify_gather", C.byref(g))
     return outs
 
 
@@ -75,7 +70,6 @@ def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, sc
     that do not take part: the actors of emd_amd.model.density_control).
     -> (outs or None when nothing changes, totals): (n_keep, n_clone, n_split), in REFINE mode (n_keep, n_dup, n_samp, n_split) -- originals,
     duplicates and split sources whose samples are kept, split sources.  The event's single host read is the totals."""
-    lib = L.load()
     refine = isinstance(args, L.EmdRefineArgs)
     assert refine == (mode == L.DENSIFY_MODE_REFINE)
     cols = 4 if refine else 3
@@ -100,12 +94,11 @@ def restructure_rows(mode, args, jobs, N, seed=0, samples=None, front_rows=0, sc
     kind = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
     rank = torch.empty(max(M, 1), dtype=torch.int32, device=dev) if samples is not None else None      # the row of a recorded draw
     if refine:
-        L.check(lib.emd_refine_index(N, M, num_samples, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), L.ptr(rank),
-                                     _stream()), "emd_refine_index")
+        L.launch("emd_refine_index", N, M, num_samples, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), L.ptr(rank))
     else:
-        L.check(lib.emd_densify_index(N, M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), _stream()), "emd_densify_index")
+        L.launch("emd_densify_index", N, M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr())
         if rank is not None:
-            L.check(lib.emd_densify_split_rank(M, n_keep, n_clone, n_split, rank.data_ptr(), _stream()), "emd_densify_split_rank")
+            L.launch("emd_densify_split_rank", M, n_keep, n_clone, n_split, rank.data_ptr())
     if samples is not None:
         samples = samples.to(dev).float().contiguous()
         assert samples.shape == (num_samples, n_split, 3), (tuple(samples.shape), num_samples, n_split)
@@ -121,7 +114,6 @@ def restructure_node_rows(args, jobs, N, samples=None, front_rows=0):
     normals by SOURCE ROW to use instead of the Philox draw; `jobs`, `front_rows`: as restructure_rows.
     -> (outs or None when nothing changes, ids_out int32 [M], segment_start int32 [A + 1] (None when not grouped), counts) with counts =
     (n_keep, n_dup, n_split, [n_samp_r]).  An id outside [0, num_actors) raises before anything is gathered.  The single host read is the totals."""
-    lib = L.load()
     ns, A = int(args.num_samples), int(args.num_actors)
     if N == 0:
         return None, None, None, (0, 0, 0, [0] * ns)
@@ -143,10 +135,10 @@ def restructure_node_rows(args, jobs, N, samples=None, front_rows=0):
     src, kind, ids_out = new(max(M, 1)), new(max(M, 1)), new(max(M, 1))
     rank = new(max(M, 1)) if samples is not None else None
     seg = new(A + 1) if grouped else None
-    ws_bytes = int(lib.emd_refine_nodes_index_workspace(M)) if grouped else 0
+    ws_bytes = int(L.load().emd_refine_nodes_index_workspace(M)) if grouped else 0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    L.check(lib.emd_refine_nodes_index(C.byref(args), M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), ids_out.data_ptr(),
-                                       L.ptr(seg), L.ptr(rank), L.ptr(ws), ws_bytes, _stream()), "emd_refine_nodes_index")
+    L.launch("emd_refine_nodes_index", C.byref(args), M, code.data_ptr(), inc.data_ptr(), totals.data_ptr(), src.data_ptr(), kind.data_ptr(), ids_out.data_ptr(),
+             L.ptr(seg), L.ptr(rank), L.ptr(ws), ws_bytes)
     outs = _gather(L.DENSIFY_MODE_REFINE, M, N, src, kind, args.seed, args.scaling, args.rotation, samples, rank, jobs, N, front_rows)
     return outs, ids_out[:M], seg, counts
 

@@ -119,8 +119,7 @@ def sh_grad_from_factors(means3D, campos, sh_color_grads, sh_degree, sh_coeffs=1
     import ctypes as C
     from . import _lib as L
     from .rasterizer import _fill_motion
-    if means3D.device.type != "cuda":
-        raise L.EmdError("sh_grad_from_factors needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("sh_grad_from_factors", means3D)
     N, V = means3D.shape[0], campos.shape[0]
     means3D, campos, g = means3D.detach().contiguous().float(), campos.detach().contiguous().float(), sh_color_grads.contiguous().float()
     assert g.shape == (V, N, 3)
@@ -135,9 +134,8 @@ def sh_grad_from_factors(means3D, campos, sh_color_grads, sh_degree, sh_coeffs=1
     if per_view:
         mo.actor_pose = pose.data_ptr()
     out = torch.empty(N, sh_coeffs, 3, device=means3D.device, dtype=torch.float32)
-    L.check(L.load().emd_sh_grad_from_factors(N, V, int(sh_degree), int(sh_coeffs), means3D.data_ptr(), C.byref(mo), 1 if per_view else 0,
-                                              campos.data_ptr(), g.data_ptr(), float(scale), out.data_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_sh_grad_from_factors")
+    L.launch("emd_sh_grad_from_factors", N, V, int(sh_degree), int(sh_coeffs), means3D.data_ptr(), C.byref(mo), 1 if per_view else 0,
+             campos.data_ptr(), g.data_ptr(), float(scale), out.data_ptr())
     return out
 
 
@@ -163,8 +161,7 @@ def compact_rows(radii, sources, capacity, out=None, counter=None):
     Gaussian with radii > 0, values gathered from the [N, w_k] float tensors `sources` (at most four)."""
     import ctypes as C
     from . import _lib as L
-    if radii.device.type != "cuda":
-        raise L.EmdError("compact_rows needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("compact_rows", radii)
     N = radii.shape[0]
     width = lambda t: 1 if t.dim() < 2 else int(torch.tensor(t.shape[1:]).prod())
     srcs = [t.detach().reshape(N, width(t)) for t in sources]
@@ -177,8 +174,8 @@ def compact_rows(radii, sources, capacity, out=None, counter=None):
     if counter is None:
         counter = torch.empty(1, dtype=torch.int32, device=radii.device)
     r = radii.contiguous().to(torch.int32)
-    L.check(L.load().emd_compact_rows(N, r.data_ptr(), len(srcs), _ptr_array(srcs), (C.c_int32 * len(widths))(*widths), int(capacity), out.data_ptr(),
-                                      counter.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_compact_rows")
+    L.launch("emd_compact_rows", N, r.data_ptr(), len(srcs), _ptr_array(srcs), (C.c_int32 * len(widths))(*widths), int(capacity), out.data_ptr(),
+             counter.data_ptr())
     return out.view(1 + capacity, rw)
 
 
@@ -192,8 +189,8 @@ def scatter_rows(rows, dests, add, scale=1.0, overflow=None):
         assert t.dtype == torch.float32 and t.is_contiguous(), "scatter_rows: contiguous float32 destinations"
     widths = [int(t.shape[1]) for t in ds]
     assert rows.shape[1] == 1 + sum(widths), (tuple(rows.shape), widths)
-    L.check(L.load().emd_scatter_rows(rows.data_ptr(), int(rows.shape[0] - 1), N, len(ds), _ptr_array(ds), (C.c_int32 * len(widths))(*widths), 1 if add else 0,
-                                      float(scale), L.ptr(overflow), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_scatter_rows")
+    L.launch("emd_scatter_rows", rows.data_ptr(), int(rows.shape[0] - 1), N, len(ds), _ptr_array(ds), (C.c_int32 * len(widths))(*widths), 1 if add else 0,
+             float(scale), L.ptr(overflow))
 
 
 class GradientExchange:
@@ -477,17 +474,13 @@ def add_densification_stats(viewspace_points_grad, radii, xyz_gradient_accum, de
     """In-place update of the three per-Gaussian densification statistics for one view in ONE launch and without the
     boolean-mask indexing of the reference (gaussian_model.py:728-730, train.py:403-406), which costs a host sync per step:
     where radii > 0:  xyz_gradient_accum += |grad.xy|, denom += 1, max_radii2D = max(max_radii2D, radii)."""
-    import ctypes as C
     from . import _lib as L
-    if radii.device.type != "cuda":
-        raise L.EmdError("add_densification_stats needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("add_densification_stats", radii)
     g = viewspace_points_grad.contiguous().float()
     r = radii.contiguous().to(torch.int32)
     for t in (xyz_gradient_accum, denom, max_radii2D):
         assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == r.numel())
-    L.check(L.load().emd_densification_stats(r.numel(), r.data_ptr(), g.data_ptr(), L.ptr(xyz_gradient_accum), L.ptr(denom),
-                                             L.ptr(max_radii2D), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-            "emd_densification_stats")
+    L.launch("emd_densification_stats", r.numel(), r.data_ptr(), g.data_ptr(), L.ptr(xyz_gradient_accum), L.ptr(denom), L.ptr(max_radii2D))
 
 
 def densification_stats(viewspace_points_grad, radii):

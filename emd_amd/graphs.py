@@ -40,7 +40,7 @@ def select_step_inputs(sel, table, out_row, frames=None, frame_out=None, t_out=N
     a.k_min, a.k_max, a.k_until = k_sched if k_sched is not None else (1, 1, 1)
     a.steps, a.k_fine_out = None, L.ptr(k_fine_out)
     a.status, a.status_log, a.prev_sel, a.next_sel = L.ptr(status), L.ptr(status_log), L.ptr(prev_sel), L.ptr(next_sel)
-    L.check(L.load().emd_select_step_inputs(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_select_step_inputs")
+    L.launch("emd_select_step_inputs", C.byref(a))
 
 
 class StepInputs:

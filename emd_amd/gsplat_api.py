@@ -17,7 +17,6 @@ differences from current gsplat releases: tile/radius bookkeeping (not observabl
 rule) and the pixel-centre convention (centres at integer coordinates, i.e. cx is the reference's cx - 0.5 shifted
 inside `projection_from_K`).
 """
-import ctypes as C
 import math
 
 import torch
@@ -30,28 +29,22 @@ from .rasterizer import GaussianRasterizationSettings, RasterCall, RasterConfig,
 class _SphericalHarmonics(torch.autograd.Function):
     @staticmethod
     def forward(ctx, degree, dirs, coeffs):
-        lib = L.load()
-        if dirs.device.type != "cuda":
-            raise L.EmdError("spherical_harmonics needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("spherical_harmonics", dirs)
         n, K = coeffs.shape[0], coeffs.shape[1]
         rgb = torch.empty(n, 3, device=dirs.device, dtype=torch.float32)
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(lib.emd_sh_forward(n, int(degree), K, dirs.data_ptr(), coeffs.data_ptr(), rgb.data_ptr(), st), "emd_sh_forward")
+        L.launch("emd_sh_forward", n, int(degree), K, dirs.data_ptr(), coeffs.data_ptr(), rgb.data_ptr())
         ctx.degree = int(degree)
         ctx.save_for_backward(dirs, coeffs)
         return rgb
 
     @staticmethod
     def backward(ctx, g):
-        lib = L.load()
         dirs, coeffs = ctx.saved_tensors
         n, K = coeffs.shape[0], coeffs.shape[1]
         g = g.contiguous().float()
         d_coeffs = torch.empty_like(coeffs)
         d_dirs = torch.empty_like(dirs) if ctx.needs_input_grad[1] else None
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(lib.emd_sh_backward(n, ctx.degree, K, dirs.data_ptr(), coeffs.data_ptr(), g.data_ptr(), d_coeffs.data_ptr(),
-                                    L.ptr(d_dirs), st), "emd_sh_backward")
+        L.launch("emd_sh_backward", n, ctx.degree, K, dirs.data_ptr(), coeffs.data_ptr(), g.data_ptr(), d_coeffs.data_ptr(), L.ptr(d_dirs))
         return None, d_dirs, d_coeffs
 
 

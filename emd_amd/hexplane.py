@@ -46,9 +46,7 @@ class _HexLookup(torch.autograd.Function):
         plane_orders = order if isinstance(order, VisitingOrders) else None
         if plane_orders is not None:
             order = plane_orders.order
-        if pts.device.type != "cuda":
-            raise L.EmdError("HexPlane lookup needs tensors on a ROCm device; there is no CPU path")
-        lib = L.load()
+        L.need_device("HexPlane lookup", pts)
         S = len(planes) // 6
         Cc = planes[0].shape[1]
         N = pts.shape[0]
@@ -78,7 +76,7 @@ class _HexLookup(torch.autograd.Function):
             a.aabb[k] = aabb[k]
         out = torch.empty(N, S * Cc, device=pts.device, dtype=torch.float32)
         a.out = out.data_ptr()
-        L.check(lib.emd_hexplane_forward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_hexplane_forward")
+        L.launch("emd_hexplane_forward", C.byref(a))
         a.time_tables, a.out = None, None         # (forward-only pointers: `tables` and `out` are not kept alive by ctx, the backward reads neither)
         ctx.args, ctx.keep = a, (pts_c, times_c, cl, order, plane_orders)
         ctx.shapes = [tuple(p.shape) for p in planes]
@@ -87,7 +85,6 @@ class _HexLookup(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = L.load()
         a = ctx.args
         S, Cc = a.num_scales, a.channels
         g_out = g_out.contiguous().float()
@@ -129,8 +126,7 @@ class _HexLookup(torch.autograd.Function):
                 g.order2d[k], g.pos2d[k] = po.order2d[k].data_ptr(), po.pos2d[k].data_ptr()
             rows = torch.empty(bin(po.defer_mask).count("1") * 3 * a.num_points * Cc + 6 * a.num_points, device=g_out.device, dtype=torch.float32)
             g.defer_rows, g.defer_mask = rows.data_ptr(), po.defer_mask
-        L.check(lib.emd_hexplane_backward(C.byref(a), C.byref(g), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "emd_hexplane_backward")
+        L.launch("emd_hexplane_backward", C.byref(a), C.byref(g))
         if det is not None:
             det.det_state = _hex_det_views(det_ws, a, g.det_keep_plane) if (det_ws is not None and g.det_keep_plane) else None
         grads = [t.permute(2, 0, 1)[None] for t in gcl] if need_planes else [None] * len(ctx.shapes)   # channel-last, like the planes
@@ -142,9 +138,7 @@ class _PlaneReg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weights, *planes):
-        if any(p.device.type != "cuda" for p in planes):
-            raise L.EmdError("HexPlane regularisers need planes on a ROCm device; there is no CPU path")
-        lib = L.load()
+        L.need_device("plane_regulation", *planes)
         if not planes or len(planes) % 6 or any(p.dim() != 4 or p.shape[0] != 1 for p in planes):
             raise L.EmdError(f"plane regularisers: {len(planes)} planes, expected six [1, C, H, W] planes per scale")
         S, Cc, dev = len(planes) // 6, planes[0].shape[1], planes[0].device
@@ -168,10 +162,9 @@ class _PlaneReg(torch.autograd.Function):
                 a.planes[s][p] = g[p].data_ptr()
         out = torch.empty(4, device=dev, dtype=torch.float32)
         # the workgroups' partial sums: caller-owned, never cleared (a captured step takes it from the graph's pool)
-        ws = torch.empty(max(int(lib.emd_plane_reg_workspace_size(C.byref(a))), 8), device=dev, dtype=torch.uint8)
+        ws = torch.empty(max(int(L.load().emd_plane_reg_workspace_size(C.byref(a))), 8), device=dev, dtype=torch.uint8)
         a.out = out.data_ptr()
-        L.check(lib.emd_plane_reg_forward(C.byref(a), ws.data_ptr(), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "emd_plane_reg_forward")
+        L.launch("emd_plane_reg_forward", C.byref(a), ws.data_ptr(), ws.numel())
         a.out = None
         ctx.args, ctx.keep = a, cl
         ctx.shapes = [tuple(p.shape) for p in planes]
@@ -191,7 +184,7 @@ class _PlaneReg(torch.autograd.Function):
             a.dL_dplanes[i // 6][i % 6] = base + 4 * off
             off += c * h * w
         a.g = g_loss.data_ptr()
-        L.check(L.load().emd_plane_reg_backward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_plane_reg_backward")
+        L.launch("emd_plane_reg_backward", C.byref(a))
         return (None, *grads)
 
 
@@ -283,8 +276,7 @@ class VisitingOrders:
             # all four sort keys in one launch (emd_hexplane_order_keys); `morton_order` / `plane_order` are the same curves in torch ops
             # (~600 element-wise launches for the three Hilbert walks: 6 ms per refresh at 2 M points) and serve CPU tensors
             keys = torch.empty(4 * n, device=pts.device, dtype=torch.int32)
-            L.check(L.load().emd_hexplane_order_keys(pts.detach().contiguous().float().data_ptr(), aabb.detach().contiguous().float().data_ptr(), n,
-                                                     keys.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_hexplane_order_keys")
+            L.launch("emd_hexplane_order_keys", pts.detach().contiguous().float().data_ptr(), aabb.detach().contiguous().float().data_ptr(), n, keys.data_ptr())
             keys = keys.view(4, n)
         order = keys[0].argsort().to(torch.int32) if keys is not None else morton_order(pts, aabb)
         if not mask:

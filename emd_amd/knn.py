@@ -22,13 +22,8 @@ MAX_K = L.KNN_MAX_K
 EMBED_DIMS = (4, 8, 16, 32)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _points(points):
-    if not isinstance(points, torch.Tensor) or points.device.type != "cuda":
-        raise L.EmdError("knn needs a tensor on a ROCm device; there is no CPU path")
+    L.need_device("knn", points)
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"knn: points must be [N, 3], got {tuple(points.shape)}")
     return points.detach().contiguous().float()
@@ -50,7 +45,7 @@ def _knn_into(pts, k, idx, d2, mean, ws):
         raise ValueError(f"knn: {n} points x {k} neighbours is outside the supported range")
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=pts.device)
-    L.check(L.load().emd_knn(n, k, pts.data_ptr(), L.ptr(idx), L.ptr(d2), L.ptr(mean), ws.data_ptr(), ws.numel(), _stream()), "emd_knn")
+    L.launch("emd_knn", n, k, pts.data_ptr(), L.ptr(idx), L.ptr(d2), L.ptr(mean), ws.data_ptr(), ws.numel())
     return ws
 
 
@@ -84,8 +79,7 @@ def _segments(segment_start, pts):
 
 
 def _knn_segments_into(pts, seg, k, idx, d2):
-    L.check(L.load().emd_knn_segments(pts.shape[0], seg.numel() - 1, k, pts.data_ptr(), seg.data_ptr(), L.ptr(idx), L.ptr(d2), _stream()),
-            "emd_knn_segments")
+    L.launch("emd_knn_segments", pts.shape[0], seg.numel() - 1, k, pts.data_ptr(), seg.data_ptr(), L.ptr(idx), L.ptr(d2))
 
 
 def knn_segments(points, segment_start, k):
@@ -130,7 +124,6 @@ class KnnTable:
         if segment_start is not None:
             self.segment_start = segment_start
         n, k, dev = pts.shape[0], self.k, pts.device
-        lib = L.load()
         if n != self.N or self.idx.device != dev:
             self.idx = torch.empty(n, k, dtype=torch.int32, device=dev)
             self.d2 = torch.empty(n, k, dtype=torch.float32, device=dev)
@@ -145,11 +138,11 @@ class KnnTable:
             self._ws = _knn_into(pts, k, self.idx, self.d2, None, self._ws)
         else:
             _knn_segments_into(pts, _segments(self.segment_start, pts), k, self.idx, self.d2)
-        need = lib.emd_knn_reverse_workspace(n, k)
+        need = L.load().emd_knn_reverse_workspace(n, k)
         if self._rev_ws is None or self._rev_ws.numel() < need:
             self._rev_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        L.check(lib.emd_knn_reverse(n, k, self.idx.data_ptr(), self.rev_start.data_ptr(), self.rev_slot.data_ptr(), self._rev_ws.data_ptr(),
-                                    self._rev_ws.numel(), _stream()), "emd_knn_reverse")
+        L.launch("emd_knn_reverse", n, k, self.idx.data_ptr(), self.rev_start.data_ptr(), self.rev_slot.data_ptr(), self._rev_ws.data_ptr(),
+                 self._rev_ws.numel())
         if self.weight_fn is None:
             self.w, self._unit = torch.ones(n, k, dtype=torch.float32, device=dev), True
         else:
@@ -168,8 +161,7 @@ class KnnTable:
 
 
 def _check_table(e, table):
-    if not isinstance(e, torch.Tensor) or e.device.type != "cuda":
-        raise L.EmdError("embedding_reg needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("embedding_reg", e)
     if e.dim() != 2 or e.shape[1] not in EMBED_DIMS:
         raise ValueError(f"embedding_reg: the embedding must be [N, E] with E in {EMBED_DIMS}, got {tuple(e.shape)}")
     if e.shape[0] != table.N:
@@ -182,17 +174,17 @@ def _check_table(e, table):
 def embed_reg_forward(e, table):
     """-> [2] device tensor: (loss, 1 / number of pairs).  `e` fp32 contiguous [N,E]."""
     out = torch.empty(2, dtype=torch.float32, device=e.device)
-    L.check(L.load().emd_embed_reg_forward(table.N, table.k, e.shape[1], e.data_ptr(), table.idx.data_ptr(), table._w_ptr(), L.ptr(table.factors),
-                                           out.data_ptr(), table._scratch.data_ptr(), _stream()), "emd_embed_reg_forward")
+    L.launch("emd_embed_reg_forward", table.N, table.k, e.shape[1], e.data_ptr(), table.idx.data_ptr(), table._w_ptr(), L.ptr(table.factors),
+             out.data_ptr(), table._scratch.data_ptr())
     return out
 
 
 def embed_reg_backward(e, table, fwd, g, grad_e, accumulate=False):
     """grad_e (+)= g * dloss/de with `fwd` the forward's result for the same `e` and `g` a one-element device tensor; `accumulate=True` adds
     into `grad_e` (e.g. the buffer the rasterizer's gradients land in) instead of overwriting it."""
-    L.check(L.load().emd_embed_reg_backward(table.N, table.k, e.shape[1], e.data_ptr(), table.idx.data_ptr(), table._w_ptr(), L.ptr(table.factors),
-                                            table.rev_start.data_ptr(), table.rev_slot.data_ptr(), g.data_ptr(), fwd.data_ptr() + 4, grad_e.data_ptr(),
-                                            1 if accumulate else 0, _stream()), "emd_embed_reg_backward")
+    L.launch("emd_embed_reg_backward", table.N, table.k, e.shape[1], e.data_ptr(), table.idx.data_ptr(), table._w_ptr(), L.ptr(table.factors),
+             table.rev_start.data_ptr(), table.rev_slot.data_ptr(), g.data_ptr(), fwd.data_ptr() + 4, grad_e.data_ptr(),
+             1 if accumulate else 0)
     return grad_e
 
 
@@ -241,7 +233,7 @@ class _NeighbourStd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, acts, weights, *blocks):
-        lib, dev = L.load(), table.idx.device
+        dev = table.idx.device
         xs = [x.detach().reshape(x.shape[0], _cols(x)).contiguous().float() for x in blocks]
         a = _nstd_args(table, xs, acts, weights)
         active = sum(x.shape[1] for x, w in zip(xs, weights) if w != 0.0)
@@ -249,9 +241,9 @@ class _NeighbourStd(torch.autograd.Function):
         terms = torch.empty(len(xs), dtype=torch.float32, device=dev)
         if table._nstd_ws is None or table._nstd_ws.device != dev:
             # the ticket at its head is zero between calls; a hipGraph recorded with this table has the address baked in
-            table._nstd_ws = torch.zeros(int(lib.emd_neighbour_std_workspace_size()), dtype=torch.uint8, device=dev)
+            table._nstd_ws = torch.zeros(int(L.load().emd_neighbour_std_workspace_size()), dtype=torch.uint8, device=dev)
         a.stash, a.terms = stash.data_ptr(), terms.data_ptr()
-        L.check(lib.emd_neighbour_std_forward(C.byref(a), table._nstd_ws.data_ptr(), table._nstd_ws.numel(), _stream()), "emd_neighbour_std_forward")
+        L.launch("emd_neighbour_std_forward", C.byref(a), table._nstd_ws.data_ptr(), table._nstd_ws.numel())
         ctx.save_for_backward(stash, *xs)
         ctx.table, ctx.acts, ctx.weights, ctx.shapes = table, acts, weights, [x.shape for x in blocks]
         return terms
@@ -268,7 +260,7 @@ class _NeighbourStd(torch.autograd.Function):
         for b, d in enumerate(grads):
             a.dx[b] = L.ptr(d)
         a.stash, a.g_terms = stash.data_ptr(), g.data_ptr()
-        L.check(L.load().emd_neighbour_std_backward(C.byref(a), _stream()), "emd_neighbour_std_backward")
+        L.launch("emd_neighbour_std_backward", C.byref(a))
         return (None, None, None) + tuple(None if d is None else d.reshape(s) for d, s in zip(grads, ctx.shapes))
 
 
@@ -280,9 +272,7 @@ def neighbour_std(blocks, table, weights, activations):
     records into a hipGraph.  Values and gradients are bit-identical from run to run (the contract: EmdNeighbourStdArgs, include/emd_raster.h).
     No gradient flows to the table or the positions."""
     blocks = list(blocks)
-    for x in blocks:
-        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-            raise L.EmdError("neighbour_std needs tensors on a ROCm device; there is no CPU path (the checker's restatement is tests/neighbour_std_ref.py)")
+    L.need_device("neighbour_std (the checker's restatement is tests/neighbour_std_ref.py)", *blocks)
     if not 1 <= len(blocks) <= L.NSTD_MAX_BLOCKS:
         raise ValueError(f"neighbour_std: 1 .. {L.NSTD_MAX_BLOCKS} blocks, got {len(blocks)}")
     if len(weights) != len(blocks) or len(activations) != len(blocks):

@@ -15,9 +15,7 @@ from . import _lib as L
 class _ImageLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt, depth, gt_depth, mask, weight, sky_mask, lam_dssim, lam_depth, lam_sky, max_depth):
-        if image.device.type != "cuda":
-            raise L.EmdError("image_loss needs tensors on a ROCm device; there is no CPU path")
-        lib = L.load()
+        L.need_device("image_loss", image)
         dev = image.device
         H, W = image.shape[-2:]
         f = lambda t: None if t is None else t.detach().contiguous().float()
@@ -41,10 +39,9 @@ class _ImageLoss(torch.autograd.Function):
         g_dep = torch.empty_like(depth_c) if (depth is not None and need[2]) else None
         g_wgt = (torch.empty_like(weight_c) if weight_c is not None else torch.zeros_like(f(weight))) if (weight is not None and need[5]) else None
         a.dL_dimage, a.dL_ddepth, a.dL_dweight = L.ptr(g_img), L.ptr(g_dep), L.ptr(g_wgt)
-        nbytes = lib.emd_image_loss_workspace(H, W)
+        nbytes = L.load().emd_image_loss_workspace(H, W)
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        L.check(lib.emd_image_loss(C.byref(a), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "emd_image_loss")
+        L.launch("emd_image_loss", C.byref(a), ws.data_ptr(), nbytes)
         ctx.save_for_backward(g_img, g_dep, g_wgt)
         ctx.shapes = (image.shape, None if depth is None else depth.shape, None if weight is None else weight.shape)
         ctx.mark_non_differentiable(losses)

@@ -38,10 +38,6 @@ def _alloc_grads(numel, dev):
     return torch.zeros(numel, device=dev, dtype=torch.float32)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def eligible(ka, kb, hidden_shapes, out_dims):
     """The shapes csrc/mlp.hip serves: width 64 everywhere, ka a multiple of 4 up to 128, kb <= 8, out_dim <= 64, at most six heads."""
     return (0 <= ka <= 128 and ka % 4 == 0 and 0 <= kb <= 8 and ka + kb > 0 and all(tuple(s) == (WIDTH, WIDTH) for s in hidden_shapes) and
@@ -71,14 +67,14 @@ class _DetJobs:
         self.jobs.append(dict(offset=off + lay["offset"][tensor_id], groups=lay["groups"], pitch=lay["pitch"][tensor_id], rows=rows, cols=cols,
                               ld=dst.shape[-1] if rows > 1 else cols, col0=col0, scale=scale, dst=dst))
 
-    def reduce(self, lib):
+    def reduce(self):
         if not self.jobs:
             return
         arr = (L.EmdMlpDetJob * len(self.jobs))()
         for a, j in zip(arr, self.jobs):
             a.slab, a.dst = self.slab.data_ptr() + j["offset"], j["dst"].data_ptr()
             a.groups, a.pitch, a.rows, a.cols, a.ld, a.col0, a.scale = j["groups"], j["pitch"], j["rows"], j["cols"], j["ld"], j["col0"], j["scale"]
-        L.check(lib.emd_mlp_det_reduce(arr, len(self.jobs), _stream()), "emd_mlp_det_reduce")
+        L.launch("emd_mlp_det_reduce", arr, len(self.jobs))
         if DET_TRACE is not None:
             DET_TRACE.append(dict(direction=self.direction, slab=self.slab, jobs=self.jobs))
 
@@ -88,11 +84,9 @@ class _LevelMLP(torch.autograd.Function):
     def forward(ctx, spec, xa, xb, w0, b_eff, *params):
         """spec = (col_a, col_b, ((relu_input, depth, out_dim), ...), l1_heads, deterministic); params = per branch: (w_h, b_h) x depth, w_out, b_out.
         l1_heads: indices of the heads whose regulariser mean |out| is returned behind the outputs (formed by the head's own kernels)."""
-        lib = L.load()
         col_a, col_b, branches, l1_heads, det = spec
         dev = w0.device
-        if dev.type != "cuda":
-            raise L.EmdError("level_mlp needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("level_mlp", w0)
         f = lambda t: None if t is None else t.detach().contiguous().float()
         xa_c, xb_c, w0_c, b_c = f(xa), f(xb), f(w0), f(b_eff)
         params_c = [f(p) for p in params]
@@ -107,7 +101,7 @@ class _LevelMLP(torch.autograd.Function):
         t.col_a, t.col_b = int(col_a), int(col_b)
         t.xa, t.xb, t.w, t.b, t.h = L.ptr(xa_c), L.ptr(xb_c), w0_c.data_ptr(), b_c.data_ptr(), L.ptr(h)
         if not recompute:
-            L.check(lib.emd_mlp_trunk_forward(C.byref(t), _stream()), "emd_mlp_trunk_forward")
+            L.launch("emd_mlp_trunk_forward", C.byref(t))
         outs, structs, i = [], [], 0
         l1 = torch.zeros(max(len(l1_heads), 1), device=dev, dtype=torch.float32)
         todo = []
@@ -128,16 +122,16 @@ class _LevelMLP(torch.autograd.Function):
             if det and k in l1_heads and N > 0:
                 todo.append((k, b))            # (after the loop: the slabs of every regularised head are one allocation)
             else:
-                L.check(lib.emd_mlp_branch_forward(C.byref(b), _stream()), "emd_mlp_branch_forward")
+                L.launch("emd_mlp_branch_forward", C.byref(b))
             outs.append(out)
             structs.append(b)
         if todo:
             jobs = _DetJobs("forward", dev, [L.mlp_det_layout(L.MLP_DET_BRANCH_FWD, b) for _, b in todo])
             for k, b in todo:
                 _, p, nbytes = jobs.take()
-                L.check(lib.emd_mlp_branch_forward_det(C.byref(b), p, nbytes, _stream()), "emd_mlp_branch_forward_det")
+                L.launch("emd_mlp_branch_forward_det", C.byref(b), p, nbytes)
                 jobs.add(0, l1[l1_heads.index(k):l1_heads.index(k) + 1], 1, 1, scale=1.0 / (float(N) * float(b.out_dim)))
-            jobs.reduce(lib)
+            jobs.reduce()
         ctx.spec, ctx.trunk, ctx.structs, ctx.N = spec, t, structs, N
         ctx.set_materialize_grads(False)        # a head nobody uses costs no backward launch and leaves its parameters' .grad at None
         ctx.has = (xa is not None, xb is not None)
@@ -147,7 +141,6 @@ class _LevelMLP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g_outs):
-        lib = L.load()
         xa_c, xb_c, w0_c, b_c, h, *rest = ctx.saved_tensors
         params_c, l1_outs = rest[:ctx.num_params], rest[ctx.num_params:]
         col_a, col_b, branches, l1_heads, det = ctx.spec
@@ -196,7 +189,7 @@ class _LevelMLP(torch.autograd.Function):
                 if det:
                     launches.append((b, g, i))
                 else:
-                    L.check(lib.emd_mlp_branch_backward(C.byref(b), C.byref(g), _stream()), "emd_mlp_branch_backward")
+                    L.launch("emd_mlp_branch_backward", C.byref(b), C.byref(g))
                 if not chained:
                     g_hs.append(g_h)
             i += n_par
@@ -212,7 +205,7 @@ class _LevelMLP(torch.autograd.Function):
                 d_xb = torch.empty_like(xb_c)
             tg.d_xa, tg.d_xb, tg.d_w, tg.d_b = L.ptr(d_xa), L.ptr(d_xb), d_w0.data_ptr(), d_b.data_ptr()
             if not det:
-                L.check(lib.emd_mlp_trunk_backward(C.byref(ctx.trunk), C.byref(tg), _stream()), "emd_mlp_trunk_backward")
+                L.launch("emd_mlp_trunk_backward", C.byref(ctx.trunk), C.byref(tg))
             else:
                 # ONE slab (torch.empty: every workgroup writes its whole slot) for the heads and the trunk, then the one reduction of the level
                 t = ctx.trunk
@@ -220,20 +213,20 @@ class _LevelMLP(torch.autograd.Function):
                                 [L.mlp_det_layout(L.MLP_DET_TRUNK_BWD, t, tg)])
                 for b, g, i0 in launches:
                     _, p, nbytes = jobs.take()
-                    L.check(lib.emd_mlp_branch_backward_det(C.byref(b), C.byref(g), p, nbytes, _stream()), "emd_mlp_branch_backward_det")
+                    L.launch("emd_mlp_branch_backward_det", C.byref(b), C.byref(g), p, nbytes)
                     for d in range(b.depth):
                         jobs.add(2 * d, d_params[i0 + 2 * d], WIDTH, WIDTH)
                         jobs.add(2 * d + 1, d_params[i0 + 2 * d + 1], 1, WIDTH)
                     jobs.add(4, d_params[i0 + 2 * b.depth], b.out_dim, WIDTH)
                     jobs.add(5, d_params[i0 + 2 * b.depth + 1], 1, b.out_dim)
                 _, p, nbytes = jobs.take()
-                L.check(lib.emd_mlp_trunk_backward_det(C.byref(t), C.byref(tg), p, nbytes, _stream()), "emd_mlp_trunk_backward_det")
+                L.launch("emd_mlp_trunk_backward_det", C.byref(t), C.byref(tg), p, nbytes)
                 if t.ka:
                     jobs.add(0, d_w0, WIDTH, t.ka, col0=t.col_a)
                 if t.kb:
                     jobs.add(1, d_w0, WIDTH, t.kb, col0=t.col_b)
                 jobs.add(2, d_b, 1, WIDTH)
-                jobs.reduce(lib)
+                jobs.reduce()
         if not g_hs:
             d_w0 = d_b = None
         return (None, d_xa, d_xb, d_w0, d_b, *[None if k in unused else p for k, p in enumerate(d_params)])

@@ -96,8 +96,7 @@ def density_control(model: "StreetGaussians", xyz_gradient_accum, denom, max_rad
     from . import _lib as L
     from .density import EventRows, restructure_rows
     dev, N = model._xyz.device, model._xyz.shape[0]
-    if dev.type != "cuda":
-        raise L.EmdError("density_control needs the store on a ROCm device; there is no CPU path")
+    L.need_device("density_control", model._xyz)
     n_dyn = int((model.actor_id >= 0).sum()) if model.has_actors else 0
     if model.has_actors and n_dyn and not bool((model.actor_id[:n_dyn] >= 0).all()):
         raise ValueError("density_control expects the actors' points in front of the background's (the reference's node order)")
@@ -396,14 +395,12 @@ _l1_scratch = {}
 def _l1_call(n, a_ptr, b_ptr, loss, grad_ptr):
     """emd_l1_loss_ws with the per-(device, stream) scratch table: no zero-fill launch in front of the kernel.  The table is created (zeroed)
     outside of stream capture only -- a capture that meets a stream for the first time uses the plain entry point."""
-    import ctypes as C
     from . import _lib as L
-    st = torch.cuda.current_stream()
-    key = (loss.device.index, st.cuda_stream)
+    key = (loss.device.index, torch.cuda.current_stream().cuda_stream)
     sc = _l1_scratch.get(key)
     if sc is None and not torch.cuda.is_current_stream_capturing():
         sc = _l1_scratch[key] = torch.zeros(1024, dtype=torch.int32, device=loss.device)       # EMD_L1_SCRATCH_WORDS
-    L.check(L.load().emd_l1_loss_ws(n, a_ptr, b_ptr, loss.data_ptr(), grad_ptr, L.ptr(sc), C.c_void_p(st.cuda_stream)), "emd_l1_loss")
+    L.launch("emd_l1_loss_ws", n, a_ptr, b_ptr, loss.data_ptr(), grad_ptr, L.ptr(sc))
 
 
 def _aligned(t):
@@ -417,10 +414,8 @@ def _aligned(t):
 class _L1Loss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
-        import ctypes as C
         from . import _lib as L
-        if a.device.type != "cuda":
-            raise L.EmdError("l1_loss needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("l1_loss", a)
         a, b = _aligned(a), _aligned(b)
         loss = torch.empty(1, device=a.device, dtype=torch.float32)
         grad = torch.empty_like(a) if ctx.needs_input_grad[0] else None
@@ -455,10 +450,8 @@ def unit_gradient(device):
 class _AbsMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        import ctypes as C
         from . import _lib as L
-        if x.device.type != "cuda":
-            raise L.EmdError("abs_mean needs a tensor on a ROCm device; there is no CPU path")
+        L.need_device("abs_mean", x)
         xc = _aligned(x.detach().float())
         out = torch.empty(1, device=x.device, dtype=torch.float32)
         _l1_call(xc.numel(), xc.data_ptr(), None, out, None)
@@ -468,13 +461,11 @@ class _AbsMean(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
         from . import _lib as L
         (xc,) = ctx.saved_tensors
         grad = torch.empty_like(xc)
         gc = g.detach().reshape(1).float().contiguous()
-        L.check(L.load().emd_abs_mean_backward(xc.numel(), xc.data_ptr(), gc.data_ptr(), grad.data_ptr(),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_abs_mean_backward")
+        L.launch("emd_abs_mean_backward", xc.numel(), xc.data_ptr(), gc.data_ptr(), grad.data_ptr())
         return grad.view(ctx.shape)
 
 
@@ -492,10 +483,8 @@ class _ResidualPairL1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xa, xb):
-        import ctypes as C
         from . import _lib as L
-        if xa.device.type != "cuda":
-            raise L.EmdError("residual_pair_l1 needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("residual_pair_l1", xa)
         if xa.shape != xb.shape:
             raise ValueError("residual_pair_l1: the two residuals must have one shape")
         a, b = _aligned(xa.detach().float()), _aligned(xb.detach().float())
@@ -507,7 +496,6 @@ class _ResidualPairL1(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, up_a, up_b, g_a, g_b):
-        import ctypes as C
         from . import _lib as L
         a, b = ctx.saved_tensors
         same = up_a is not None and up_b is not None and (up_a is up_b or (up_a.data_ptr() == up_b.data_ptr() and up_a.stride() == up_b.stride()))
@@ -516,9 +504,8 @@ class _ResidualPairL1(torch.autograd.Function):
         ga = None if g_a is None else g_a.detach().reshape(1).float().contiguous()
         gb = None if g_b is None else g_b.detach().reshape(1).float().contiguous()
         grad_a, grad_b = torch.empty_like(a), torch.empty_like(b)
-        L.check(L.load().emd_residual_l1_backward(a.numel(), L.ptr(ua), L.ptr(ub), a.data_ptr(), b.data_ptr(), L.ptr(ga), L.ptr(gb),
-                                                  grad_a.data_ptr(), grad_b.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                "emd_residual_l1_backward")
+        L.launch("emd_residual_l1_backward", a.numel(), L.ptr(ua), L.ptr(ub), a.data_ptr(), b.data_ptr(), L.ptr(ga), L.ptr(gb),
+                 grad_a.data_ptr(), grad_b.data_ptr())
         return grad_a, grad_b
 
 

@@ -27,10 +27,6 @@ from . import _lib as L
 DET_TRACE = None
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _alloc_det_ws(nbytes, dev):
     """The workspace of one deterministic call of the actor chain: never cleared.  A function of its own so that a test can put guard bands around it."""
     return torch.empty(nbytes, device=dev, dtype=torch.uint8)
@@ -192,9 +188,7 @@ class TrackOffsetHeads(torch.nn.Module):
         """-> (track_trans [A,3], track_rot [A,4]).  embeddings [n,4] of the actor Gaussians; point_ids [n] their actor (device
         tensors).  One HIP launch (+ the per-actor embedding sums) forward and one backward for all actors and both levels
         (`emd_track_heads_forward/backward`); no host synchronisation: the frame time is a by-value scalar."""
-        if self.weight.device.type != "cuda":
-            raise L.EmdError("TrackOffsetHeads needs its parameters on a ROCm device; there is no CPU path "
-                             "(the checker's restatement is oracle/torch_ref.track_offsets)")
+        L.need_device("TrackOffsetHeads (the checker's restatement is oracle/torch_ref.track_offsets)", self.weight)
         ids32, cnt, seg = self._prepare_ids(point_ids)
         t, k_f = self._time_and_k(frame, num_frames, step)
         return _TrackHeads.apply(self.weight, embeddings, self.track_trans_c.weight, self.track_trans_c.bias, self.track_trans_f.weight,
@@ -205,8 +199,7 @@ class TrackOffsetHeads(torch.nn.Module):
         """The frame's [A,12] pose table WITH the learned offsets, the whole per-actor chain (embedding sums -> heads -> pose row) in
         ONE launch each way (`emd_tracked_pose_forward/backward`) when an actor's points are contiguous (the reference's layout) and
         the embedding is at most 8 wide; otherwise the three-launch path `actor_pose_table(..., *self(...))`.  Same values either way."""
-        if self.weight.device.type != "cuda":
-            raise L.EmdError("TrackOffsetHeads needs its parameters on a ROCm device; there is no CPU path")
+        L.need_device("TrackOffsetHeads", self.weight)
         ids32, cnt, seg = self._prepare_ids(point_ids)
         num_frames = instances_quats.shape[0]
         if seg is None or embeddings.shape[1] > 8 or embeddings.shape[1] == 0:
@@ -253,9 +246,9 @@ class _TrackHeads(torch.autograd.Function):
             ws = None
             if E > 0 and emb_c.shape[0] > 0 and (seg is None or E > 8):
                 ws = torch.empty(L.track_det_workspace_size(A, 0, emb_c.shape[0], E), device=dev, dtype=torch.uint8)
-            L.check(L.load().emd_track_heads_forward_det(C.byref(a), L.ptr(ws), 0 if ws is None else ws.numel(), _stream()), "emd_track_heads_forward_det")
+            L.launch("emd_track_heads_forward_det", C.byref(a), L.ptr(ws), 0 if ws is None else ws.numel())
         else:
-            L.check(L.load().emd_track_heads_forward(C.byref(a), _stream()), "emd_track_heads_forward")
+            L.launch("emd_track_heads_forward", C.byref(a))
         ctx.save_for_backward(weight_c, emb_c, ids32, cnt, emb_sum, *heads)
         ctx.scal, ctx.seg, ctx.deterministic = (t, k_c, k_f), seg, bool(deterministic)
         return trans, rot
@@ -282,9 +275,9 @@ class _TrackHeads(torch.autograd.Function):
         if ctx.deterministic:
             ws = _alloc_det_ws(L.track_det_workspace_size(A, weight.shape[2] + E), dev)
             _trace_det("heads", ws, A, weight.shape[2] + E)
-            L.check(L.load().emd_track_heads_backward_det(C.byref(a), C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "emd_track_heads_backward_det")
+            L.launch("emd_track_heads_backward_det", C.byref(a), C.byref(g), ws.data_ptr(), ws.numel())
         else:
-            L.check(L.load().emd_track_heads_backward(C.byref(a), C.byref(g), _stream()), "emd_track_heads_backward")
+            L.launch("emd_track_heads_backward", C.byref(a), C.byref(g))
         return (d_weight, d_emb, *d_heads, None, None, None, None, None, None, None)
 
 
@@ -307,7 +300,7 @@ class _TrackedPose(torch.autograd.Function):
         # (deterministic: no accumulator -- the backward stores per actor and reduces: emd_tracked_pose_backward_det)
         head_acc = torch.empty(sum(h.numel() for h in heads), device=dev) if any(ctx.needs_input_grad[:10]) and not deterministic else None
         p = _TrackedPose._args(weight_c, emb_c, heads, ids32, cnt, seg, t, k_c, k_f, emb_sum, q_c, t_c, valid, frame, pose, head_acc)
-        L.check(L.load().emd_tracked_pose_forward(C.byref(p), _stream()), "emd_tracked_pose_forward")
+        L.launch("emd_tracked_pose_forward", C.byref(p))
         ctx.save_for_backward(weight_c, emb_c, ids32, cnt, seg, emb_sum, q_c, t_c, *heads)
         ctx.scal, ctx.valid, ctx.head_acc, ctx.acc_used = (t, k_c, k_f, frame), valid, head_acc, False
         ctx.shapes, ctx.deterministic = (q_all.shape, t_all.shape), bool(deterministic)
@@ -356,9 +349,9 @@ class _TrackedPose(torch.autograd.Function):
         if ctx.deterministic:
             ws = _alloc_det_ws(L.track_det_workspace_size(A, width), dev)
             _trace_det("pose", ws, A, width)
-            L.check(L.load().emd_tracked_pose_backward_det(C.byref(p), C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "emd_tracked_pose_backward_det")
+            L.launch("emd_tracked_pose_backward_det", C.byref(p), C.byref(g), ws.data_ptr(), ws.numel())
         else:
-            L.check(L.load().emd_tracked_pose_backward(C.byref(p), C.byref(g), _stream()), "emd_tracked_pose_backward")
+            L.launch("emd_tracked_pose_backward", C.byref(p), C.byref(g))
         return (d_weight, d_emb, *d_heads, d_q.view(ctx.shapes[0]), d_t.view(ctx.shapes[1]), *([None] * 9))
 
 
@@ -399,9 +392,7 @@ class _ActorPose(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, instances_quats, instances_trans, instances_fv, frame, track_trans, track_rot):
-        lib = L.load()
-        if instances_quats.device.type != "cuda":
-            raise L.EmdError("actor_pose_table needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("actor_pose_table", instances_quats)
         on_dev = _frame_on_device(frame, instances_quats.device)
         if on_dev:
             q_f, t_f = instances_quats.detach().contiguous(), instances_trans.detach().contiguous()
@@ -412,15 +403,14 @@ class _ActorPose(torch.autograd.Function):
             valid = None if instances_fv is None else instances_fv[frame].contiguous().view(torch.uint8)   # bool bytes, no copy kernel
             A = q_f.shape[0]
         pose = torch.empty(A, L.ACTOR_STRIDE, device=q_f.device, dtype=torch.float32)
-        L.check(lib.emd_actor_pose_forward(A, q_f.data_ptr(), t_f.data_ptr(), L.ptr(valid), L.ptr(track_trans), L.ptr(track_rot),
-                                           pose.data_ptr(), frame.data_ptr() if on_dev else None, _stream()), "emd_actor_pose_forward")
+        L.launch("emd_actor_pose_forward", A, q_f.data_ptr(), t_f.data_ptr(), L.ptr(valid), L.ptr(track_trans), L.ptr(track_rot),
+                 pose.data_ptr(), frame.data_ptr() if on_dev else None)
         ctx.frame, ctx.shapes = (frame if on_dev else int(frame)), (instances_quats.shape, instances_trans.shape)
         ctx.save_for_backward(q_f, track_trans, track_rot)
         return pose
 
     @staticmethod
     def backward(ctx, g_pose):
-        lib = L.load()
         q_f, track_trans, track_rot = ctx.saved_tensors
         on_dev = isinstance(ctx.frame, torch.Tensor)
         A = q_f.shape[1] if on_dev else q_f.shape[0]
@@ -430,9 +420,8 @@ class _ActorPose(torch.autograd.Function):
         d_dt = torch.empty_like(track_trans) if track_trans is not None else None
         d_dq = torch.empty_like(track_rot) if track_rot is not None else None
         dq_row, dt_row = (d_q, d_t) if on_dev else (d_q[ctx.frame], d_t[ctx.frame])
-        L.check(lib.emd_actor_pose_backward(A, q_f.data_ptr(), L.ptr(track_trans), L.ptr(track_rot), g_pose.contiguous().data_ptr(),
-                                            dq_row.data_ptr(), dt_row.data_ptr(), L.ptr(d_dt), L.ptr(d_dq),
-                                            ctx.frame.data_ptr() if on_dev else None, _stream()), "emd_actor_pose_backward")
+        L.launch("emd_actor_pose_backward", A, q_f.data_ptr(), L.ptr(track_trans), L.ptr(track_rot), g_pose.contiguous().data_ptr(),
+                 dq_row.data_ptr(), dt_row.data_ptr(), L.ptr(d_dt), L.ptr(d_dq), ctx.frame.data_ptr() if on_dev else None)
         return d_q, d_t, None, None, d_dt, d_dq
 
 
@@ -447,23 +436,19 @@ def actor_pose_table(instances_quats, instances_trans, instances_fv, frame, trac
 class _MotionTransform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, opacities, actor_pose, residual_dx, residual_dq, actor_ids, deterministic=False):
-        lib = L.load()
         ctx.deterministic = bool(deterministic)
-        if means.device.type != "cuda":
-            raise L.EmdError("transform_gaussians needs tensors on a ROCm device; there is no CPU path")
+        L.need_device("transform_gaussians", means)
         N = means.shape[0]
         wm = torch.empty_like(means)
         wq = torch.empty_like(quats) if quats is not None else None
         wo = torch.empty_like(opacities) if opacities is not None else None
         m = L.EmdMotion(L.ptr(actor_ids), L.ptr(actor_pose), int(actor_pose.shape[0]), L.ptr(residual_dx), L.ptr(residual_dq))
-        L.check(lib.emd_motion_forward(N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), wm.data_ptr(),
-                                       L.ptr(wq), L.ptr(wo), _stream()), "emd_motion_forward")
+        L.launch("emd_motion_forward", N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), wm.data_ptr(), L.ptr(wq), L.ptr(wo))
         ctx.save_for_backward(means, quats, opacities, actor_pose, residual_dx, residual_dq, actor_ids)
         return wm, wq, wo
 
     @staticmethod
     def backward(ctx, g_wm, g_wq, g_wo):
-        lib = L.load()
         means, quats, opacities, actor_pose, residual_dx, residual_dq, actor_ids = ctx.saved_tensors
         N = means.shape[0]
         c = lambda t: None if t is None else t.contiguous()
@@ -479,14 +464,13 @@ class _MotionTransform(torch.autograd.Function):
             # the pose gradient summed per actor in a pinned order (emd_motion_backward_det); the workspace comes from torch's
             # allocator (512-byte aligned; under capture from the graph's pool), no host synchronisation
             ws = torch.empty(L.motion_det_workspace_size(N), device=means.device, dtype=torch.uint8)
-            L.check(lib.emd_motion_backward_det(N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
-                                                L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
-                                                d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq), ws.data_ptr(), ws.numel(), _stream()),
-                    "emd_motion_backward_det")
+            L.launch("emd_motion_backward_det", N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
+                     L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
+                     d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq), ws.data_ptr(), ws.numel())
         else:
-            L.check(lib.emd_motion_backward(N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
-                                            L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
-                                            d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq), _stream()), "emd_motion_backward")
+            L.launch("emd_motion_backward", N, means.data_ptr(), L.ptr(quats), L.ptr(opacities), C.byref(m), L.ptr(g_wm),
+                     L.ptr(g_wq), L.ptr(g_wo), d_means.data_ptr(), L.ptr(d_quats), L.ptr(d_opac),
+                     d_pose.data_ptr(), L.ptr(d_rdx), L.ptr(d_rdq))
         return d_means, d_quats, d_opac, d_pose, d_rdx, d_rdq, None, None
 
 

@@ -388,7 +388,7 @@ class _VanillaGaussians(torch.autograd.Function):
         opac, scales, quats_out, rgbs = new(n, 1), new(n, 3), new(n, 4), new(n, 3)
         mask = torch.empty(n, device=dev, dtype=torch.uint8)
         a.opacities, a.scales, a.quats_out, a.rgbs, a.clamp_mask = opac.data_ptr(), scales.data_ptr(), quats_out.data_ptr(), rgbs.data_ptr(), mask.data_ptr()
-        L.check(L.load().emd_vanilla_forward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_vanilla_forward")
+        L.launch("emd_vanilla_forward", C.byref(a))
         ctx.save_for_backward(means, quats, opacity_logits, log_scales, features_dc, features_rest, camera_center, mask)
         ctx.cfg = (int(degree), int(sh_mode))
         ctx.set_materialize_grads(False)                     # an output nobody used arrives as None and goes in as NULL
@@ -413,7 +413,7 @@ class _VanillaGaussians(torch.autograd.Function):
         out = [torch.empty_like(t) if need[k] else None for k, t in ((1, quats), (2, opacity_logits), (3, log_scales), (4, features_dc), (5, features_rest))]
         a.dL_dquats, a.dL_dopacity_logits, a.dL_dlog_scales, a.dL_dfeatures_dc = (L.ptr(t) for t in out[:4])
         a.dL_dfeatures_rest = L.ptr(out[4]) if M > 1 else None
-        L.check(L.load().emd_vanilla_backward(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_vanilla_backward")
+        L.launch("emd_vanilla_backward", C.byref(a))
         return (None, *out, None, None, None)
 
 
@@ -423,8 +423,7 @@ def vanilla_gaussians(means, quats, opacity_logits, log_scales, features_dc, fea
     SH colour of degree n = min(step // sh_degree_interval, sh_degree) on the detached directions means - camera_center, + 0.5, clamped to [0, 1];
     sh_degree == 0: sigmoid(features_dc).  camera_center [3] stays on the device.  With check_finite off the call makes no host synchronisation
     and can be captured into a graph.  The upstream gradients may be views at any row offset (a torch.cat of this dictionary behind other rows)."""
-    if means.device.type != "cuda":
-        raise L.EmdError("vanilla_gaussians needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("vanilla_gaussians", means)
     if log_scales.dim() != 2 or log_scales.shape[1] != 3:
         raise NotImplementedError("ball gaussians ([N,1] scales) are not served")
     n = min(step // sh_degree_interval, sh_degree)

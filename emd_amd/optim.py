@@ -84,7 +84,6 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = L.load()
         batch, keep = [], []
         cap = self.capturable
         if cap:
@@ -103,7 +102,7 @@ class Adam(torch.optim.Optimizer):
                 t = a.tensors[i]
                 (t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel, t.step_size, t.bias_correction2_sqrt, t.one_minus_beta1, t.beta2,
                  t.one_minus_beta2, t.eps, t.step_dev, t.lr_dev) = d
-            L.check(lib.emd_adam_step(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "emd_adam_step")
+            L.launch("emd_adam_step", C.byref(a))
             batch.clear()
 
         for gi, group in enumerate(self.param_groups):
@@ -111,8 +110,7 @@ class Adam(torch.optim.Optimizer):
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                if p.device.type != "cuda":
-                    raise L.EmdError("emd_amd.optim.Adam needs parameters on a ROCm device; there is no CPU path")
+                L.need_device("emd_amd.optim.Adam", p)
                 if p.dtype != torch.float32 or p.grad.is_sparse:
                     raise L.EmdError("emd_amd.optim.Adam handles dense fp32 parameters")
                 state = self.state[p]

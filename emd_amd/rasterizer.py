@@ -136,7 +136,6 @@ class RasterCall:
     def export_binning(self, with_masks=False):
         """Sorted keys (uint64 as int64 bit pattern), Gaussian ids and tile ranges of this call's forward (+ the quadrant mask of every
         list entry with `with_masks`)."""
-        lib = L.load()
         st = self.last_status()
         D = 0 if st["overflow"] else st["num_rendered"]
         dev = self.status.device
@@ -146,30 +145,26 @@ class RasterCall:
         masks = torch.empty(max(D, 1), device=dev, dtype=torch.int32) if with_masks else None
         ranges = torch.empty(T, 2, device=dev, dtype=torch.int32)
         d = L.EmdDims(self.N, self.H, self.W, self.capacity, self.flags)
-        L.check(lib.emd_raster_export_binning(C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], self.bin_ws.data_ptr(), self.sizes[1], D,
-                                              keys.data_ptr(), ids.data_ptr(), ranges.data_ptr(), L.ptr(masks), _stream()),
-                "emd_raster_export_binning")
+        L.launch("emd_raster_export_binning", C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], self.bin_ws.data_ptr(), self.sizes[1], D,
+                 keys.data_ptr(), ids.data_ptr(), ranges.data_ptr(), L.ptr(masks))
         return (keys[:D], ids[:D], ranges, masks[:D]) if with_masks else (keys[:D], ids[:D], ranges)
 
     def export_contributed(self):
         """bool [N]: the contributed words of this call's geom_ws as they are now (all False between the forward and its backward)."""
         words = torch.empty(max(self.N, 1), device=self.status.device, dtype=torch.int32)
         d = L.EmdDims(self.N, self.H, self.W, self.capacity, self.flags)
-        L.check(L.load().emd_raster_export_contributed(C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], words.data_ptr(), _stream()),
-                "emd_raster_export_contributed")
+        L.launch("emd_raster_export_contributed", C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], words.data_ptr())
         return words[:self.N] != 0
 
     def export_geometry(self):
-        lib = L.load()
         dev, N = self.status.device, self.N
         e = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
         out = dict(means2D=e(N, 2), depths=e(N), conic_opacity=e(N, 4), rgb=e(N, 3),
                    normal=e(N, 3) if self.flags & L.FLAG_NORMAL else None, tiles_touched=e(N, dt=torch.int32))
         d = L.EmdDims(N, self.H, self.W, self.capacity, self.flags)
-        L.check(lib.emd_raster_export_geometry(C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], out["means2D"].data_ptr(),
-                                               out["depths"].data_ptr(), out["conic_opacity"].data_ptr(), out["rgb"].data_ptr(),
-                                               L.ptr(out["normal"]), out["tiles_touched"].data_ptr(), _stream()),
-                "emd_raster_export_geometry")
+        L.launch("emd_raster_export_geometry", C.byref(d), self.geom_ws.data_ptr(), self.sizes[0], out["means2D"].data_ptr(),
+                 out["depths"].data_ptr(), out["conic_opacity"].data_ptr(), out["rgb"].data_ptr(),
+                 L.ptr(out["normal"]), out["tiles_touched"].data_ptr())
         return out
 
 
@@ -314,10 +309,6 @@ def _f32c(t, name, shape_tail=None):
     return t.contiguous()
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _fill_motion(m: L.EmdMotion, actor_ids, actor_pose, residual_dx, residual_dq):
     m.actor_id = L.ptr(actor_ids)
     m.actor_pose = L.ptr(actor_pose)
@@ -353,8 +344,7 @@ class _Rasterize(torch.autograd.Function):
         are read from raster_settings as always."""
         lib = L.load()
         dev = means3D.device
-        if dev.type != "cuda":
-            raise L.EmdError("GaussianRasterizer needs tensors on a ROCm device (cuda:N); there is no CPU path")
+        L.need_device("GaussianRasterizer", means3D)
         N = means3D.shape[0]
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         cs, sdev = make_c_settings(raster_settings, opts.near_plane)
@@ -416,7 +406,7 @@ class _Rasterize(torch.autograd.Function):
                     aux = _aux_streams[dev.index] = torch.cuda.Stream(device=dev)
                 if aux.cuda_stream != torch.cuda.current_stream().cuda_stream:
                     a.aux_stream = aux.cuda_stream
-            rc = lib.emd_raster_forward(C.byref(a), _stream())
+            rc = lib.emd_raster_forward(C.byref(a), L.stream())
             if rc == L.EMD_ERR_DEPTH_RANGE and not (flags & L.FLAG_WIDE_DEPTH_SORT):
                 _wide_depth.add(key)
                 flags |= L.FLAG_WIDE_DEPTH_SORT
@@ -456,7 +446,6 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_normal, g_alpha, _g_radii, *g_extra):
-        lib = L.load()
         nx = ctx.num_extra
         saved = ctx.saved_tensors
         (means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, actor_pose, residual_dx,
@@ -563,19 +552,18 @@ class _Rasterize(torch.autograd.Function):
             # accumulator rows before the projection backward consumes them, and the caller's hook (collectives of the factors on the
             # communication stream) -- then the projection backward, under which the collectives run
             b.flags = bflags | L.FLAG_BWD_RENDER_ONLY
-            L.check(lib.emd_raster_backward(C.byref(b), _stream()), "emd_raster_backward (render half)")
+            L.launch("emd_raster_backward", C.byref(b), what="emd_raster_backward (render half)")
             if want_cam:
-                L.check(lib.emd_raster_backward_camera(C.byref(b), d_cam.data_ptr(), cam_rows.data_ptr(), cam_rows.numel() * 4, _stream()),
-                        "emd_raster_backward_camera")
+                L.launch("emd_raster_backward_camera", C.byref(b), d_cam.data_ptr(), cam_rows.data_ptr(), cam_rows.numel() * 4)
             if two_calls:
                 rec.sh_color_grad = d_shc
                 rec.on_sh_factor(rec)
             b.flags = bflags | L.FLAG_BWD_PROJECT_ONLY
             if d_shc is not None:
                 b.dL_dsh_color = None                  # (extracted behind the render half already)
-            L.check(lib.emd_raster_backward(C.byref(b), _stream()), "emd_raster_backward (projection half)")
+            L.launch("emd_raster_backward", C.byref(b), what="emd_raster_backward (projection half)")
         else:
-            L.check(lib.emd_raster_backward(C.byref(b), _stream()), "emd_raster_backward")
+            L.launch("emd_raster_backward", C.byref(b))
         if ws_key is not None:
             while len(_clean_ws) >= 4:                    # a few sizes at most (the point count changes at densification events)
                 _clean_ws.pop(next(iter(_clean_ws)))

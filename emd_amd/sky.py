@@ -15,15 +15,6 @@ import torch
 from . import _lib as L
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _need_gpu(t, what):
-    if t.device.type != "cuda":
-        raise L.EmdError(f"{what} needs tensors on a ROCm device; there is no CPU path")
-
-
 def _fill_camera(a, vals):
     for i in range(9):
         a.Kinv[i] = vals[i]
@@ -37,8 +28,7 @@ class _SkyOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cube, fg, acc, dirs, cam, jitter, H, W, flags, threshold, fill, want_blend, deterministic=False):
-        _need_gpu(cube, "sky lookup")
-        lib = L.load()
+        L.need_device("sky lookup", cube)
         cube = cube.contiguous().float()
         res = cube.shape[1]
         if cube.shape != (6, res, res, 3):
@@ -78,14 +68,13 @@ class _SkyOp(torch.autograd.Function):
             a.fg = fg.data_ptr()
             out = torch.empty(shape, device=dev, dtype=torch.float32)
             a.out = out.data_ptr()
-        L.check(lib.emd_sky_forward(C.byref(a), _stream()), "emd_sky_forward")
+        L.launch("emd_sky_forward", C.byref(a))
         ctx.args, ctx.keep, ctx.want_blend, ctx.deterministic = a, keep, want_blend, bool(deterministic)
         ctx.save_for_backward(cube, fg if want_blend else None, acc)
         return (sky, out) if want_blend else (sky, sky.new_empty(0))
 
     @staticmethod
     def backward(ctx, g_sky, g_out):
-        lib = L.load()
         cube, fg, acc = ctx.saved_tensors
         b = L.EmdSkyBwdArgs()
         C.memmove(C.byref(b.f), C.byref(ctx.args), C.sizeof(L.EmdSkyArgs))
@@ -108,9 +97,9 @@ class _SkyOp(torch.autograd.Function):
             ws = None
             if d_cube is not None:
                 ws = torch.empty(L.sky_det_workspace_size(b.f.height * b.f.width), device=cube.device, dtype=torch.uint8)
-            L.check(lib.emd_sky_backward_det(C.byref(b), L.ptr(ws), 0 if ws is None else ws.numel(), _stream()), "emd_sky_backward_det")
+            L.launch("emd_sky_backward_det", C.byref(b), L.ptr(ws), 0 if ws is None else ws.numel())
         else:
-            L.check(lib.emd_sky_backward(C.byref(b), _stream()), "emd_sky_backward")
+            L.launch("emd_sky_backward", C.byref(b))
         return (d_cube, d_fg, d_acc) + (None,) * 10
 
 

@@ -21,10 +21,7 @@ SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17
 J = L.SKIN_JOINTS
 
 _parents_cache = {}
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_CHECKER = " (the checker's restatement is tests/skinning_ref.py)"       # behind the operator's name in a refusal of CPU tensors
 
 
 def _parents_dev(parents, device):
@@ -102,11 +99,6 @@ class SkinLayout:
         return self._layout
 
 
-def _need_device(t, what):
-    if t.device.type != "cuda":
-        raise L.EmdError(f"{what} needs tensors on a ROCm device; there is no CPU path (the checker's restatement is tests/skinning_ref.py)")
-
-
 def _chain_args(theta, joints, parents_dev, canon_inv, A):
     a = L.EmdJointChainArgs()
     a.num_instances = theta.shape[0] if theta is not None else A.shape[0]
@@ -121,7 +113,7 @@ def _chain_forward(theta, joints, parents_dev, canon_inv):
         raise ValueError(f"canon_inv must be [P,{J},12] (row-major 3x4)")
     A = torch.empty(theta.shape[0], J, 12, device=theta.device, dtype=torch.float32)
     a = _chain_args(theta, joints, parents_dev, canon_inv, A)
-    L.check(L.load().emd_joint_chain_forward(C.byref(a), _stream()), "emd_joint_chain_forward")
+    L.launch("emd_joint_chain_forward", C.byref(a))
     return A
 
 
@@ -142,7 +134,7 @@ def _skin_args(means, quats, opac, weights, A, trans, valid, lay, outs=(None, No
 def _skin_forward(means, quats, opac, weights, A, trans, valid, lay):
     outs = (torch.empty_like(means), torch.empty_like(quats), torch.empty_like(opac))
     a = _skin_args(means, quats, opac, weights, A, trans, valid, lay, outs)
-    L.check(L.load().emd_skin_forward(C.byref(a), _stream()), "emd_skin_forward")
+    L.launch("emd_skin_forward", C.byref(a))
     return outs
 
 
@@ -157,7 +149,7 @@ def _skin_backward(means, quats, opac, weights, A, trans, valid, lay, g_wm, g_wq
     g = L.EmdSkinGrads()
     g.g_world_means, g.g_world_quats, g.g_opacities_out = g_wm.data_ptr(), g_wq.data_ptr(), g_wo.data_ptr()
     g.d_means, g.d_quats, g.d_opacities, g.d_weights, g.partials = d_means.data_ptr(), d_quats.data_ptr(), d_opac.data_ptr(), L.ptr(d_w), partials.data_ptr()
-    L.check(L.load().emd_skin_backward(C.byref(a), C.byref(g), _stream()), "emd_skin_backward")
+    L.launch("emd_skin_backward", C.byref(a), C.byref(g))
     return d_means, d_quats, d_opac, d_w, partials
 
 
@@ -174,8 +166,7 @@ class _JointChain(torch.autograd.Function):
         g_A = g_A.contiguous().float()
         d_theta = torch.empty_like(theta)
         a = _chain_args(theta, joints, parents_dev, canon_inv, None)
-        L.check(L.load().emd_joint_chain_backward(C.byref(a), g_A.data_ptr(), None, None, None, None, d_theta.data_ptr(), _stream()),
-                "emd_joint_chain_backward")
+        L.launch("emd_joint_chain_backward", C.byref(a), g_A.data_ptr(), None, None, None, None, d_theta.data_ptr())
         return d_theta, None, None, None
 
 
@@ -198,8 +189,8 @@ class _Skin(torch.autograd.Function):
             # the per-instance sums: an instance's chunk slabs added in ascending chunk order (the first half of k_joint_chain_backward)
             dA, d_trans = torch.empty_like(A), torch.empty_like(trans)
             a = _chain_args(None, None, None, None, A)
-            L.check(L.load().emd_joint_chain_backward(C.byref(a), None, partials.data_ptr(), lay.chunk_start.data_ptr(), dA.data_ptr(),
-                                                      d_trans.data_ptr(), None, _stream()), "emd_joint_chain_backward")
+            L.launch("emd_joint_chain_backward", C.byref(a), None, partials.data_ptr(), lay.chunk_start.data_ptr(), dA.data_ptr(),
+                     d_trans.data_ptr(), None)
         return d_means, d_quats, d_opac, d_w, dA, d_trans, None, None
 
 
@@ -223,8 +214,8 @@ class _PosedSkin(torch.autograd.Function):
                                                                  ctx.needs_input_grad[3])
         d_theta, d_trans = torch.empty_like(theta), torch.empty_like(trans)
         a = _chain_args(theta, joints, parents_dev, canon_inv, None)
-        L.check(L.load().emd_joint_chain_backward(C.byref(a), None, partials.data_ptr(), lay.chunk_start.data_ptr(), None, d_trans.data_ptr(),
-                                                  d_theta.data_ptr(), _stream()), "emd_joint_chain_backward")
+        L.launch("emd_joint_chain_backward", C.byref(a), None, partials.data_ptr(), lay.chunk_start.data_ptr(), None, d_trans.data_ptr(),
+                 d_theta.data_ptr())
         return d_means, d_quats, d_opac, d_w, d_theta, None, d_trans, None, None, None, None
 
 
@@ -241,7 +232,7 @@ def joint_transforms(theta, joints, parents=SMPL_PARENTS, canon_inv=None):
     theta [P,24,4]: unnormalised joint quaternions (w, x, y, z), row 0 the global orientation (the caller concatenates `instances_quats` and
     `smpl_qauts`); joints [P,24,3]: rest-pose joint positions; canon_inv [P,24,12]: the inverse of the canonical "da-pose" transforms, composed
     on the right.  The gradient goes to theta, through the normalisation; joints and canon_inv are buffers in the reference and get none."""
-    _need_device(theta, "joint_transforms")
+    L.need_device("joint_transforms" + _CHECKER, theta)
     return _JointChain.apply(_f(theta), _f(joints).detach(), _parents_dev(parents, theta.device), None if canon_inv is None else _f(canon_inv).detach())
 
 
@@ -255,7 +246,7 @@ def skin_gaussians(means, quats, opacities, point_ids, weights, A, trans, valid=
     weights, A and trans.  point_ids [N]: the instance of a point, or < 0 (returned as `transform_gaussians` returns a static point);
     weights [N,24]: dense skinning weights; A: `joint_transforms`; layout: a `SkinLayout` the caller keeps between steps (and invalidates when
     the point set changes) -- without one the layout is rebuilt, with its host read, on every call."""
-    _need_device(means, "skin_gaussians")
+    L.need_device("skin_gaussians" + _CHECKER, means)
     lay = _layout_for(layout, point_ids, A.shape[0])
     return _Skin.apply(_f(means), _f(quats), _f(opacities).reshape(-1), _f(weights), _f(A), _f(trans), _valid_floats(valid), lay)
 
@@ -264,7 +255,7 @@ def posed_skin_gaussians(means, quats, opacities, point_ids, weights, theta, joi
                          layout=None):
     """`skin_gaussians(..., joint_transforms(theta, joints, parents, canon_inv), ...)` as one autograd node: the same values and, bit for bit,
     the same gradients, with two launches each way (the per-instance sums and the reverse chain share a launch)."""
-    _need_device(means, "posed_skin_gaussians")
+    L.need_device("posed_skin_gaussians" + _CHECKER, means)
     lay = _layout_for(layout, point_ids, theta.shape[0])
     return _PosedSkin.apply(_f(means), _f(quats), _f(opacities).reshape(-1), _f(weights), _f(theta), _f(joints).detach(), _f(trans),
                             _valid_floats(valid), _parents_dev(parents, theta.device), None if canon_inv is None else _f(canon_inv).detach(), lay)

@@ -16,24 +16,18 @@ _MASK_TYPES = {"bce": L.TL_MASK_BCE, "safe_bce": L.TL_MASK_SAFE_BCE}
 _DEPTH_TYPES = {"l1": L.TL_DEPTH_L1, "l2": L.TL_DEPTH_L2, "smooth_l1": L.TL_DEPTH_SMOOTH_L1}
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class _Affine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, affine):
-        lib = L.load()
         x = rgb.detach().contiguous().float()
         A = affine.detach().contiguous().float()
         out = torch.empty_like(x)
-        L.check(lib.emd_affine_forward(x.numel() // 3, x.data_ptr(), A.data_ptr(), out.data_ptr(), _stream()), "emd_affine_forward")
+        L.launch("emd_affine_forward", x.numel() // 3, x.data_ptr(), A.data_ptr(), out.data_ptr())
         ctx.save_for_backward(x, A)
         return out.view(rgb.shape)
 
     @staticmethod
     def backward(ctx, g):
-        lib = L.load()
         x, A = ctx.saved_tensors
         g = g.contiguous().float()
         P = x.numel() // 3
@@ -41,9 +35,9 @@ class _Affine(torch.autograd.Function):
         d_x = torch.empty_like(x) if need_x else None
         d_A = torch.empty(3, 4, device=x.device, dtype=torch.float32) if need_A else None
         # the chunks' partial sums of dL/dA: caller-owned, never cleared (a captured step takes it from the graph's pool)
-        ws = torch.empty(max(int(lib.emd_affine_workspace_size(P)), 8), device=x.device, dtype=torch.uint8) if need_A else None
-        L.check(lib.emd_affine_backward(P, x.data_ptr(), A.data_ptr(), g.data_ptr(), L.ptr(d_x), L.ptr(d_A), L.ptr(ws),
-                                        0 if ws is None else ws.numel(), _stream()), "emd_affine_backward")
+        ws = torch.empty(max(int(L.load().emd_affine_workspace_size(P)), 8), device=x.device, dtype=torch.uint8) if need_A else None
+        L.launch("emd_affine_backward", P, x.data_ptr(), A.data_ptr(), g.data_ptr(), L.ptr(d_x), L.ptr(d_A), L.ptr(ws),
+                 0 if ws is None else ws.numel())
         return d_x, d_A
 
 
@@ -52,8 +46,7 @@ def apply_affine(rgb, affine, pixel_affine=False):
     row, `img_idx.flatten()[:1]`: see INTEGRATION.md).  Gradients reach both.  A per-pixel [H,W,3,4] matrix is not served."""
     if pixel_affine or affine.dim() != 2:
         raise NotImplementedError("apply_affine takes one [3,4] matrix per image; per-pixel affine (pixel_affine=True, a [H,W,3,4] input) is not built")
-    if rgb.device.type != "cuda" or affine.device.type != "cuda":
-        raise L.EmdError("apply_affine needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("apply_affine", rgb, affine)
     if tuple(affine.shape) != (3, 4) or rgb.dim() < 1 or rgb.shape[-1] != 3 or rgb.numel() == 0:
         raise L.EmdError(f"apply_affine: rgb {tuple(rgb.shape)} / affine {tuple(affine.shape)}, expected [...,3] and [3,4]")
     return _Affine.apply(rgb, affine)
@@ -62,7 +55,6 @@ def apply_affine(rgb, affine, pixel_affine=False):
 class _TrainerLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, gt_rgb, opacity, sky_mask, depth, lidar_depth, H, W, cfg):
-        lib = L.load()
         dev = rgb.device
         f = lambda t: None if t is None else t.detach().contiguous().float()
         x, y, o, s, d, l = f(rgb), f(gt_rgb), f(opacity), f(sky_mask), f(depth), f(lidar_depth)
@@ -83,8 +75,8 @@ class _TrainerLoss(torch.autograd.Function):
         g_d = torch.empty_like(d) if (need[4] and on_d) else None
         a.dL_drgb, a.dL_dopacity, a.dL_ddepth = L.ptr(g_x), L.ptr(g_o), L.ptr(g_d)
         # partial sums and the SSIM derivative maps: caller-owned, never cleared (a captured step takes it from the graph's pool)
-        ws = torch.empty(max(int(lib.emd_trainer_loss_workspace_size(C.byref(a))), 8), device=dev, dtype=torch.uint8)
-        L.check(lib.emd_trainer_loss(C.byref(a), ws.data_ptr(), ws.numel(), _stream()), "emd_trainer_loss")
+        ws = torch.empty(max(int(L.load().emd_trainer_loss_workspace_size(C.byref(a))), 8), device=dev, dtype=torch.uint8)
+        L.launch("emd_trainer_loss", C.byref(a), ws.data_ptr(), ws.numel())
         ctx.save_for_backward(g_x, g_o, g_d)
         ctx.shapes = (rgb.shape, None if opacity is None else opacity.shape, None if depth is None else depth.shape)
         ctx.mark_non_differentiable(losses)
@@ -121,9 +113,7 @@ def trainer_losses(rgb, gt_rgb, opacity=None, sky_mask=None, depth=None, lidar_d
         raise NotImplementedError("trainer_losses: depth_error_percentile is not built (the depth loss runs over every hit pixel)")
     if mask_type not in _MASK_TYPES or depth_type not in _DEPTH_TYPES:
         raise L.EmdError(f"trainer_losses: mask_type {mask_type!r} / depth_type {depth_type!r}, expected one of {list(_MASK_TYPES)} / {list(_DEPTH_TYPES)}")
-    tensors = [t for t in (rgb, gt_rgb, opacity, sky_mask, depth, lidar_depth) if t is not None]
-    if any(t.device.type != "cuda" for t in tensors):
-        raise L.EmdError("trainer_losses needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("trainer_losses", rgb, gt_rgb, opacity, sky_mask, depth, lidar_depth)
     H, W = _image_size(rgb)
     if gt_rgb.numel() != 3 * H * W:
         raise L.EmdError(f"trainer_losses: gt_rgb is {tuple(gt_rgb.shape)}, rgb {tuple(rgb.shape)}")

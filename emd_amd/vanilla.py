@@ -37,10 +37,6 @@ from .density import EventRows, restructure_rows
 SH_C0 = 0.28209479177387814
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _get(cfg, key, default=None):
     if isinstance(cfg, dict):
         return cfg.get(key, default)
@@ -52,15 +48,15 @@ class _GaussianReg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, log_scales, opacity_logits, radii, weights):
-        lib, dev, n = L.load(), log_scales.device, log_scales.shape[0]
+        dev, n = log_scales.device, log_scales.shape[0]
         a = L.EmdVanillaRegArgs()
         a.num_points = n
         a.log_scales, a.opacity_logits, a.radii = log_scales.data_ptr(), L.ptr(opacity_logits), L.ptr(radii)
         a.w_sharp, a.max_gauss_ratio, a.w_flatten, a.w_sparse, a.w_max_s_square = weights
         terms = torch.empty(4, device=dev, dtype=torch.float32)
-        ws = torch.empty(max(int(lib.emd_vanilla_reg_workspace_size(n)), 8), device=dev, dtype=torch.uint8)
+        ws = torch.empty(max(int(L.load().emd_vanilla_reg_workspace_size(n)), 8), device=dev, dtype=torch.uint8)
         a.terms = terms.data_ptr()
-        L.check(lib.emd_vanilla_reg_forward(C.byref(a), ws.data_ptr(), ws.numel(), _stream()), "emd_vanilla_reg_forward")
+        L.launch("emd_vanilla_reg_forward", C.byref(a), ws.data_ptr(), ws.numel())
         ctx.save_for_backward(log_scales, opacity_logits, radii, ws)
         ctx.weights = weights
         return terms
@@ -77,7 +73,7 @@ class _GaussianReg(torch.autograd.Function):
         sparse = ctx.weights[3] != 0.0 and opacity_logits is not None and radii is not None
         d_lo = torch.empty_like(opacity_logits) if (sparse and ctx.needs_input_grad[1]) else None
         a.g, a.dL_dlog_scales, a.dL_dopacity_logits = g.data_ptr(), d_ls.data_ptr(), L.ptr(d_lo)
-        L.check(L.load().emd_vanilla_reg_backward(C.byref(a), ws.data_ptr(), ws.numel(), _stream()), "emd_vanilla_reg_backward")
+        L.launch("emd_vanilla_reg_backward", C.byref(a), ws.data_ptr(), ws.numel())
         return d_ls, d_lo, None, None
 
 
@@ -87,8 +83,7 @@ def gaussian_regulation(log_scales, opacity_logits=None, radii=None, *, w_sharp=
     EmdVanillaRegArgs, include/emd_raster.h).  A term whose weight is 0 is skipped (value 0, no gradient), the sparse term also without
     `opacity_logits` or `radii`; `opacity_logits` receives no gradient when there is no sparse term.  The weights are Python numbers.
     Bit-reproducible, forward and backward; no host synchronisation."""
-    if log_scales.device.type != "cuda":
-        raise L.EmdError("gaussian_regulation needs tensors on a ROCm device; there is no CPU path")
+    L.need_device("gaussian_regulation", log_scales)
     if log_scales.dim() != 2 or log_scales.shape[1] != 3:
         raise NotImplementedError("ball gaussians ([N,1] scales) are not served")
     lo = None if opacity_logits is None else opacity_logits.contiguous().float()
@@ -219,8 +214,7 @@ class VanillaGaussians(torch.nn.Module):
             n = self.num_points
             if self.filter_mask is not None and not bool(self.filter_mask.all()):
                 raise NotImplementedError("a partial filter_mask (rows hidden from the rasterizer) is not used by the reference's VanillaGaussians")
-            if radii.device.type != "cuda" or xys_grad.device.type != "cuda":
-                raise L.EmdError("VanillaGaussians.after_train needs tensors on a ROCm device; there is no CPU path")
+            L.need_device("VanillaGaussians.after_train", radii, xys_grad)
             r = radii.reshape(-1).to(torch.int32).contiguous()
             g = xys_grad.reshape(n, -1).float()
             if g.stride(1) != 1:
@@ -232,9 +226,8 @@ class VanillaGaussians(torch.nn.Module):
                 self.vis_counts = torch.ones_like(self.xys_grad_norm)
             if self.max_2Dsize is None:
                 self.max_2Dsize = torch.zeros(n, device=r.device, dtype=torch.float32)
-            L.check(L.load().emd_after_train_stats(n, r.data_ptr(), g.data_ptr(), int(g.stride(0)), None if first else self.xys_grad_norm.data_ptr(),
-                                                   None if first else self.vis_counts.data_ptr(), self.max_2Dsize.data_ptr(), float(last_size),
-                                                   _stream()), "emd_after_train_stats")
+            L.launch("emd_after_train_stats", n, r.data_ptr(), g.data_ptr(), int(g.stride(0)), None if first else self.xys_grad_norm.data_ptr(),
+                     None if first else self.vis_counts.data_ptr(), self.max_2Dsize.data_ptr(), float(last_size))
 
     # ---- the refinement event ------------------------------------------------------------------------------------------------------------
     def refinement_after(self, step, optimizer, samples=None):
@@ -268,8 +261,7 @@ class VanillaGaussians(torch.nn.Module):
     def _refine(self, optimizer, do_densify, do_cull, samples):
         """The event's body, once for every class: args -> the rows that travel (`density.EventRows`) -> the driver -> install.  A class states what
         differs in `_refine_args`, `_refine_attrs`, `_refine_rows` and `_after_refine`."""
-        if self._means.device.type != "cuda":
-            raise L.EmdError(f"{type(self).__name__}.refinement_after needs tensors on a ROCm device; there is no CPU path")
+        L.need_device(f"{type(self).__name__}.refinement_after", self._means)
         N, prefix = self.num_points, self.class_prefix
         a, keep = self._refine_args(do_densify, do_cull)
         groups = {grp["name"]: grp for grp in (optimizer.param_groups if optimizer is not None else [])}

@@ -3,6 +3,7 @@ host-only entry points and argument validation work without a GPU (no compute ca
 import ctypes as C
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -32,34 +33,50 @@ def test_abi_version_matches_header():
     assert L.load().emd_abi_version() == v == L.ABI_VERSION
 
 
-def test_struct_layout_matches_c():
-    """ctypes mirrors must have the sizes the C compiler gives the header's structs."""
-    import subprocess, tempfile
-    prog = r'''
-#include <stdio.h>
-#include "emd_raster.h"
-int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(EmdSettings), sizeof(EmdMotion), sizeof(EmdDims),
- sizeof(EmdFwdArgs), sizeof(EmdBwdArgs), sizeof(EmdStatus), sizeof(EmdSkyArgs), sizeof(EmdSkyBwdArgs), sizeof(EmdLossArgs),
- sizeof(EmdHexArgs), sizeof(EmdHexGrads), sizeof(EmdDeformInArgs), sizeof(EmdAdamTensor), sizeof(EmdAdamArgs),
- sizeof(EmdTrackArgs), sizeof(EmdTrackGrads), sizeof(EmdTrackedPoseArgs), sizeof(EmdTrackedPoseGrads), sizeof(EmdStepSelect),
- sizeof(EmdMlpTrunk), sizeof(EmdMlpTrunkGrads), sizeof(EmdMlpBranch), sizeof(EmdMlpBranchGrads),
- sizeof(EmdRefineArgs), sizeof(EmdDensifyArgs), sizeof(EmdDensifyGather), sizeof(EmdRadixSortArgs), sizeof(EmdBinningArgs));return 0;}
-'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        sizes = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert sizes[:5] == [C.sizeof(L.EmdSettings), C.sizeof(L.EmdMotion), C.sizeof(L.EmdDims), C.sizeof(L.EmdFwdArgs),
-                         C.sizeof(L.EmdBwdArgs)]
-    assert sizes[5] == 16
-    assert sizes[6:] == [C.sizeof(L.EmdSkyArgs), C.sizeof(L.EmdSkyBwdArgs), C.sizeof(L.EmdLossArgs), C.sizeof(L.EmdHexArgs),
-                         C.sizeof(L.EmdHexGrads), C.sizeof(L.EmdDeformInArgs), C.sizeof(L.EmdAdamTensor), C.sizeof(L.EmdAdamArgs),
-                         C.sizeof(L.EmdTrackArgs), C.sizeof(L.EmdTrackGrads), C.sizeof(L.EmdTrackedPoseArgs),
-                         C.sizeof(L.EmdTrackedPoseGrads), C.sizeof(L.EmdStepSelect),
-                         C.sizeof(L.EmdMlpTrunk), C.sizeof(L.EmdMlpTrunkGrads), C.sizeof(L.EmdMlpBranch), C.sizeof(L.EmdMlpBranchGrads),
-                         C.sizeof(L.EmdRefineArgs), C.sizeof(L.EmdDensifyArgs), C.sizeof(L.EmdDensifyGather), C.sizeof(L.EmdRadixSortArgs), C.sizeof(L.EmdBinningArgs)]
+# upper-case ints of _lib that the header does not name: the payload floats of an accumulator row and the pitch derived from them (csrc/common.h),
+# and the floats of one camera-gradient row (csrc/camera_grad.hip)
+CONSTANTS_WITHOUT_HEADER_NAME = {"BWD_PAYLOAD", "BWD_STRIDE", "CAMERA_GRAD_FLOATS"}
+
+
+def _mirrored_constants():
+    """{name of an upper-case int of _lib: the header names it must equal}; a name neither matched nor listed above maps to nothing and fails."""
+    header = set(re.findall(r"\bEMD_[A-Z0-9_]+\b", open(os.path.join(ROOT, "include", "emd_raster.h")).read()))
+    want = {}
+    for name, v in vars(L).items():
+        if not name.isupper() or isinstance(v, bool) or not isinstance(v, int) or name in CONSTANTS_WITHOUT_HEADER_NAME:
+            continue
+        c_name = name if name.startswith("EMD_") else "EMD_" + name
+        want[name] = ["EMD_TILE_X", "EMD_TILE_Y"] if name == "TILE" else [c_name] if c_name in header else []
+    return want
+
+
+def test_struct_layout_matches_c(tmp_path):
+    """The whole mirror against the C compiler in one program: sizeof of every ctypes.Structure of _lib, offsetof and sizeof of every field its
+    `_fields_` names (a name the header does not have fails the compile), and every integer constant of _lib the header names."""
+    structs = [t for t in vars(L).values() if isinstance(t, type) and issubclass(t, C.Structure) and t.__module__ == L.__name__]
+    constants = _mirrored_constants()
+    assert len(structs) >= 40 and all(constants.values()), [n for n, c in constants.items() if not c]
+    acts = {f"EMD_NSTD_ACT_{k.upper()}": v for k, v in L.NSTD_ACT.items()}
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "emd_raster.h"', 'int main(void){', 'printf("S EmdStatus - %zu 0\\n", sizeof(EmdStatus));']
+    for t in structs:
+        n = t.__name__
+        lines.append(f'printf("S {n} - %zu 0\\n", sizeof({n}));')
+        lines += [f'printf("F {n} {f} %zu %zu\\n", offsetof({n}, {f}), sizeof((({n} *)0)->{f}));' for f, *_ in t._fields_]
+    lines += [f'printf("K {c} - %lld 0\\n", (long long)({c}));' for c in sorted({c for cs in constants.values() for c in cs} | set(acts))]
+    lines.append("return 0;}")
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = {(kind, a, b): (int(x), int(y)) for kind, a, b, x, y in (ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())}
+    want = {("S", "EmdStatus", "-"): (16, 0)}
+    for t in structs:
+        want["S", t.__name__, "-"] = (C.sizeof(t), 0)
+        want.update({("F", t.__name__, f): (getattr(t, f).offset, getattr(t, f).size) for f, *_ in t._fields_})
+    want.update({("K", c, "-"): (getattr(L, name), 0) for name, cs in constants.items() for c in cs})
+    want.update({("K", c, "-"): (v, 0) for c, v in acts.items()})
+    assert got.keys() == want.keys()
+    wrong = [f"{' '.join(k)}: C (offset or value, size) {got[k]}, ctypes {want[k]}" for k in want if got[k] != want[k]]
+    assert not wrong, "\n".join(wrong)
 
 
 def test_workspace_size_host_only():

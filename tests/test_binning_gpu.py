@@ -51,10 +51,6 @@ class Workspaces:
         self.geom, self.bin = _filled(self.geom_bytes // 4), _filled(self.bin_bytes // 4)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _bin_and_check(depth_key, binrec, *, H, W, capacity, near_plane=0.2, wide=False, ws=None, ref=None, label=""):
     """One emd_raster_binning call on the current stream, checked in full -> (reference, dict of what the device returned)."""
     depth_key = np.ascontiguousarray(depth_key, np.uint32)
@@ -74,7 +70,7 @@ def _bin_and_check(depth_key, binrec, *, H, W, capacity, near_plane=0.2, wide=Fa
     a.depth_key, a.binrec = L.ptr(dk), L.ptr(br)
     a.geom_ws, a.geom_bytes, a.bin_ws, a.bin_bytes = ws.geom.data_ptr(), ws.geom_bytes, ws.bin.data_ptr(), ws.bin_bytes
     a.status, a.tile_order = status.data_ptr(), order.data_ptr()
-    rc = lib.emd_raster_binning(C.byref(a), _stream())
+    rc = lib.emd_raster_binning(C.byref(a), L.stream())
     assert rc == 0, f"{label}: (a) returned {rc}: {lib.emd_last_error()}"
     st = _host(status)                                       # (the copy synchronises with the stream)
     got = dict(status=tuple(int(x) for x in st[:4]))
@@ -86,7 +82,7 @@ def _bin_and_check(depth_key, binrec, *, H, W, capacity, near_plane=0.2, wide=Fa
     ids, masks = (torch.zeros(max(D, 1), dtype=torch.int32, device=DEV) for _ in range(2))
     ranges = torch.full((T, 2), -1, dtype=torch.int32, device=DEV)
     rc = lib.emd_raster_export_binning(C.byref(dims), ws.geom.data_ptr(), ws.geom_bytes, ws.bin.data_ptr(), ws.bin_bytes, D, keys.data_ptr(), ids.data_ptr(),
-                                       ranges.data_ptr(), masks.data_ptr(), _stream())
+                                       ranges.data_ptr(), masks.data_ptr(), L.stream())
     assert rc == 0, f"{label}: export returned {rc}: {lib.emd_last_error()}"
     got["ranges"], got["order"] = _host(ranges).reshape(T, 2), _host(order)[:T]
     if not ref["overflow"]:
@@ -465,7 +461,7 @@ def test_rejected_arguments_leave_every_buffer_untouched():
         a.geom_bytes, a.bin_bytes = ws.geom_bytes, ws.bin_bytes
         for k, v in kw.items():
             setattr(a, k, v(ws.geom_bytes, ws.bin_bytes) if callable(v) else v)
-        assert lib.emd_raster_binning(C.byref(a), _stream()) == code, kw
+        assert lib.emd_raster_binning(C.byref(a), L.stream()) == code, kw
         assert text in lib.emd_last_error(), (kw, lib.emd_last_error())
     torch.cuda.synchronize()
     for k, v in bufs.items():

@@ -187,7 +187,7 @@ def test_camera_gradient_on_kept_rows():
     ws_bytes = L.camera_grad_workspace_size(N)
     ws = torch.empty(ws_bytes // 4, device=DEV)
     out = torch.full((35,), float("nan"), device=DEV)
-    L.check(L.load().emd_raster_backward_camera(C.byref(b), out.data_ptr(), ws.data_ptr(), ws_bytes, T._st()), "camera")
+    L.check(L.load().emd_raster_backward_camera(C.byref(b), out.data_ptr(), ws.data_ptr(), ws_bytes, L.stream()), "camera")
     torch.cuda.synchronize()
     assert torch.equal(call.render_grads, rows0)
     assert T._ratio(out.cpu().numpy().astype(np.float64), want, R.bound35(want, terms), "kept rows at the 64-byte pitch") <= 1.0

@@ -210,10 +210,6 @@ def _bwd_args(hip, case, raw, outs):
     return b
 
 
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 @pytest.mark.parametrize("name", ["static-sh", "motion-residual", "cov-colors", "raw-params"])
 def test_c_entry_point_reads_the_rows_and_is_deterministic(name):
     rf, hip = _reference(name), _hip(name)
@@ -225,31 +221,31 @@ def test_c_entry_point_reads_the_rows_and_is_deterministic(name):
     assert ws_bytes >= 3 * 36 * 4
     # projection half alone ...
     b1.flags = hip["call"].flags | L.FLAG_BWD_PROJECT_ONLY
-    L.check(lib.emd_raster_backward(C.byref(b1), _st()), "projection half")
+    L.check(lib.emd_raster_backward(C.byref(b1), L.stream()), "projection half")
     # ... against camera call (twice: bit-identical outputs, into buffers with different garbage) + projection half, on the same rows
     ws = torch.full((ws_bytes // 4,), float("nan"), device=DEV)
     g1, g2 = torch.full((35,), float("nan"), device=DEV), torch.full((35,), 7.0, device=DEV)
     b2.flags = hip["call"].flags
-    L.check(lib.emd_raster_backward_camera(C.byref(b2), g1.data_ptr(), ws.data_ptr(), ws_bytes, _st()), "camera")
+    L.check(lib.emd_raster_backward_camera(C.byref(b2), g1.data_ptr(), ws.data_ptr(), ws_bytes, L.stream()), "camera")
     ws2 = torch.zeros(ws_bytes // 4 + 64, device=DEV)
-    L.check(lib.emd_raster_backward_camera(C.byref(b2), g2.data_ptr(), ws2.data_ptr(), ws_bytes, _st()), "camera, again")
+    L.check(lib.emd_raster_backward_camera(C.byref(b2), g2.data_ptr(), ws2.data_ptr(), ws_bytes, L.stream()), "camera, again")
     assert torch.equal(hip["call"].render_grads, rows0)                                 # the rows are read, not written
     assert torch.equal(ws2[ws_bytes // 4:], torch.zeros(64, device=DEV))                # nothing beyond the reported size
     b2.flags = hip["call"].flags | L.FLAG_BWD_PROJECT_ONLY
-    L.check(lib.emd_raster_backward(C.byref(b2), _st()), "projection half after the camera call")
+    L.check(lib.emd_raster_backward(C.byref(b2), L.stream()), "projection half after the camera call")
     assert torch.equal(g1, g2) and torch.equal(g1, hip["call"].camera_grad)
     for k in o1:
         if o1[k] is not None and not k.startswith("_"):
             assert torch.equal(o1[k], o2[k]), k
     assert o1["means3D"].abs().max() > 0
     # validation: a workspace one byte short, a normal-image gradient
-    assert lib.emd_raster_backward_camera(C.byref(b2), g1.data_ptr(), ws.data_ptr(), ws_bytes - 1, _st()) == L.EMD_ERR_WORKSPACE
+    assert lib.emd_raster_backward_camera(C.byref(b2), g1.data_ptr(), ws.data_ptr(), ws_bytes - 1, L.stream()) == L.EMD_ERR_WORKSPACE
     assert b"workspace" in lib.emd_last_error()
     b2.dL_dnormal = ws.data_ptr()
-    assert lib.emd_raster_backward_camera(C.byref(b2), g1.data_ptr(), ws.data_ptr(), ws_bytes, _st()) == L.EMD_ERR_INVALID
+    assert lib.emd_raster_backward_camera(C.byref(b2), g1.data_ptr(), ws.data_ptr(), ws_bytes, L.stream()) == L.EMD_ERR_INVALID
     assert b"normal" in lib.emd_last_error()
     b2.dL_dnormal = None
-    assert lib.emd_raster_backward_camera(C.byref(b2), None, ws.data_ptr(), ws_bytes, _st()) == L.EMD_ERR_INVALID
+    assert lib.emd_raster_backward_camera(C.byref(b2), None, ws.data_ptr(), ws_bytes, L.stream()) == L.EMD_ERR_INVALID
 
 
 # ---- edge cases ---------------------------------------------------------------------------------------------------------------------------
@@ -296,7 +292,7 @@ def test_no_gaussians():
     ws_bytes = L.camera_grad_workspace_size(0)
     ws = torch.full((max(ws_bytes // 4, 4),), float("nan"), device=DEV)
     out = torch.full((35,), float("nan"), device=DEV)
-    L.check(lib.emd_raster_backward_camera(C.byref(b), out.data_ptr(), ws.data_ptr(), ws_bytes, _st()), "camera, N = 0")
+    L.check(lib.emd_raster_backward_camera(C.byref(b), out.data_ptr(), ws.data_ptr(), ws_bytes, L.stream()), "camera, N = 0")
     torch.cuda.synchronize()
     assert torch.equal(out, torch.zeros(35, device=DEV))
 

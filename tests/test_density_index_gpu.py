@@ -61,10 +61,6 @@ def _expect(t, want, msg):
         raise AssertionError(msg)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _lib():
     from emd_amd import _lib as L
     return L, L.load()
@@ -94,7 +90,7 @@ def test_scan_alone(blocks):
                 b = Buffers()
                 col, tot = b.out(cols * blocks), b.out(cols)
                 col[:cols * blocks] = torch.from_numpy(counts.astype(np.int32).ravel()).to(DEV)
-                assert lib.emd_densify_scan(num_points, cols, col.data_ptr(), tot.data_ptr(), _stream()) == L.EMD_OK
+                assert lib.emd_densify_scan(num_points, cols, col.data_ptr(), tot.data_ptr(), L.stream()) == L.EMD_OK
                 b.check()
                 _expect(col, want, f"{name}, {cols} columns, N {num_points}")
                 _expect(tot, want_totals, f"totals: {name}, {cols} columns, N {num_points}")
@@ -105,13 +101,13 @@ def test_scan_of_no_points_zeroes_the_totals_and_bad_arguments_are_refused():
     for cols in (1, 3, 8):
         b = Buffers()
         col, tot = b.out(8), b.out(8)
-        assert lib.emd_densify_scan(0, cols, col.data_ptr(), tot.data_ptr(), _stream()) == L.EMD_OK
+        assert lib.emd_densify_scan(0, cols, col.data_ptr(), tot.data_ptr(), L.stream()) == L.EMD_OK
         b.check()
         assert _read(tot, 8).tolist() == [0] * cols + [SENTINEL] * (8 - cols) and (_read(col, 8) == SENTINEL).all()
     for num_points, cols, with_totals in ((300, 0, True), (300, 9, True), (300, 3, False), (0, 3, False), (-1, 3, True)):
         b = Buffers()
         col, tot = b.out(32), b.out(16)
-        assert lib.emd_densify_scan(num_points, cols, col.data_ptr(), tot.data_ptr() if with_totals else None, _stream()) == L.EMD_ERR_INVALID
+        assert lib.emd_densify_scan(num_points, cols, col.data_ptr(), tot.data_ptr() if with_totals else None, L.stream()) == L.EMD_ERR_INVALID
         b.check()
         assert (_read(col, 32) == SENTINEL).all() and (_read(tot, 16) == SENTINEL).all()
 
@@ -157,7 +153,7 @@ def test_densify_index_alone(n):
         assert m == totals[0] + totals[1] + 2 * totals[2]
         b = Buffers()
         d_code, d_off, d_tot, d_src, d_kind = b.put(code), b.put(offsets), b.put(totals), b.out(m), b.out(m)
-        assert lib.emd_densify_index(n, m, d_code.data_ptr(), d_off.data_ptr(), d_tot.data_ptr(), d_src.data_ptr(), d_kind.data_ptr(), _stream()) == L.EMD_OK
+        assert lib.emd_densify_index(n, m, d_code.data_ptr(), d_off.data_ptr(), d_tot.data_ptr(), d_src.data_ptr(), d_kind.data_ptr(), L.stream()) == L.EMD_OK
         b.check()
         _expect(d_src, src, name)
         _expect(d_kind, kind, name)
@@ -179,7 +175,7 @@ def test_refine_index_alone(n):
                 b = Buffers()
                 d_src, d_kind, d_rank = b.out(m), b.out(m), b.out(m)
                 rc = lib.emd_refine_index(n, m, ns, d_code.data_ptr(), d_off.data_ptr(), d_tot.data_ptr(), d_src.data_ptr(), d_kind.data_ptr(),
-                                          d_rank.data_ptr() if with_rank else None, _stream())
+                                          d_rank.data_ptr() if with_rank else None, L.stream())
                 assert rc == L.EMD_OK
                 b.check()
                 tag = f"{name}, {ns} samples"
@@ -199,7 +195,7 @@ def test_refine_index_refuses_0_and_14_samples():
         m = 300 * 15
         d_src, d_kind, d_rank = b.out(m), b.out(m), b.out(m)
         rc = lib.emd_refine_index(300, 300 + 300 * ns, ns, d_code.data_ptr(), d_off.data_ptr(), d_tot.data_ptr(), d_src.data_ptr(), d_kind.data_ptr(),
-                                  d_rank.data_ptr(), _stream())
+                                  d_rank.data_ptr(), L.stream())
         assert rc == L.EMD_ERR_INVALID
         b.check()
         assert all((_read(t, m) == SENTINEL).all() for t in (d_src, d_kind, d_rank))
@@ -211,7 +207,7 @@ def test_densify_split_rank(n_keep, n_clone, n_split):
     m = n_keep + n_clone + 2 * n_split
     b = Buffers()
     d_rank = b.out(m)
-    assert lib.emd_densify_split_rank(m, n_keep, n_clone, n_split, d_rank.data_ptr(), _stream()) == L.EMD_OK
+    assert lib.emd_densify_split_rank(m, n_keep, n_clone, n_split, d_rank.data_ptr(), L.stream()) == L.EMD_OK
     b.check()
     _expect(d_rank, R.split_rank_densify(m, n_keep, n_clone, n_split), "rank")
 
@@ -228,7 +224,7 @@ def _chain(n, cols, decide, index, want_code, want_index):
     _expect(d_code, want_code, "code")
     counts = R.block_counts(want_code, cols)
     _expect(d_col, counts, "block counts")
-    assert lib.emd_densify_scan(n, cols, d_col.data_ptr(), d_tot.data_ptr(), _stream()) == L.EMD_OK
+    assert lib.emd_densify_scan(n, cols, d_col.data_ptr(), d_tot.data_ptr(), L.stream()) == L.EMD_OK
     b.check()
     offsets, totals = R.exclusive_offsets(counts)
     _expect(d_col, offsets, "block offsets")
@@ -243,9 +239,9 @@ def _chain(n, cols, decide, index, want_code, want_index):
 
 
 def _densify_index_call(n):
-    lib = _lib()[1]
+    L, lib = _lib()
     return lambda m, code, off, tot, outs: lib.emd_densify_index(n, m, code.data_ptr(), off.data_ptr(), tot.data_ptr(), outs[0].data_ptr(),
-                                                                 outs[1].data_ptr(), _stream())
+                                                                 outs[1].data_ptr(), L.stream())
 
 
 def _run_densify(n, inp):
@@ -256,7 +252,7 @@ def _run_densify(n, inp):
         a.num_points, a.mode = n, L.DENSIFY_MODE_DENSIFY
         a.scaling, a.grad_accum, a.denom = (b.put(inp[k]).data_ptr() for k in ("scaling", "grad_accum", "denom"))
         a.grad_threshold, a.size_threshold = float(inp["grad_threshold"]), float(inp["size_threshold"])
-        return lib.emd_densify_decide(C.byref(a), d_code.data_ptr(), d_col.data_ptr(), _stream())
+        return lib.emd_densify_decide(C.byref(a), d_code.data_ptr(), d_col.data_ptr(), L.stream())
     code = R.decide_densify(inp["scaling"], inp["grad_accum"], inp["denom"], inp["grad_threshold"], inp["size_threshold"])
     _chain(n, 3, decide, _densify_index_call(n), code, R.index_densify(code))
     return code
@@ -272,7 +268,7 @@ def _run_prune(n, inp):
         if inp["extra_drop"] is not None:
             a.extra_drop = b.put(inp["extra_drop"]).data_ptr()
         a.min_opacity, a.max_screen_size, a.size_threshold = float(inp["min_opacity"]), float(inp["max_screen_size"]), float(inp["size_threshold"])
-        return lib.emd_densify_decide(C.byref(a), d_code.data_ptr(), d_col.data_ptr(), _stream())
+        return lib.emd_densify_decide(C.byref(a), d_code.data_ptr(), d_col.data_ptr(), L.stream())
     code = R.decide_prune(inp["scaling"], inp["opacity"], inp["max_radii2D"], inp["extra_drop"], inp["min_opacity"], inp["max_screen_size"],
                           inp["size_threshold"])
     _chain(n, 3, decide, _densify_index_call(n), code, R.index_densify(code))
@@ -290,11 +286,11 @@ def _run_refine(n, inp, flags, ns):
                                                                          for k in ("scaling", "opacity", "grad_norm", "vis_counts", "max_2Dsize"))
         for k, v in inp["thr"].items():
             setattr(a, k, float(v))
-        return lib.emd_refine_decide(C.byref(a), d_code.data_ptr(), d_col.data_ptr(), _stream())
+        return lib.emd_refine_decide(C.byref(a), d_code.data_ptr(), d_col.data_ptr(), L.stream())
 
     def index(m, code, off, tot, outs):
         return lib.emd_refine_index(n, m, ns, code.data_ptr(), off.data_ptr(), tot.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                                    _stream())
+                                    L.stream())
     code = R.decide_refine(flags, inp["scaling"], inp["opacity"], inp["grad_norm"], inp["vis_counts"], inp["max_2Dsize"], inp["thr"])
     _chain(n, 4, decide, index, code, R.index_refine(code, ns))
     return code
@@ -389,7 +385,7 @@ def test_after_train_stats(n, stride):
                 if t is not None:
                     t[:n] = torch.from_numpy(init.view(np.int32).copy()).to(DEV)
             ptr = [None if t is None else t.data_ptr() for t in outs]
-            rc = lib.emd_after_train_stats(n, d_radii.data_ptr(), d_grad.data_ptr(), stride, ptr[0], ptr[1], ptr[2], last_size, _stream())
+            rc = lib.emd_after_train_stats(n, d_radii.data_ptr(), d_grad.data_ptr(), stride, ptr[0], ptr[1], ptr[2], last_size, L.stream())
             assert rc == L.EMD_OK
             b.check()
             if outs[0] is not None:
@@ -405,7 +401,7 @@ def test_after_train_stats(n, stride):
         d_radii, d_grad = b.put(radii), b.put(grad)
         outs = [b.out(n) for _ in range(3)]
         rc = lib.emd_after_train_stats(n, d_radii.data_ptr(), d_grad.data_ptr(), bad_stride, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                                       bad_last, _stream())
+                                       bad_last, L.stream())
         assert rc == L.EMD_ERR_INVALID
         b.check()
         assert all((_read(t, n) == SENTINEL).all() for t in outs)

@@ -3,8 +3,6 @@ its three places, workspace sizing, and the numpy restatement of the pinned asso
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -17,16 +15,9 @@ HEADER = os.path.join(ROOT, "include", "emd_raster.h")
 
 
 def test_struct_sizes_match_the_c_compiler():
-    prog = '#include <stdio.h>\n#include "emd_raster.h"\nint main(void){printf("%zu %zu %d %d\\n", sizeof(EmdSegSumArgs), sizeof(EmdBwdArgs), ' \
-           '(int)EMD_FLAG_DETERMINISTIC, (int)EMD_SEG_CHUNK);return 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(c, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        seg, bwd, flag, chunk = (int(x) for x in subprocess.check_output([exe]).split())
-    assert seg == C.sizeof(L.EmdSegSumArgs) and bwd == C.sizeof(L.EmdBwdArgs)
-    assert flag == L.FLAG_DETERMINISTIC == 1 << 12
-    assert chunk == L.SEG_CHUNK == sg.SEG_CHUNK
+    """What the compiler cannot say (sizes, offsets and the header's constants: tests/test_abi.py): the flag's bit, the checker's chunk, the tail."""
+    assert L.FLAG_DETERMINISTIC == 1 << 12
+    assert L.SEG_CHUNK == sg.SEG_CHUNK
     # det_ws / det_bytes are the LAST two fields of EmdBwdArgs
     assert [f[0] for f in L.EmdBwdArgs._fields_[-2:]] == ["det_ws", "det_bytes"]
     assert L.EmdBwdArgs.det_bytes.offset + C.sizeof(C.c_size_t) == C.sizeof(L.EmdBwdArgs)

@@ -380,15 +380,15 @@ def test_flag_without_workspace_and_with_pair_stats():
     b = tc._bwd_args(hip, case, None, outs)
     lib = L.load()
     b.flags = hip["call"].flags | L.FLAG_DETERMINISTIC
-    assert lib.emd_raster_backward(C.byref(b), tc._st()) == L.EMD_ERR_WORKSPACE
+    assert lib.emd_raster_backward(C.byref(b), L.stream()) == L.EMD_ERR_WORKSPACE
     assert b"det_ws" in lib.emd_last_error() and b"emd_raster_det_workspace_size" in lib.emd_last_error()
     need = L.det_workspace_size(case["N"], hip["call"].capacity, 0)
     ws = torch.empty(need, device=DEV, dtype=torch.uint8)
     b.det_ws, b.det_bytes = ws.data_ptr(), need - 1
-    assert lib.emd_raster_backward(C.byref(b), tc._st()) == L.EMD_ERR_WORKSPACE
+    assert lib.emd_raster_backward(C.byref(b), L.stream()) == L.EMD_ERR_WORKSPACE
     stats = torch.zeros(4, device=DEV, dtype=torch.int64)
     b.det_bytes, b.pair_stats = need, stats.data_ptr()
-    assert lib.emd_raster_backward(C.byref(b), tc._st()) == L.EMD_ERR_INVALID
+    assert lib.emd_raster_backward(C.byref(b), L.stream()) == L.EMD_ERR_INVALID
     assert b"pair_stats" in lib.emd_last_error()
     torch.cuda.synchronize()
     assert not stats.any()
@@ -397,6 +397,6 @@ def test_flag_without_workspace_and_with_pair_stats():
     color = hip["outs"][0]
     gC = torch.from_numpy(case["dL_dcolor"]).to(DEV)
     b.dL_dcolor = gC.data_ptr()
-    assert lib.emd_raster_backward(C.byref(b), tc._st()) == 0, lib.emd_last_error()
+    assert lib.emd_raster_backward(C.byref(b), L.stream()) == 0, lib.emd_last_error()
     torch.cuda.synchronize()
     assert outs["means3D"].abs().max() > 0 and color.abs().max() > 0

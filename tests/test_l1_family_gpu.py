@@ -7,8 +7,6 @@ float4), 4095, 4096, 4097, 2*4096+3 (one block and its edges, two blocks), 512*4
 of the stride loop and a scalar tail).  The two backward kernels run 256 lanes of float4 per block and cap at 8192 blocks: n = 0, 1, 3, 4, 5,
 1023, 1024, 1025, 8192*1024 (the cap exactly) and 8192*1024+1024+3, the smallest size that enters their stride loop (34 MB per tensor,
 generated on the device).  Every output lies between guard words; inputs are compared bit for bit afterwards."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -22,17 +20,13 @@ BWD_N = (0, 1, 3, 4, 5, 1023, 1024, 1025, 8192 * 1024, 8192 * 1024 + 1024 + 3)
 NAN_BITS = 0x7FC00000
 
 
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def l1(path, n, a, b, loss, grad, scratch=None):
     """a, b, loss, grad, scratch: device addresses or None -> return code (synchronised)."""
     from emd_amd import _lib as L
     if path == "ws":
-        rc = L.load().emd_l1_loss_ws(n, a, b, loss, grad, scratch, stream())
+        rc = L.load().emd_l1_loss_ws(n, a, b, loss, grad, scratch, L.stream())
     else:
-        rc = L.load().emd_l1_loss(n, a, b, loss, grad, stream())
+        rc = L.load().emd_l1_loss(n, a, b, loss, grad, L.stream())
     torch.cuda.synchronize()
     return rc
 
@@ -132,7 +126,7 @@ def test_abs_mean_backward_is_bit_exact(n, g0):
     from emd_amd import _lib as L
     x, g = residual_inputs(n), torch.tensor([g0], device=DEV)
     x0, out = x.clone(), lr.Guarded(n, DEV)
-    assert L.load().emd_abs_mean_backward(n, x.data_ptr(), g.data_ptr(), out.ptr(), stream()) == L.EMD_OK
+    assert L.load().emd_abs_mean_backward(n, x.data_ptr(), g.data_ptr(), out.ptr(), L.stream()) == L.EMD_OK
     torch.cuda.synchronize()
     assert out.guards_intact() and lr.same_bits(x, x0) and float(g[0]) == float(np.float32(g0))
     if n:
@@ -161,7 +155,7 @@ def test_residual_l1_backward_every_pointer_form_is_bit_exact(n):
             fa, fb = (None if gs in ("a_null", "both_null") else 0.37), (None if gs in ("b_null", "both_null") else -1.25)
             oa.buf.fill_(lr.GUARD_BITS); ob.buf.fill_(lr.GUARD_BITS)
             rc = L.load().emd_residual_l1_backward(n, L.ptr(ua), L.ptr(ub), xa.data_ptr(), xb.data_ptr(), None if fa is None else ga.data_ptr(),
-                                                   None if fb is None else gb.data_ptr(), oa.ptr(), ob.ptr(), stream())
+                                                   None if fb is None else gb.data_ptr(), oa.ptr(), ob.ptr(), L.stream())
             torch.cuda.synchronize()
             assert rc == L.EMD_OK and oa.guards_intact() and ob.guards_intact(), (up, gs)
             if n:
@@ -182,7 +176,7 @@ def test_backward_kernels_refuse_bad_arguments_and_write_nothing():
     P = [b.ptr() for b in bufs]
 
     def pair(n_, p):
-        rc = lib.emd_residual_l1_backward(n_, p[0], p[1], p[2], p[3], g.data_ptr(), g.data_ptr(), p[4], p[5], stream())
+        rc = lib.emd_residual_l1_backward(n_, p[0], p[1], p[2], p[3], g.data_ptr(), g.data_ptr(), p[4], p[5], L.stream())
         torch.cuda.synchronize()
         assert bufs[4].untouched() and bufs[5].untouched()
         return rc
@@ -193,7 +187,7 @@ def test_backward_kernels_refuse_bad_arguments_and_write_nothing():
     assert pair(-1, P) == L.EMD_ERR_INVALID
 
     def single(n_, x, gp, out):
-        rc = lib.emd_abs_mean_backward(n_, x, gp, out, stream())
+        rc = lib.emd_abs_mean_backward(n_, x, gp, out, L.stream())
         torch.cuda.synchronize()
         assert bufs[4].untouched()
         return rc

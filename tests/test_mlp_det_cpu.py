@@ -197,18 +197,6 @@ def test_reduce_and_temporal_refusals():
     assert te(P, 3, 150, 32, 30, P, P, P, P, None, None) == L.EMD_ERR_WORKSPACE          # dL/dt of several tables needs one partial per table
 
 
-def test_struct_sizes_match_the_header():
-    import subprocess
-    import tempfile
-    prog = '#include <stdio.h>\n#include "emd_raster.h"\nint main(void){printf("%zu %zu\\n", sizeof(EmdMlpDetLayout), sizeof(EmdMlpDetJob));return 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "s")])
-        sizes = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert sizes == [C.sizeof(L.EmdMlpDetLayout), C.sizeof(L.EmdMlpDetJob)]
-
-
 def test_the_switch_is_an_argument_and_defaults_to_off():
     from emd_amd import deformation, mlp
     assert inspect.signature(mlp.level_mlp).parameters["deterministic"].default is False

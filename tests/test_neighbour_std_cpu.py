@@ -1,7 +1,7 @@
 """-m "not gpu": the segmented k-NN and the neighbour-std regulariser (emd_knn_segments, emd_neighbour_std_forward / _backward; DESIGN.md section
 8.19) without a GPU: the fp64 restatement of tests/neighbour_std_ref.py against plain Python, the input conditions of every case the GPU tests
-use, an fp32 emulation of the contract's operation order against the GPU tolerances on those inputs, the host-only refusals, and the struct
-mirror."""
+use, an fp32 emulation of the contract's operation order against the GPU tolerances on those inputs, and the host-only refusals (the struct
+mirror: tests/test_abi.py)."""
 import ctypes as C
 import math
 import os
@@ -30,20 +30,6 @@ def test_new_symbols_exported_and_constants_match_the_header():
         assert int(re.search(rf"#define EMD_NSTD_ACT_{name.upper()} (\d+)", src).group(1)) == code
     assert int(re.search(r"#define EMD_ABI_VERSION (\d+)", src).group(1)) == 31 == L.ABI_VERSION
     assert lib.emd_neighbour_std_workspace_size() >= 16
-
-
-def test_struct_layout_matches_c():
-    import subprocess
-    import tempfile
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "emd_raster.h"\nint main(void){printf("%zu %zu %zu %zu\\n", sizeof(EmdNeighbourStdArgs),' \
-           ' offsetof(EmdNeighbourStdArgs, x), offsetof(EmdNeighbourStdArgs, stash), offsetof(EmdNeighbourStdArgs, dx));return 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(c, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        sizes = [int(x) for x in subprocess.check_output([exe]).split()]
-    T = L.EmdNeighbourStdArgs
-    assert sizes == [C.sizeof(T), T.x.offset, T.stash.offset, T.dx.offset]
 
 
 def _args(n=10, k=2, blocks=1, cols=4, act=0, weight=1.0):

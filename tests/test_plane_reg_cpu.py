@@ -1,10 +1,8 @@
 """-m "not gpu": the HexPlane regularisers (emd_amd.hexplane.plane_regulation, csrc/plane_reg.hip) without a GPU -- the inputs of the GPU tests
 validated (the fp32 torch formulation meets the criterion against the fp64 restatement on every case), closed forms of the restatement, and the
-host layer: exported symbols, struct layout, argument validation, the refusal of CPU tensors, the GaussianModel methods without a network."""
+host layer: exported symbols, argument validation, the refusal of CPU tensors, the GaussianModel methods without a network.  (The struct's
+layout and the constants: tests/test_abi.py.)"""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -12,8 +10,6 @@ import torch
 from emd_amd import _lib as L
 from emd_amd import hexplane
 from tests import plane_reg_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the reference and the cases -------------------------------------------------------------------------
@@ -60,8 +56,6 @@ def test_restatement_closed_forms():
 # ---- host layer ------------------------------------------------------------------------------------------
 
 NEW_SYMBOLS = ("emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward")
-FIELDS = ("channels", "num_scales", "res", "planes", "plane_tv_weight", "time_smoothness_weight", "l1_time_planes_weight", "reserved", "out", "g",
-          "dL_dplanes")
 
 
 def test_new_symbols_exported():
@@ -69,25 +63,6 @@ def test_new_symbols_exported():
     for n in NEW_SYMBOLS:
         assert n in L.EXPORTED_SYMBOLS and hasattr(lib, n)
     assert lib.emd_abi_version() == L.ABI_VERSION
-
-
-def test_new_struct_layout_matches_c():
-    assert tuple(n for n, *_ in L.EmdPlaneRegArgs._fields_) == FIELDS
-    prints = "".join(f'printf("%zu ", offsetof(EmdPlaneRegArgs, {f}));' for f in FIELDS)
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "emd_raster.h"
-int main(void){printf("%zu %d %d ", sizeof(EmdPlaneRegArgs), EMD_PLANE_REG_SEG, EMD_HEX_MAX_SCALES);''' + prints + r'''printf("\n");return 0;}
-'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert got[:3] == [C.sizeof(L.EmdPlaneRegArgs), L.PLANE_REG_SEG, L.HEX_MAX_SCALES]
-    assert got[3:] == [getattr(L.EmdPlaneRegArgs, f).offset for f in FIELDS]
 
 
 FAKE = 0x1000        # a non-null, 16-byte aligned pointer value: every call below is refused on the host, before anything is launched or read

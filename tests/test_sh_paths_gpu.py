@@ -28,10 +28,6 @@ def _same_bits(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _nan(*shape):
     return torch.full(shape, float("nan"), device=DEV, dtype=torch.float32)
 
@@ -107,8 +103,8 @@ def test_c_every_output_element_is_written_and_nothing_past_row_n(deg, M):
     lib, case, ref = L.load(), R.sh_case(deg, M, N), R.sh_reference(deg, M, N)
     dirs, coeffs, g = _on_device(case, "dirs", "coeffs", "g")
     rgb, d_coeffs, d_dirs = _nan(N + 1, 3), _nan(N + 1, M, 3), _nan(N + 1, 3)
-    assert lib.emd_sh_forward(N, deg, M, dirs.data_ptr(), coeffs.data_ptr(), rgb.data_ptr(), _stream()) == L.EMD_OK
-    assert lib.emd_sh_backward(N, deg, M, dirs.data_ptr(), coeffs.data_ptr(), g.data_ptr(), d_coeffs.data_ptr(), d_dirs.data_ptr(), _stream()) == L.EMD_OK
+    assert lib.emd_sh_forward(N, deg, M, dirs.data_ptr(), coeffs.data_ptr(), rgb.data_ptr(), L.stream()) == L.EMD_OK
+    assert lib.emd_sh_backward(N, deg, M, dirs.data_ptr(), coeffs.data_ptr(), g.data_ptr(), d_coeffs.data_ptr(), d_dirs.data_ptr(), L.stream()) == L.EMD_OK
     for buf, key in ((rgb, "colour"), (d_coeffs, "d_coeffs"), (d_dirs, "d_dirs")):
         assert not bool(torch.isnan(buf[:N]).any()), key
         assert bool(torch.isnan(buf[N]).all()), key + ": the row past N is untouched"
@@ -123,8 +119,8 @@ def test_d_argument_checks_refuse_and_launch_nothing():
     dirs, coeffs, g = _on_device(case, "dirs", "coeffs", "g")
     rgb, d_coeffs, d_dirs = _nan(N, 3), _nan(N, M, 3), _nan(N, 3)
     p = lambda t: t.data_ptr()
-    fwd = lambda n=N, d=deg, m=M, a=p(dirs), b=p(coeffs), c=p(rgb): lib.emd_sh_forward(n, d, m, a, b, c, _stream())
-    bwd = lambda n=N, d=deg, m=M, a=p(dirs), b=p(coeffs), c=p(g): lib.emd_sh_backward(n, d, m, a, b, c, p(d_coeffs), p(d_dirs), _stream())
+    fwd = lambda n=N, d=deg, m=M, a=p(dirs), b=p(coeffs), c=p(rgb): lib.emd_sh_forward(n, d, m, a, b, c, L.stream())
+    bwd = lambda n=N, d=deg, m=M, a=p(dirs), b=p(coeffs), c=p(g): lib.emd_sh_backward(n, d, m, a, b, c, p(d_coeffs), p(d_dirs), L.stream())
     for call in (fwd, bwd):
         assert call(d=-1) == L.EMD_ERR_INVALID
         assert call(d=4) == L.EMD_ERR_INVALID
@@ -153,7 +149,7 @@ def _factors_c(case, deg, rows, scale, out):
     if per_view:
         mo.actor_pose = pose.data_ptr()
     rc = L.load().emd_sh_grad_from_factors(case["N"], case["V"], deg, rows, means.data_ptr(), C.byref(mo), 1 if per_view else 0, campos.data_ptr(),
-                                           factors.data_ptr(), float(scale), out.data_ptr(), _stream())
+                                           factors.data_ptr(), float(scale), out.data_ptr(), L.stream())
     torch.cuda.synchronize()                                            # (the device copies above live until the launch has run)
     return rc
 

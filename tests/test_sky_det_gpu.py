@@ -24,10 +24,6 @@ def _dev():
     return torch.device("cuda", 0)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _refuse(name):
     def f(*a, **k):
         raise AssertionError(f"{name} must not be called here")
@@ -69,9 +65,9 @@ def _backward(inp, det, want_cube=True, ws=None):
             ws = torch.empty(L.sky_det_workspace_size(P), dtype=torch.uint8, device=dev)
             ws.fill_(0xA5)                                                                             # never cleared by the call, and need not be
         lay = L.sky_det_layout(P, res)
-        L.check(lib.emd_sky_backward_det(C.byref(b), L.ptr(ws), 0 if ws is None else ws.numel(), _stream()), "emd_sky_backward_det")
+        L.check(lib.emd_sky_backward_det(C.byref(b), L.ptr(ws), 0 if ws is None else ws.numel(), L.stream()), "emd_sky_backward_det")
     else:
-        L.check(lib.emd_sky_backward(C.byref(b), _stream()), "emd_sky_backward")
+        L.check(lib.emd_sky_backward(C.byref(b), L.stream()), "emd_sky_backward")
     torch.cuda.synchronize()
     n = lambda x: None if x is None else x.cpu().numpy()
     return dict(d_cube=n(d_cube), d_fg=n(d_fg), d_acc=n(d_acc), ws=ws, lay=lay)

@@ -40,10 +40,6 @@ def _refuse_defaults(monkeypatch):
         monkeypatch.setattr(L.load(), name, _refuse(name))
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 # ---- 1. the row sum ---------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _rows_case(n, sizes, width, seed=0):
@@ -69,7 +65,7 @@ def _row_sum(ids, rows, width, A, seg=None):
     seg_d = None if seg is None else torch.from_numpy(seg).to(DEV)
     out = torch.full((A, width), float("nan"), device=DEV)
     L.check(L.load().emd_actor_row_sum_det(n, width, buf.data_ptr() + nbytes, pitch, ids_d.data_ptr(), A, L.ptr(seg_d), out.data_ptr(), width, buf.data_ptr(),
-                                           nbytes, _stream()), "emd_actor_row_sum_det")
+                                           nbytes, L.stream()), "emd_actor_row_sum_det")
     torch.cuda.synchronize()
     lay = dict(lay, rows=nbytes)
     return out.cpu().numpy(), buf, lay
@@ -414,9 +410,9 @@ def test_embedding_gradient_of_the_heads_form_has_the_default_entrys_bits(order)
             gr.d_head_w[h], gr.d_head_b[h] = bufs["d_heads"][2 * h].data_ptr(), bufs["d_heads"][2 * h + 1].data_ptr()
         if det:
             ws = torch.empty(L.track_det_workspace_size(A, width), dtype=torch.uint8, device=DEV)
-            L.check(L.load().emd_track_heads_backward_det(C.byref(a), C.byref(gr), ws.data_ptr(), ws.numel(), _stream()), "emd_track_heads_backward_det")
+            L.check(L.load().emd_track_heads_backward_det(C.byref(a), C.byref(gr), ws.data_ptr(), ws.numel(), L.stream()), "emd_track_heads_backward_det")
         else:
-            L.check(L.load().emd_track_heads_backward(C.byref(a), C.byref(gr), _stream()), "emd_track_heads_backward")
+            L.check(L.load().emd_track_heads_backward(C.byref(a), C.byref(gr), L.stream()), "emd_track_heads_backward")
         torch.cuda.synchronize()
         got[det] = bufs["d_emb"]
     assert bool(torch.isfinite(got[True]).all()) and float(got[True].abs().min()) > 0

@@ -1,12 +1,9 @@
 """-m "not gpu": the image tail of an OmniRe step (emd_amd.trainer_loss, csrc/trainer_loss.hip) without a GPU -- the inputs of the GPU tests
 validated (the fp32 torch formulation meets the criterion against the fp64 restatement on every case, so a failure on the GPU is the kernel's),
-closed forms of the restatement, and the host layer: exported symbols, struct layout, ABI, argument validation, the options that are not built and
-the refusal of CPU tensors."""
+closed forms of the restatement, and the host layer: exported symbols, ABI, argument validation, the options that are not built and the refusal
+of CPU tensors.  (The struct's layout and the constants: tests/test_abi.py.)"""
 import ctypes as C
 import math
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -14,8 +11,6 @@ import torch
 from emd_amd import _lib as L
 from emd_amd import trainer_loss as TL
 from tests import trainer_loss_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the reference and the cases -------------------------------------------------------------------------
@@ -119,8 +114,6 @@ def test_restatement_closed_forms():
 # ---- host layer ------------------------------------------------------------------------------------------
 
 NEW_SYMBOLS = ("emd_affine_workspace_size", "emd_affine_forward", "emd_affine_backward", "emd_trainer_loss_workspace_size", "emd_trainer_loss")
-FIELDS = ("height", "width", "mask_type", "depth_type", "normalize", "inverse", "rgb", "gt_rgb", "opacity", "sky_mask", "depth", "lidar_depth",
-          "w_rgb", "w_ssim", "w_mask", "safe_limit", "w_depth", "upper_bound", "w_entropy", "w_smooth", "losses", "dL_drgb", "dL_dopacity", "dL_ddepth")
 
 
 def test_new_symbols_exported_and_abi_unchanged():
@@ -128,27 +121,6 @@ def test_new_symbols_exported_and_abi_unchanged():
     for n in NEW_SYMBOLS:
         assert n in L.EXPORTED_SYMBOLS and hasattr(lib, n)
     assert lib.emd_abi_version() == L.ABI_VERSION == 31
-
-
-def test_new_struct_layout_and_constants_match_c():
-    assert tuple(n for n, *_ in L.EmdTrainerLossArgs._fields_) == FIELDS
-    prints = "".join(f'printf("%zu ", offsetof(EmdTrainerLossArgs, {f}));' for f in FIELDS)
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "emd_raster.h"
-int main(void){printf("%zu %d %d %d %d %d %d %d ", sizeof(EmdTrainerLossArgs), EMD_TRAINER_LOSS_CHUNK, EMD_TRAINER_SSIM_TILE, EMD_TL_MASK_BCE,
- EMD_TL_MASK_SAFE_BCE, EMD_TL_DEPTH_L1, EMD_TL_DEPTH_L2, EMD_TL_DEPTH_SMOOTH_L1);''' + prints + r'''printf("\n");return 0;}
-'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert got[:8] == [C.sizeof(L.EmdTrainerLossArgs), L.TRAINER_LOSS_CHUNK, L.TRAINER_SSIM_TILE, L.TL_MASK_BCE, L.TL_MASK_SAFE_BCE, L.TL_DEPTH_L1,
-                       L.TL_DEPTH_L2, L.TL_DEPTH_SMOOTH_L1]
-    assert got[8:] == [getattr(L.EmdTrainerLossArgs, f).offset for f in FIELDS]
 
 
 FAKE = 0x1000        # a non-null, 16-byte aligned pointer value: every call below is refused on the host, before anything is launched or read

@@ -28,10 +28,6 @@ UPS = dict(_opacities="g_opacities", _scales="g_scales", _quats="g_quats", _rgbs
 IDS = lambda c: "-".join(map(str, c))
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _leaves(c):
     return {k: c[k].to(DEV).requires_grad_(True) for k in LEAVES}
 
@@ -75,7 +71,7 @@ def test_dictionary_and_all_five_gradients_match_the_fp64_reference(case):
     # the bits of the existing ops
     ls, rq, lo = leaves["log_scales"].detach(), leaves["quats"].detach(), leaves["opacity_logits"].detach()
     s, q, o = torch.empty_like(ls), torch.empty_like(rq), torch.empty_like(lo)
-    L.check(L.load().emd_activations_forward(N, ls.data_ptr(), s.data_ptr(), rq.data_ptr(), q.data_ptr(), lo.data_ptr(), o.data_ptr(), _stream()),
+    L.check(L.load().emd_activations_forward(N, ls.data_ptr(), s.data_ptr(), rq.data_ptr(), q.data_ptr(), lo.data_ptr(), o.data_ptr(), L.stream()),
             "emd_activations_forward")
     assert torch.equal(gs["_scales"], s) and torch.equal(gs["_quats"], q) and torch.equal(gs["_opacities"], o)
     if c["sh_mode"]:
@@ -192,8 +188,8 @@ def test_every_output_element_is_written_and_nothing_beside_it(case):
     a.dL_dquats, a.dL_dopacity_logits, a.dL_dlog_scales, a.dL_dfeatures_dc = ptrs[:4]
     a.dL_dfeatures_rest = ptrs[4] if M > 1 else None
     lib = L.load()
-    L.check(lib.emd_vanilla_forward(C.byref(a), _stream()), "emd_vanilla_forward")
-    L.check(lib.emd_vanilla_backward(C.byref(a), _stream()), "emd_vanilla_backward")
+    L.check(lib.emd_vanilla_forward(C.byref(a), L.stream()), "emd_vanilla_forward")
+    L.check(lib.emd_vanilla_backward(C.byref(a), L.stream()), "emd_vanilla_backward")
     torch.cuda.synchronize()
     assert _guards_untouched(obuf, ooff, out_sizes) and _guards_untouched(gbuf, goff, grad_sizes)
     assert bool((mask[:GUARD] == 0xAB).all()) and bool((mask[GUARD + N:] == 0xAB).all()) and bool((mask[GUARD:GUARD + N] <= 7).all())
@@ -295,8 +291,8 @@ def test_regulariser_outputs_and_workspace_are_written_and_nothing_beside_them(n
     a.w_sharp, a.max_gauss_ratio, a.w_flatten, a.w_sparse, a.w_max_s_square = w["w_sharp"], w["max_gauss_ratio"], w["w_flatten"], w["w_sparse"], w["w_max_s_square"]
     a.terms, a.dL_dlog_scales, a.dL_dopacity_logits = (buf.data_ptr() + 4 * o for o in offs)
     a.g = up.data_ptr()
-    L.check(lib.emd_vanilla_reg_forward(C.byref(a), ws.data_ptr() + 256, nbytes, _stream()), "emd_vanilla_reg_forward")
-    L.check(lib.emd_vanilla_reg_backward(C.byref(a), ws.data_ptr() + 256, nbytes, _stream()), "emd_vanilla_reg_backward")
+    L.check(lib.emd_vanilla_reg_forward(C.byref(a), ws.data_ptr() + 256, nbytes, L.stream()), "emd_vanilla_reg_forward")
+    L.check(lib.emd_vanilla_reg_backward(C.byref(a), ws.data_ptr() + 256, nbytes, L.stream()), "emd_vanilla_reg_backward")
     torch.cuda.synchronize()
     assert _guards_untouched(buf, offs, sizes)
     assert bool((ws[:256] == 0xFF).all()) and bool((ws[256 + nbytes:] == 0xFF).all())
