@@ -31,6 +31,10 @@ __device__ __forceinline__ float wave_scan_add_f32(float v) {
 __device__ __forceinline__ float wave_shift_up1_f32(float v, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, false));
 }
+// The same shift with lane 0 receiving 0: bound_ctrl makes the hardware write the zero, so no register has to be set to the fill value first.
+__device__ __forceinline__ float wave_shift_up1_zero_f32(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), DPP_WAVE_SHR1, 0xf, 0xf, true));
+}
 
 // Hand-fused scans: one VALU op per step (v_mul_f32_dpp / v_add_f32_dpp with the destination doubling as `old`, so
 // lanes without a valid source keep their value); hipcc emits v_mov_b32_dpp + v_mul_f32 (+ an identity v_mov) per

@@ -403,7 +403,7 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
     // ~15 v_readlane / v_mov / v_cndmask per pixel-iteration off the VALU, which is what bounds this kernel.
     // Pixels are handled in horizontal pairs (a, b) = (2 pp, 2 pp + 1); every quantity is stored as the pair:
     //   [pp][0] = (dC0 a,b | dC1 a,b)  [pp][1] = (dC2 a,b | dD a,b)  [pp][2] = (running T a,b | running S a,b)
-    //   [pp][3] = (Q a,b | -)          [pp][4] = (dN0 a,b | dN1 a,b) [pp][5] = (dN2 a,b | -)
+    //   [pp][3] = (Q a,b | n_contrib a,b as bits)   [pp][4] = (dN0 a,b | dN1 a,b) [pp][5] = (dN2 a,b | -)
     //   [pp][PB + 2k] = (dX_k0 a,b | dX_k1 a,b)  [pp][PB + 2k + 1] = (dX_k2 a,b | -)     gradients of extra colour set k
     __shared__ float4 s_pix[EMD_WAVE / 2][PB + 2 * NX];
     __shared__ uint32_t s_myn[EMD_WAVE];                        // n_contrib of the quadrant's pixels (half-wave batches read it per lane)
@@ -413,6 +413,8 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
     const uint32_t lane = threadIdx.x;
     const float tile_x0 = (float)((tile % (uint32_t)d.gx) * EMD_TILE_X), tile_y0 = (float)((tile / (uint32_t)d.gx) * EMD_TILE_Y);
     const float qx0 = tile_x0 + (float)((quad & 1) * 8), qy0 = tile_y0 + (float)((quad >> 1) * 8);
+    // (the same origin as wave-uniform integers: the pixel loop forms its pixel centres from them with scalar adds)
+    const int qxi = (int)((tile % (uint32_t)d.gx) * EMD_TILE_X + (quad & 1) * 8), qyi = (int)((tile / (uint32_t)d.gx) * EMD_TILE_Y + (quad >> 1) * 8);
     const int px = (int)qx0 + (int)(lane & 7), py = (int)qy0 + (int)(lane >> 3);
     const bool inside = px < d.W && py < d.H;
     const uint32_t start = ranges[2 * tile], n_tile = ranges[2 * tile + 1] - start;
@@ -451,7 +453,7 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
         float* sp = reinterpret_cast<float*>(&s_pix[lane >> 1][0]) + (lane & 1);
         sp[0] = dC0; sp[2] = dC1; sp[4] = dC2; sp[6] = dD;
         sp[8] = Tf; sp[10] = 0.f;       // transmittance behind / weighted colour behind the entries processed so far (back to front)
-        sp[12] = Q; sp[14] = 0.f;
+        sp[12] = Q; sp[14] = __uint_as_float(my_n);     // (n_contrib rides beside Q as bits: the 64-lane pixel loop takes both from one broadcast read)
         if (NORMAL) { sp[16] = dN0; sp[18] = dN1; sp[20] = dN2; sp[22] = 0.f; }
 #pragma unroll
         for (int k = 0; k < NX; k++) { float* sx_ = sp + 4 * (PB + 2 * k); sx_[0] = dX[k][0]; sx_[2] = dX[k][1]; sx_[4] = dX[k][2]; sx_[6] = 0.f; }
@@ -479,30 +481,27 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
         const v2f z2 = splat2(0.f);
         v2f m0_2 = z2, gx_2 = z2, gy_2 = z2, m2xx_2 = z2, m2xy_2 = z2, m2yy_2 = z2, dz_2 = z2, r_2 = z2, g_2 = z2, b_2 = z2;
         float a_ax = 0.f, a_ay = 0.f;
-        for (int pp0 = 0; pp0 < (HALF ? EMD_WAVE / 4 : EMD_WAVE / 2); pp0++) {
-            const int pp = HALF ? pp0 + (int)(hp * (EMD_WAVE / 4)) : pp0;                    // (per lane half in the HALF form)
-            uint32_t n_a, n_b;
-            if (HALF) {
-                n_a = s_myn[2 * pp]; n_b = s_myn[2 * pp + 1];
-                if (__ballot(max(n_a, n_b) > last_pos) == 0ull) continue;
-            } else {
-                n_a = readlane_u32(my_n, 2 * pp); n_b = readlane_u32(my_n, 2 * pp + 1);
-                if (max(n_a, n_b) <= last_pos) continue;         // both pixels terminated before the shallowest entry of this batch
-            }
+        // a lane without an entry carries the largest number, so that `posv < n` is false in it for every pixel
+        const uint32_t posv = valid ? pos : 0xFFFFFFFFu;
+        // One pixel pair (a, b) = (2 pp, 2 pp + 1) against the batch; n_a, n_b = n_contrib of the two pixels.
+        auto pixel_pair = [&](const int pp, const uint32_t n_a, const uint32_t n_b) {
             const float4 c01 = s_pix[pp][0], c2d = s_pix[pp][1], ts = s_pix[pp][2], qq = s_pix[pp][3];
-            const float pxs = qx0 + (float)((2 * pp) & 7), pys = qy0 + (float)(pp >> 2);
+            // pixel centres: the integer sum converted once (the coordinates are whole numbers below 2^24, so this is qx0 + (float)k exactly)
+            const int pxi = qxi + ((2 * pp) & 7);
+            const float pxs = (float)pxi, pxs1 = (float)(pxi + 1), pys = (float)(qyi + (pp >> 2));
             const float dy = g0.y - pys;
-            const v2f dx = (v2f){g0.x - pxs, g0.x - (pxs + 1.f)};
+            const v2f dx = (v2f){g0.x - pxs, g0.x - pxs1};
             const v2f power = gauss_power2(g1.x, g1.y, g1.z, dx, dy);
             // (the hardware v_exp_f32 with a pinned re-evaluation next to the 1/255 threshold was measured in round 3: 0.489 vs 0.494 ms,
             //  i.e. nothing, while its 1-ulp differences cost the end-to-end rotation bar of one sweep scene its margin: not kept)
             const v2f G = pinned_exp2(power);
             const v2f aw = splat2(g0.w) * G;
             const v2f alpha = (v2f){fminf(0.99f, aw.x), fminf(0.99f, aw.y)};
-            const bool hit_a = valid && pos < n_a && power.x <= 0.f && alpha.x >= (1.f / 255.f);
-            const bool hit_b = valid && pos < n_b && power.y <= 0.f && alpha.y >= (1.f / 255.f);
+            const bool hit_a = posv < n_a && power.x <= 0.f && alpha.x >= (1.f / 255.f);
+            const bool hit_b = posv < n_b && power.y <= 0.f && alpha.y >= (1.f / 255.f);
             if (STATS) { st_eval += (HALF ? 4ull : 2ull) * nb; st_hit += (unsigned long long)(__popcll(__ballot(hit_a)) + __popcll(__ballot(hit_b))); }
-            if (__ballot(hit_a || hit_b) == 0ull) continue;
+            // (the builtin takes the bool as it is: __ballot's int argument costs a v_cndmask and a v_cmp per trip)
+            if (__builtin_amdgcn_ballot_w64(hit_a || hit_b) == 0ull) return;
             const v2f a = (v2f){hit_a ? alpha.x : 0.f, hit_b ? alpha.y : 0.f};
             const v2f om = splat2(1.f) - a;
             const v2f inv = (v2f){__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
@@ -529,7 +528,7 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
             const v2f gw = g * w;
             float s_a = gw.x, s_b = gw.y;
             if (HALF) half_scan_add2_f32_asm(s_a, s_b); else wave_scan_add2_f32_asm(s_a, s_b);
-            float ex_a = wave_shift_up1_f32(s_a, 0.f), ex_b = wave_shift_up1_f32(s_b, 0.f);
+            float ex_a = wave_shift_up1_zero_f32(s_a), ex_b = wave_shift_up1_zero_f32(s_b);
             if (HALF && lane == 32u) { ex_a = 0.f; ex_b = 0.f; }                             // (lane 32 is the deepest entry of its half)
             const v2f Rk = cR + (v2f){ex_a, ex_b};
             // dL/dalpha_k = g_k T_k - R_k / (1 - alpha_k) + T_final (dL/dalpha_img - bg . dL/dC) / (1 - alpha_k)
@@ -554,6 +553,25 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
             }
             // lane 63 holds the batch totals: carry the transmittance and the weighted colour in front of this batch to the next one
             if ((lane & (HALF ? 31u : 63u)) == (HALF ? 31u : 63u)) s_pix[pp][2] = make_float4(cT.x * t_a, cT.y * t_b, cR.x + s_a, cR.y + s_b);
+        };
+        if constexpr (HALF) {
+            for (int pp0 = 0; pp0 < EMD_WAVE / 4; pp0++) {
+                const int pp = pp0 + (int)(hp * (EMD_WAVE / 4));                             // (per lane half)
+                const uint32_t n_a = s_myn[2 * pp], n_b = s_myn[2 * pp + 1];
+                if (__ballot(max(n_a, n_b) > last_pos) == 0ull) continue;     // all four pixels terminated before the shallowest entry of this batch
+                pixel_pair(pp, n_a, n_b);
+            }
+        } else {
+            // The pairs with a pixel that outlives the shallowest entry of this batch, as a wave-uniform bit set (lane = pixel for my_n): the loop runs
+            // over its set bits in ascending order, so a pair whose two pixels terminated earlier costs no vector instruction, and the two n_contrib
+            // of a live pair come from one broadcast read of the plane that holds them beside Q, as the half-wave form reads s_myn.  (It took two
+            // v_readlane per pair, skipped ones included.)
+            const unsigned long long live = __builtin_amdgcn_ballot_w64(my_n > last_pos);
+            for (unsigned long long pm = (live | (live >> 1)) & 0x5555555555555555ull; pm != 0ull; pm &= pm - 1ull) {
+                const int pp = (int)(__builtin_ctzll(pm) >> 1);
+                const uint32_t* const nn = reinterpret_cast<const uint32_t*>(&s_pix[pp][3]) + 2;
+                pixel_pair(pp, nn[0], nn[1]);
+            }
         }
         if (HALF) {
             // the two pixel halves of every entry: lane e += lane e + 32 (both halves end up with the sums)
