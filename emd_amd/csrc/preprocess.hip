@@ -1,6 +1,7 @@
 // preprocess.hip -- K1 (fused explicit motion + projection + EWA covariance + SH colour) and K8 (its backward), with the two small
 // kernels that read K1's records (k_sh_factor, k_export_geometry).  gfx950, one Gaussian per lane.  The per-Gaussian math K1 / K8 share
-// with the stand-alone entry points (standalone_ops.hip) is in gaussian_math.h.
+// with the stand-alone entry points (standalone_ops.hip) is in gaussian_math.h; the projection chain K1, K8 and the camera-gradient kernel
+// (camera_grad.hip) walk is in projection_math.h, and the blocks of K8 that kernel repeats are the *_body.inc texts named there.
 //
 // Built with -ffp-contract=off: the view depth (sort key), radius and tile rectangle are a bit-exact
 // contract with oracle/raster_oracle.c, so every operation here is an individually rounded fp32 op in
@@ -15,6 +16,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "gaussian_math.h"
+#include "projection_math.h"
 
 #pragma clang fp contract(off)
 
@@ -52,41 +54,6 @@ __device__ __forceinline__ int tile_clamp(float f, int grid) {
     if (!(f > 0.f)) return 0;
     if (f > g) return grid;
     return (int)f;
-}
-
-// Shared by K1 and K8: everything up to cov2D for one visible Gaussian.
-struct Proj {
-    float tx, ty, tz, cx, cy;
-    bool clx, cly;
-    float M0[3], M1[3], T0[3], T1[3];
-    float a, b, c, det;
-};
-
-__device__ __forceinline__ void project_cov2d(const EmdSettings& S, const float m[3], const float c3[6], float fx,
-                                              float fy, Proj& p) {
-    const float* V = S.viewmatrix;
-    float limx = 1.3f * S.tanfovx, limy = 1.3f * S.tanfovy;
-    float txtz = p.tx / p.tz, tytz = p.ty / p.tz;
-    p.clx = (txtz < -limx) || (txtz > limx);
-    p.cly = (tytz < -limy) || (tytz > limy);
-    p.cx = fminf(limx, fmaxf(-limx, txtz)) * p.tz;
-    p.cy = fminf(limy, fmaxf(-limy, tytz)) * p.tz;
-    float J00 = fx / p.tz, J02 = -(fx * p.cx) / (p.tz * p.tz), J11 = fy / p.tz, J12 = -(fy * p.cy) / (p.tz * p.tz);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        p.M0[k] = J00 * V[4 * k + 0] + J02 * V[4 * k + 2];
-        p.M1[k] = J11 * V[4 * k + 1] + J12 * V[4 * k + 2];
-    }
-    const float Sg[9] = {c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        p.T0[k] = (p.M0[0] * Sg[k] + p.M0[1] * Sg[3 + k]) + p.M0[2] * Sg[6 + k];
-        p.T1[k] = (p.M1[0] * Sg[k] + p.M1[1] * Sg[3 + k]) + p.M1[2] * Sg[6 + k];
-    }
-    p.a = ((p.T0[0] * p.M0[0] + p.T0[1] * p.M0[1]) + p.T0[2] * p.M0[2]) + 0.3f;
-    p.b = (p.T0[0] * p.M1[0] + p.T0[1] * p.M1[1]) + p.T0[2] * p.M1[2];
-    p.c = ((p.T1[0] * p.M1[0] + p.T1[1] * p.M1[1]) + p.T1[2] * p.M1[2]) + 0.3f;
-    p.det = p.a * p.c - p.b * p.b;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -159,6 +126,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_waves_per_eu(
         const float fx = (float)W / (2.f * S.tanfovx), fy = (float)H / (2.f * S.tanfovy);
         const bool raw = (a.flags & EMD_FLAG_RAW_PARAMS) != 0;
         {
+            // (twin of gaussian_pose_body.inc, K8's loads and world pose: K1 has no gradient row to stand in for an absent array and forms the pose
+            // inside its branches, so the shared text would change K1's machine code)
             // Round 5 (late), as in K8: every load whose address depends on the index alone is issued here, back to back, before any is used (optional
             // inputs through a pointer that is valid either way -- the Gaussian's own mean stands in --, selected where they are used); then the actor's pose
             // rows.  Before: mean -> actor id -> quaternion / pose rows -> opacity, each behind the wait of the one before.
@@ -196,14 +165,10 @@ __global__ void __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_waves_per_eu(
                 }
             }
         }
-        p.tx = ((V[0] * m[0] + V[4] * m[1]) + V[8] * m[2]) + V[12];
-        p.ty = ((V[1] * m[0] + V[5] * m[1]) + V[9] * m[2]) + V[13];
-        p.tz = ((V[2] * m[0] + V[6] * m[1]) + V[10] * m[2]) + V[14];
+        view_transform(V, m, p.tx, p.ty, p.tz);
         if (p.tz > S.near_plane) {
-            float hx = ((P[0] * m[0] + P[4] * m[1]) + P[8] * m[2]) + P[12];
-            float hy = ((P[1] * m[0] + P[5] * m[1]) + P[9] * m[2]) + P[13];
-            float hw = ((P[3] * m[0] + P[7] * m[1]) + P[11] * m[2]) + P[15];
-            float pw = 1.f / (hw + 0.0000001f);
+            const Clip h = clip_transform(P, m);
+            const float hx = h.hx, hy = h.hy, pw = h.pw;
             float px = hx * pw, py = hy * pw;
             float c3[6];
             if (a.cov3D_precomp) {
@@ -214,7 +179,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_waves_per_eu(
                 if (raw) { sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]); }
                 cov3d_from_sr(sc, S.scale_modifier, q, c3);
             }
-            project_cov2d(S, m, c3, fx, fy, p);
+            project_cov2d(S, c3, fx, fy, p);
             if (p.det != 0.f) {
                 float det_inv = 1.f / p.det;
                 conA = p.c * det_inv; conB = -p.b * det_inv; conC = p.a * det_inv;
@@ -457,12 +422,11 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
     float sc_in[3] = {0.f, 0.f, 0.f};       // (loaded in part 1: no global load waits behind the staging barriers)
     Proj p;
     p.tx = p.ty = p.tz = 0.f;
-    // Round 5 (late): EVERY load of a visible Gaussian whose address depends on its index alone is issued here, back to back, before any of them is
-    // used -- its parameters, its accumulated gradient row, its colour Jacobian --, then the actor's pose rows (the one dependent address).  Before, the
-    // loads sat in the branches that use them (motion / raw quaternion / scales / gradient row / Jacobian, each kernel-uniform or per-lane): seven
-    // load -> s_waitcnt -> use rounds one behind the other, each a trip to the Infinity Cache or HBM, in a kernel whose compacted blocks keep ~2 waves
-    // busy.  Optional inputs are read through a pointer that is valid either way (the Gaussian's own gradient row stands in for an absent array) and
-    // selected where they are used: a branch around a load would put it back behind a wait.
+    // Round 5 (late): every load of a visible Gaussian is issued back to back before any of them is used, and its world pose formed from the loaded
+    // values: gaussian_pose_body.inc, the text the camera-gradient kernel includes as well.  Before, the loads sat in the branches that use them (motion /
+    // raw quaternion / scales / gradient row / Jacobian, each kernel-uniform or per-lane): seven load -> s_waitcnt -> use rounds one behind the other,
+    // each a trip to the Infinity Cache or HBM, in a kernel whose compacted blocks keep ~2 waves busy.
+    // (the three lines of flags are restated in K1 and in k_camera_backward, camera_grad.hip: as a function they moved this kernel's machine code)
     const bool motion = (a.flags & EMD_FLAG_MOTION) != 0;
     const bool has_ids = motion && a.motion.actor_id != nullptr, has_rot = a.rotations != nullptr;
     const bool has_rdx = motion && a.motion.residual_dx != nullptr, has_rdq = motion && has_rot && a.motion.residual_dq != nullptr;
@@ -470,44 +434,9 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
     float mloc[3] = {0.f, 0.f, 0.f}, op_raw = 0.f;
     float4 q_raw = z4c, rdq = z4c, pr0 = z4c, pr1 = z4c, pr2 = z4c;
     if (in_range) {
-        // (the actor id of every compacted Gaussian: the pose-gradient reduction at the end looks at whole waves)
-        const int aid_raw = *(has_ids ? a.motion.actor_id + i : a.radii + i);
-        a_id = has_ids ? aid_raw : -1;
-        float4* gr = (float4*)(a.grad_rec + (size_t)i * a.bwd_stride);
-        const float* safe = (const float*)gr;                                          // 48 readable, 16-byte aligned bytes
-        const float* mp = a.means3D + 3 * (size_t)i;
-        const float* xp = has_rdx ? a.motion.residual_dx + 3 * (size_t)i : safe;
-        const float* sp = a.cov3D_precomp ? safe : a.scales + 3 * (size_t)i;
-        const float4* jr = a.colors_precomp ? (const float4*)gr : a.g.shjac + (size_t)i * 3;
-        const float m0 = mp[0], m1 = mp[1], m2 = mp[2];
-        const float x0 = xp[0], x1 = xp[1], x2 = xp[2];
-        const float4 qq = *(const float4*)(has_rot ? a.rotations + 4 * (size_t)i : safe);
-        const float4 dqq = *(const float4*)(has_rdq ? a.motion.residual_dq + 4 * (size_t)i : safe);
-        const float opv = a.opacities[i];
-        const float s0 = sp[0], s1 = sp[1], s2 = sp[2];
-        const float4 g0 = gr[0], g1 = gr[1], g2 = gr[2];
-        const float4 j0 = jr[0], j1 = jr[1], j2 = jr[2];
-        if (a_id >= 0) {                              // the one dependent address
-            const float4* Pp = (const float4*)(a.motion.actor_pose + (size_t)a_id * EMD_ACTOR_STRIDE);
-            pr0 = Pp[0]; pr1 = Pp[1]; pr2 = Pp[2];
-        }
-        if (a.flags & EMD_FLAG_BWD_WS_CLEAN) {          // the row is handed back clean: the next backward needs no zero fill
-            gr[0] = z4c; gr[1] = z4c; gr[2] = z4c;
-        }
-        // ---- the Gaussian's world pose (motion_point's arithmetic on the values above)
-        mloc[0] = has_rdx ? m0 + x0 : m0; mloc[1] = has_rdx ? m1 + x1 : m1; mloc[2] = has_rdx ? m2 + x2 : m2;
-        q_raw = qq; rdq = dqq; op_raw = opv;
-        if (motion) motion_apply(mloc, a_id, has_rot, q_raw, has_rdq, rdq, true, op_raw, pr0, pr1, pr2, raw, m, q, &op);
-        else {
-            op = raw ? sigmoidf_(op_raw) : op_raw;
-            m[0] = m0; m[1] = m1; m[2] = m2;
-            if (has_rot) { q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w; }
-        }
-        if (raw && a_id < 0 && has_rot) {   // static point: q is the raw quaternion (no-motion path) or already unit (motion path)
-            const float qr[4] = {qq.x, qq.y, qq.z, qq.w};
-            q_norm = fmaxf(quat_norm(qr), 1e-12f);
-            q[0] = qr[0] / q_norm; q[1] = qr[1] / q_norm; q[2] = qr[2] / q_norm; q[3] = qr[3] / q_norm;
-        }
+        // (a_id of every compacted Gaussian: the pose-gradient reduction at the end looks at whole waves)
+        constexpr bool consume_row = true;              // the opacity too, and the row is handed back clean
+#include "gaussian_pose_body.inc"
         if (!a.cov3D_precomp) { sc_in[0] = s0; sc_in[1] = s1; sc_in[2] = s2; }
         gm2[0] = g0.x; gm2[1] = g0.y;
         if (a.flags & EMD_FLAG_ABSGRAD) { gabs[0] = g2.z; gabs[1] = g2.w; }
@@ -515,28 +444,15 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
         dop = g0.w;
         gA = g1.x; gB = g1.y; gC = g1.z;
         gcol[0] = g1.w; gcol[1] = g2.x; gcol[2] = g2.y;
-        p.tx = ((V[0] * m[0] + V[4] * m[1]) + V[8] * m[2]) + V[12];
-        p.ty = ((V[1] * m[0] + V[5] * m[1]) + V[9] * m[2]) + V[13];
-        p.tz = ((V[2] * m[0] + V[6] * m[1]) + V[10] * m[2]) + V[14];
+        view_transform(V, m, p.tx, p.ty, p.tz);
         // (e) colour
         if (!a.colors_precomp) {
-            float d0[3] = {m[0] - S.campos[0], m[1] - S.campos[1], m[2] - S.campos[2]};
-            float n = sqrtf((d0[0] * d0[0] + d0[1] * d0[1]) + d0[2] * d0[2]);
-            float d[3] = {d0[0] / n, d0[1] / n, d0[2] / n};
-            // d L / d dir = J^T gc with the 3x3 Jacobian K1 stored: no second pass over the 192 B of coefficients
-            const uint32_t bits = __float_as_uint(j0.w);        // (the clamp bits K1 left in the row's spare word)
-            float gc[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) gc[ch] = ((bits >> ch) & 1u) ? 0.f : gcol[ch];
+#include "sh_dir_grad_body.inc"
             sh_gc[0] = gc[0]; sh_gc[1] = gc[1]; sh_gc[2] = gc[2];
             const int deg = S.sh_degree;
             const int K = (deg + 1) * (deg + 1);
             float bs[16];
             sh_basis(deg, d, bs);
-            float gd[3];
-            gd[0] = (j0.x * gc[0] + j1.x * gc[1]) + j2.x * gc[2];
-            gd[1] = (j0.y * gc[0] + j1.y * gc[1]) + j2.y * gc[2];
-            gd[2] = (j0.z * gc[0] + j1.z * gc[1]) + j2.z * gc[2];
             if (a.dL_dshs) {
                 if (sh_staged) {          // the factors of this Gaussian's row; multiplied out at staging time
 #pragma unroll
@@ -550,7 +466,6 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
                     }
                 }
             }
-            float dot = (d[0] * gd[0] + d[1] * gd[1]) + d[2] * gd[2];
 #pragma unroll
             for (int k = 0; k < 3; k++) dm[k] += (gd[k] - d[k] * dot) / n;
         }
@@ -608,14 +523,8 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
             if (raw) { sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]); }
             cov3d_from_sr(sc, S.scale_modifier, q, c3);
         }
-        project_cov2d(S, m, c3, fx, fy, p);
-        float da = 0.f, db = 0.f, dc = 0.f;
-        if (p.det != 0.f) {
-            float i2 = 1.f / (p.det * p.det);
-            da = (-p.c * p.c * gA + p.b * p.c * gB - p.b * p.b * gC) * i2;
-            db = (2.f * p.b * p.c * gA - (p.a * p.c + p.b * p.b) * gB + 2.f * p.a * p.b * gC) * i2;
-            dc = (-p.b * p.b * gA + p.a * p.b * gB - p.a * p.a * gC) * i2;
-        }
+        project_cov2d(S, c3, fx, fy, p);
+#include "conic_bwd_body.inc"
         const float* M0 = p.M0; const float* M1 = p.M1;
         dc6[0] = da * M0[0] * M0[0] + db * M0[0] * M1[0] + dc * M1[0] * M1[0];
         dc6[3] = da * M0[1] * M0[1] + db * M0[1] * M1[1] + dc * M1[1] * M1[1];
@@ -623,29 +532,15 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
         dc6[1] = 2.f * da * M0[0] * M0[1] + db * (M0[0] * M1[1] + M0[1] * M1[0]) + 2.f * dc * M1[0] * M1[1];
         dc6[2] = 2.f * da * M0[0] * M0[2] + db * (M0[0] * M1[2] + M0[2] * M1[0]) + 2.f * dc * M1[0] * M1[2];
         dc6[4] = 2.f * da * M0[1] * M0[2] + db * (M0[1] * M1[2] + M0[2] * M1[1]) + 2.f * dc * M1[1] * M1[2];
-        float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
+#include "cov2d_bwd_body.inc"
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float dM0 = 2.f * da * p.T0[k] + db * p.T1[k];
-            float dM1 = 2.f * dc * p.T1[k] + db * p.T0[k];
-            dJ00 += dM0 * V[4 * k + 0]; dJ02 += dM0 * V[4 * k + 2];
-            dJ11 += dM1 * V[4 * k + 1]; dJ12 += dM1 * V[4 * k + 2];
-        }
-        float tz2 = 1.f / (p.tz * p.tz), tz3 = tz2 / p.tz;
-        float dtx = p.clx ? 0.f : -fx * tz2 * dJ02;
-        float dty = p.cly ? 0.f : -fy * tz2 * dJ12;
-        float dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + 2.f * fx * p.cx * tz3 * dJ02 + 2.f * fy * p.cy * tz3 * dJ12;
-        dtz += g_depth;  // (d)
-#pragma unroll
-        for (int k = 0; k < 3; k++) dm[k] += V[4 * k + 0] * dtx + V[4 * k + 1] * dty + V[4 * k + 2] * dtz;
+        for (int k = 0; k < 3; k++) dm[k] += V[4 * k + 0] * dt[0] + V[4 * k + 1] * dt[1] + V[4 * k + 2] * dt[2];
         // (c) pixel mean -> clip -> world
         float gxn = 0.5f * (float)W * gm2[0], gyn = 0.5f * (float)H * gm2[1];
         gm2[0] = gxn; gm2[1] = gyn;
         gabs[0] *= 0.5f * (float)W; gabs[1] *= 0.5f * (float)H;
-        float hx = ((P[0] * m[0] + P[4] * m[1]) + P[8] * m[2]) + P[12];
-        float hy = ((P[1] * m[0] + P[5] * m[1]) + P[9] * m[2]) + P[13];
-        float hw = ((P[3] * m[0] + P[7] * m[1]) + P[11] * m[2]) + P[15];
-        float pw = 1.f / (hw + 0.0000001f);
+        const Clip h = clip_transform(P, m);
+        const float hx = h.hx, hy = h.hy, pw = h.pw;
         float mul1 = hx * pw * pw, mul2 = hy * pw * pw;
 #pragma unroll
         for (int k = 0; k < 3; k++)
