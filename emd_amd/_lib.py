@@ -277,6 +277,26 @@ class EmdMlpDetJob(C.Structure):
                 ("ld", C.c_int32), ("col0", C.c_int32), ("scale", C.c_double)]
 
 
+DEFORM_MLP_MAX_LAYERS, DEFORM_MLP_MIN_GROUP_ROWS = 16, 256
+
+
+class EmdDeformMlpArgs(C.Structure):
+    _fields_ = [("num_points", C.c_int32), ("depth", C.c_int32), ("width", C.c_int32), ("in_dim", C.c_int32), ("embed_dim", C.c_int32),
+                ("skip", C.c_int32), ("ld_x", C.c_int32), ("num_cus", C.c_int32), ("x", _f), ("w", _f * DEFORM_MLP_MAX_LAYERS),
+                ("b", _f * DEFORM_MLP_MAX_LAYERS), ("h", _f * DEFORM_MLP_MAX_LAYERS), ("w_head", _f * 3), ("b_head", _f * 3), ("out", _f * 3)]
+
+
+class EmdDeformMlpGrads(C.Structure):
+    _fields_ = [("g_out", _f * 3), ("d_w", _f * DEFORM_MLP_MAX_LAYERS), ("d_b", _f * DEFORM_MLP_MAX_LAYERS), ("d_w_head", _f * 3),
+                ("d_b_head", _f * 3), ("d_x", _f), ("ld_dx", C.c_int32), ("reserved", C.c_int32), ("g_h", _f * 2), ("slab", _f),
+                ("slab_bytes", C.c_size_t)]
+
+
+class EmdDeformMlpLayout(C.Structure):
+    _fields_ = [("groups", C.c_int32), ("group_rows", C.c_int32), ("pitch_w", C.c_int32), ("pitch_b", C.c_int32), ("offset_w", C.c_size_t),
+                ("offset_b", C.c_size_t), ("bytes", C.c_size_t)]
+
+
 ADAM_MAX_TENSORS = 32
 
 
@@ -352,6 +372,7 @@ EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_s
                     "emd_plane_reg_workspace_size", "emd_plane_reg_forward", "emd_plane_reg_backward",
                     "emd_affine_workspace_size", "emd_affine_forward", "emd_affine_backward", "emd_trainer_loss_workspace_size", "emd_trainer_loss",
                     "emd_mlp_det_slab_bytes", "emd_mlp_branch_forward_det", "emd_mlp_branch_backward_det", "emd_mlp_trunk_backward_det", "emd_mlp_det_reduce",
+                    "emd_deform_mlp_workspace", "emd_deform_mlp_forward", "emd_deform_mlp_backward",
                     "emd_temporal_embed_backward_det",
                     "emd_track_det_workspace_size", "emd_track_det_workspace_offsets", "emd_actor_row_sum_det", "emd_track_heads_forward_det",
                     "emd_track_heads_backward_det", "emd_tracked_pose_backward_det",
@@ -457,6 +478,9 @@ def load():
     lib.emd_mlp_branch_backward_det.argtypes = [C.POINTER(EmdMlpBranch), C.POINTER(EmdMlpBranchGrads), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_mlp_trunk_backward_det.argtypes = [C.POINTER(EmdMlpTrunk), C.POINTER(EmdMlpTrunkGrads), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.emd_mlp_det_reduce.argtypes = [C.POINTER(EmdMlpDetJob), C.c_int, C.c_void_p]
+    lib.emd_deform_mlp_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EmdDeformMlpLayout)]
+    lib.emd_deform_mlp_forward.argtypes = [C.POINTER(EmdDeformMlpArgs), C.c_void_p]
+    lib.emd_deform_mlp_backward.argtypes = [C.POINTER(EmdDeformMlpArgs), C.POINTER(EmdDeformMlpGrads), C.c_void_p]
     lib.emd_temporal_embed_backward_det.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     lib.emd_track_heads_forward.argtypes = [C.POINTER(EmdTrackArgs), C.c_void_p]
     lib.emd_track_det_workspace_size.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
@@ -688,3 +712,10 @@ def mlp_det_layout(kind, args, grads=None):
     n = int(load().emd_mlp_det_slab_bytes(int(kind), C.byref(args), None if grads is None else C.byref(grads), C.byref(out)))
     k = out.num_tensors
     return dict(groups=int(out.groups), pitch=[int(x) for x in out.pitch[:k]], offset=[int(x) for x in out.offset[:k]], bytes=n)
+
+
+def deform_mlp_layout(num_points, width, in_dim, num_cus):
+    """The slab of emd_deform_mlp_backward (emd_deform_mlp_workspace, host only): dict(groups, group_rows, pitch_w, pitch_b, offset_w, offset_b, bytes)."""
+    out = EmdDeformMlpLayout()
+    check(load().emd_deform_mlp_workspace(int(num_points), int(width), int(in_dim), int(num_cus), C.byref(out)), "emd_deform_mlp_workspace")
+    return {f: int(getattr(out, f)) for f, _ in EmdDeformMlpLayout._fields_}

@@ -550,13 +550,85 @@ class _DeformInput(torch.autograd.Function):
         return None, None, None, g_embed, None, None, None, None    # positions and time are detached in the reference
 
 
+class _DeformTrunk(torch.autograd.Function):
+    """The D layers and the heads of ConditionalDeformNetwork on csrc/deform_mlp.hip (emd_deform_mlp_forward / _backward): one node of the graph.
+    Saved: the encoded input and the post-ReLU activations, the tensors the unfused path keeps.  No host synchronisation; capturable."""
+
+    @staticmethod
+    def _args(cfg, x, params, hs, outs):
+        D, W, Cin, E, skip, quat, scale = cfg
+        a = L.EmdDeformMlpArgs()
+        a.num_points, a.depth, a.width, a.in_dim, a.embed_dim, a.skip, a.ld_x = x.shape[0], D, W, Cin, E, (skip if skip < D else -1), x.stride(0)
+        a.num_cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+        a.x = x.data_ptr()
+        for i in range(D):
+            a.w[i], a.b[i], a.h[i] = params[2 * i].data_ptr(), params[2 * i + 1].data_ptr(), hs[i].data_ptr()
+        present, k = [True, quat, scale], 0
+        for j in range(3):
+            if present[j]:
+                a.w_head[j], a.b_head[j] = params[2 * (D + k)].data_ptr(), params[2 * (D + k) + 1].data_ptr()
+                a.out[j] = None if outs is None else outs[k].data_ptr()
+                k += 1
+        return a
+
+    @staticmethod
+    def forward(ctx, h0, cfg, *params):
+        L.need_device("ConditionalDeformNetwork(fused=True)", h0, *params)
+        D, W, Cin, E, skip, quat, scale = cfg
+        x = h0.detach().contiguous().float()
+        params = [p.detach().contiguous().float() for p in params]
+        N = x.shape[0]
+        new = lambda *s: torch.empty(*s, device=x.device, dtype=torch.float32)
+        hs = [new(N, W) for _ in range(D)]
+        outs = [new(N, w) for w, on in ((3, True), (4, quat), (3, scale)) if on]
+        with torch.cuda.device(x.device):
+            L.launch("emd_deform_mlp_forward", C.byref(_DeformTrunk._args(cfg, x, params, hs, outs)))
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, *params, *hs)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *g_outs):
+        cfg = ctx.cfg
+        D, W, Cin, E = cfg[:4]
+        saved = ctx.saved_tensors
+        x, params, hs = saved[0], list(saved[1:len(saved) - D]), list(saved[len(saved) - D:])
+        N = x.shape[0]
+        d_params = [torch.empty_like(p) for p in params]
+        d_x = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
+        if N == 0:
+            return (d_x, None, *[d.zero_() for d in d_params])
+        g_outs = [g.contiguous().float() for g in g_outs]
+        a = _DeformTrunk._args(cfg, x, params, hs, None)
+        lay = L.deform_mlp_layout(N, W, Cin, a.num_cus)
+        g = L.EmdDeformMlpGrads()
+        for i in range(D):
+            g.d_w[i], g.d_b[i] = d_params[2 * i].data_ptr(), d_params[2 * i + 1].data_ptr()
+        k = 0
+        for j in range(3):
+            if a.w_head[j]:
+                g.g_out[j], g.d_w_head[j], g.d_b_head[j] = g_outs[k].data_ptr(), d_params[2 * (D + k)].data_ptr(), d_params[2 * (D + k) + 1].data_ptr()
+                k += 1
+        scratch = torch.empty(2, N, W, device=x.device, dtype=torch.float32)
+        slab = torch.empty(lay["bytes"], device=x.device, dtype=torch.uint8)
+        g.d_x, g.ld_dx = L.ptr(d_x), x.stride(0)
+        g.g_h[0], g.g_h[1] = scratch[0].data_ptr(), scratch[1].data_ptr()
+        g.slab, g.slab_bytes = slab.data_ptr(), slab.numel()
+        with torch.cuda.device(x.device):
+            L.launch("emd_deform_mlp_backward", C.byref(a), C.byref(g))
+        return (d_x, None, *d_params)
+
+
 class ConditionalDeformNetwork(nn.Module):
     """OmniRe/models/modules.py:411-457 (same parameters: `linear`, `gaussian_warp`, `gaussian_rotation`, `gaussian_scaling`).
-    The layers run on `tall_linear` (rocBLAS), which has no fixed-order form: `nonrigid_deformation(..., deterministic=True)` covers the gradient of
-    the actor embeddings behind the encoder input, not the gradients of these layers."""
+    By default the layers run on `tall_linear` (rocBLAS), which has no fixed-order form: `nonrigid_deformation(..., deterministic=True)` then covers the
+    gradient of the actor embeddings behind the encoder input, not the gradients of these layers.
+    `fused=True` (also the attribute `network.fused`): the whole network, forward and backward, runs on the fp32-MFMA kernels of csrc/deform_mlp.hip
+    instead -- no BLAS, no float atomics, every output and gradient bit-identical from run to run."""
 
-    def __init__(self, D=8, W=256, input_ch=3, embed_dim=10, x_multires=10, t_multires=10, deform_quat=True, deform_scale=True):
+    def __init__(self, D=8, W=256, input_ch=3, embed_dim=10, x_multires=10, t_multires=10, deform_quat=True, deform_scale=True, fused=False):
         super().__init__()
+        self.fused = bool(fused)
         self.D, self.W, self.embed_dim, self.deform_quat, self.deform_scale = D, W, embed_dim, deform_quat, deform_scale
         self.x_multires, self.t_multires = x_multires, t_multires
         self.skips = [D // 2]
@@ -571,6 +643,8 @@ class ConditionalDeformNetwork(nn.Module):
 
     def trunk(self, h0):
         """The D layers on an encoded input [N, input_ch]; the skip concat of modules.py:446-447 becomes a second addmm."""
+        if self.fused:
+            return self._trunk_fused(h0)
         h, skipped = h0, False
         for i, lin in enumerate(self.linear):
             if skipped:
@@ -585,6 +659,27 @@ class ConditionalDeformNetwork(nn.Module):
         return (out(self.gaussian_warp), out(self.gaussian_rotation) if self.deform_quat else None,
                 out(self.gaussian_scaling) if self.deform_scale else None)
 
+    def fused_refusal(self):
+        """Why the fused kernels do not serve this configuration (emd_deform_mlp_forward would refuse it), or None."""
+        if self.W % 32 or not 32 <= self.W <= 256:
+            return f"W = {self.W} is not a multiple of 32 up to 256"
+        if not 2 <= self.D <= L.DEFORM_MLP_MAX_LAYERS:
+            return f"D = {self.D} is outside 2..{L.DEFORM_MLP_MAX_LAYERS}"
+        if self.skips[0] == self.D - 1:
+            return f"the skip after layer {self.skips[0]} of {self.D} would put the concat in front of the heads"
+        if self.input_ch > 256 or self.embed_dim > 32:
+            return f"input width {self.input_ch} > 256 or embed_dim {self.embed_dim} > 32"
+        return None
+
+    def _trunk_fused(self, h0):
+        why = self.fused_refusal()
+        if why:
+            raise NotImplementedError(f"ConditionalDeformNetwork(fused=True): {why}")
+        heads = [self.gaussian_warp, self.gaussian_rotation if self.deform_quat else None, self.gaussian_scaling if self.deform_scale else None]
+        params = [p for lin in list(self.linear) + [h for h in heads if h is not None] for p in (lin.weight, lin.bias)]
+        outs = iter(_DeformTrunk.apply(h0, (self.D, self.W, self.input_ch, self.embed_dim, self.skips[0], self.deform_quat, self.deform_scale), *params))
+        return tuple(next(outs) if h is not None else None for h in heads)
+
     def forward(self, x, t, condition):
         """Reference signature: x [N,3] normalised positions, t [N,1] (one frame: every row equal), condition [N, embed_dim]."""
         return self.trunk(_DeformInput.apply(x, None, None, condition, t, self.x_multires, self.t_multires))
@@ -595,7 +690,8 @@ def nonrigid_deformation(network, local_means, point_ids, instances_size, instan
     x = mean.data / height * 2, both frequency encodings and the concat in one launch, then the network's layers.
     t: 1-element device tensor (normalized_timestamps[cur_frame]).
     deterministic: dL/d instances_embedding is summed per actor in ascending point index with a pinned association instead of float atomics (DESIGN.md
-    section 8.15); the network's own layers (rocBLAS) are not covered."""
+    section 8.15).  The network's own layers are rocBLAS calls by default and not covered; with `network.fused` they run on the fixed-order kernels of
+    csrc/deform_mlp.hip whatever this flag says, and the two together make the whole call bit-reproducible (section 8.20)."""
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
     return network.trunk(_DeformInput.apply(local_means, ids, instances_size, instances_embedding, t, network.x_multires, network.t_multires,
                                             bool(deterministic)))

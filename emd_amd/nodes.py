@@ -88,7 +88,8 @@ def deformable_gaussians(network, means, quats, opacity_logits, log_scales, feat
     """DeformableNodes.get_gaussians: delta_xyz on the canonical means (detached when `stop_optimizing_canonical_xyz`), delta_quat on
     the normalised quaternions, delta_scale (when the network has that head) on the activated scales; then as rigid_gaussians
     (`deterministic` included: it covers the motion transform and, through `nonrigid_deformation(..., deterministic=True)`, the gradient of
-    `instances_embedding` behind the encoder input; the layers of ConditionalDeformNetwork run on rocBLAS and are not covered)."""
+    `instances_embedding` behind the encoder input; the layers of ConditionalDeformNetwork are covered when `network.fused` is set: they then run on
+    the fixed-order kernels of csrc/deform_mlp.hip instead of rocBLAS)."""
     from .deformation import nonrigid_deformation
     ids = point_ids[..., 0] if point_ids.dim() == 2 else point_ids
     dx = dq = ds = None

@@ -997,6 +997,69 @@ int emd_mlp_trunk_backward_det(const EmdMlpTrunk* args, const EmdMlpTrunkGrads* 
  * groups >= 1, pitch >= rows cols, rows, cols >= 1, ld >= col0 + cols, non-NULL pointers; EMD_ERR_INVALID otherwise. */
 int emd_mlp_det_reduce(const EmdMlpDetJob* jobs, int num_jobs, void* hip_stream);
 
+/* ---- emd_deform_mlp_*: OmniRe's ConditionalDeformNetwork (models/modules.py:411-457) from its encoded input, on fp32 MFMA (csrc/deform_mlp.hip) ----
+ * A compatible extension (no struct changed, EMD_ABI_VERSION kept).  No BLAS, no float atomics, no second mode: every output and every gradient is a
+ * fixed function of the call's inputs (bit-identical from run to run, on any stream, under graph replay).  All products are exact fp32 MFMA fmaf chains.
+ * Network (N rows, D = depth layers of width W, C = in_dim = the row width of emd_deform_input_forward, E = embed_dim = its last columns):
+ *   h_0 = relu(b_0 + x W_0^T)                                        W_0 [W][C]
+ *   h_i = relu(b_i + h_{i-1} W_i^T)                                  W_i [W][W]
+ *   h_i = relu(b_i + x W_i[:, :C]^T + h_{i-1} W_i[:, C:]^T)          i = skip + 1, W_i [W][C + W]: read in place, no concat (skip = -1: no such layer)
+ *   out[k] = b_head[k] + h_{D-1} w_head[k]^T                         k = 0 warp [N][3], 1 rotation [N][4], 2 scaling [N][3]; w_head[k] NULL: head absent
+ * Summation order: an accumulator starts at the bias, takes the x block before the h block, and inside a block the input columns in ascending blocks of
+ * 32; inside a block of 32 the MFMA pairs columns (8 a + j, 8 a + 4 + j), a = 0..3, j = 0..3, in that order.  It does not depend on N or on the grid.
+ * Backward (G_i = dL/dh_i where h_i > 0, else 0):
+ *   dL/dh_{D-1}[n][c] = fmaf chain from 0 over g_out[0][n][0..2], g_out[1][n][0..3], g_out[2][n][0..2] (absent heads skipped) times w_head[.][c]
+ *   dL/dh_{i-1} = G_i W_i (the h block of the skip layer), dL/dx[:, C-E : C] = G_i W_i[:, C-E : C] for i = skip + 1 and i = 0: the accumulator starts at
+ *   0 and sums over the W output features in the order above.  Positions and time are detached in the reference, so only these E columns of d_x are
+ *   written (element (n, j) at d_x[n ld_dx + C - E + j]); with a skip layer the skip layer's launch stores its sum s and layer 0's launch, which runs
+ *   later, stores s + (its own sum), in that order.
+ *   d_w_i = G_i^T [input], d_b_i = sum_n G_i; d_w_head / d_b_head the same from g_out: the rows are cut into `groups` static groups of `group_rows`
+ *   (EmdDeformMlpLayout: a function of N and num_cus alone), a workgroup sums its group's rows in ascending steps of 32 (inside a step the MFMA pairs row s
+ *   with row 16 + s, s = 0..15; a bias partial is rows 0..15 + rows 16..31 per step) and stores the total to slot `group` of the slab; the slots are then
+ *   added in ascending order in double precision from 0.0 and rounded once.  Every slot element is written: the slab is never cleared, and its one region
+ *   serves layer after layer (the launches are stream-ordered).
+ * Slab: groups = ceil(N / group_rows), group_rows = max(EMD_DEFORM_MLP_MIN_GROUP_ROWS, ceil(N / max(1, num_cus / 2))) rounded up to 32;
+ *   [groups][pitch_w = W max(W, C)] floats at offset_w = 0, [groups][pitch_b = W] floats at offset_b, each rounded up to 256 bytes.
+ * emd_deform_mlp_workspace is host-only.  Every buffer is caller-owned; the library allocates nothing.  Refused before anything is launched:
+ *   EMD_ERR_INVALID  width not a multiple of 32 or > 256; depth < 2 or > EMD_DEFORM_MLP_MAX_LAYERS; skip == depth - 1 (the heads would see the concat)
+ *                    or outside -1 .. depth - 2; in_dim > 256; embed_dim > min(32, in_dim); ld_x < in_dim; num_cus < 1; a NULL required pointer;
+ *                    h[i] / g_h[k] not 16-byte aligned;
+ *   EMD_ERR_WORKSPACE  a missing slab, one not 256-byte aligned or shorter than the layout's `bytes`.
+ * num_points == 0 launches nothing.  The forward writes h[0 .. D-1] (the saved post-ReLU activations the backward reads) and out[k]; the backward
+ * does not read out[k] (it may be NULL there). */
+#define EMD_DEFORM_MLP_MAX_LAYERS 16
+#define EMD_DEFORM_MLP_MIN_GROUP_ROWS 256
+typedef struct EmdDeformMlpArgs {
+    int32_t num_points, depth, width, in_dim, embed_dim, skip;
+    int32_t ld_x, num_cus;                       /* row stride of x in floats; compute units of the device (the row groups of the backward) */
+    const float* x;                              /* [N][ld_x] encoded input */
+    const float* w[EMD_DEFORM_MLP_MAX_LAYERS];
+    const float* b[EMD_DEFORM_MLP_MAX_LAYERS];
+    float* h[EMD_DEFORM_MLP_MAX_LAYERS];         /* [N][W] each, 16-byte aligned */
+    const float* w_head[3];
+    const float* b_head[3];
+    float* out[3];
+} EmdDeformMlpArgs;
+typedef struct EmdDeformMlpGrads {
+    const float* g_out[3];                       /* dL/dout[k] of every present head */
+    float* d_w[EMD_DEFORM_MLP_MAX_LAYERS];
+    float* d_b[EMD_DEFORM_MLP_MAX_LAYERS];
+    float* d_w_head[3];
+    float* d_b_head[3];
+    float* d_x;                                  /* [N][ld_dx] or NULL; columns C-E .. C-1 are written */
+    int32_t ld_dx, reserved;
+    float* g_h[2];                               /* scratch: two distinct [N][W] buffers, 16-byte aligned */
+    void* slab;
+    size_t slab_bytes;
+} EmdDeformMlpGrads;
+typedef struct EmdDeformMlpLayout {
+    int32_t groups, group_rows, pitch_w, pitch_b;
+    size_t offset_w, offset_b, bytes;
+} EmdDeformMlpLayout;
+int emd_deform_mlp_workspace(int num_points, int width, int in_dim, int num_cus, EmdDeformMlpLayout* layout);
+int emd_deform_mlp_forward(const EmdDeformMlpArgs* args, void* hip_stream);
+int emd_deform_mlp_backward(const EmdDeformMlpArgs* args, const EmdDeformMlpGrads* grads, void* hip_stream);
+
 /* ---- Adaptive density control on the device ----------------------------------------------------
  * densify = densify_and_clone + densify_and_split, prune = prune / prune_points of S3Gaussian/scene/gaussian_model.py:441-603,
  * 683-701 (OmniRe: models/gaussians/vanilla.py:206-376), rewriting the SoA parameters, both Adam moments and the statistics in
