@@ -350,7 +350,7 @@ class EmdSkinGrads(C.Structure):
 
 # every symbol include/emd_raster.h declares
 EXPORTED_SYMBOLS = ("emd_abi_version", "emd_last_error", "emd_raster_workspace_size", "emd_raster_forward",
-                    "emd_raster_backward", "emd_raster_export_binning", "emd_raster_export_geometry", "emd_raster_export_contributed",
+                    "emd_raster_backward", "emd_backward_fill_slice", "emd_raster_export_binning", "emd_raster_export_geometry", "emd_raster_export_contributed",
                     "emd_motion_forward", "emd_motion_backward", "emd_sh_forward", "emd_sh_backward",
                     "emd_profile_enable", "emd_profile_read", "emd_profile_stage_name", "emd_activations_forward", "emd_actor_pose_forward", "emd_actor_pose_backward", "emd_l1_loss",
                     "emd_sky_forward", "emd_sky_backward", "emd_image_loss_workspace", "emd_image_loss", "emd_hexplane_forward", "emd_hexplane_backward", "emd_hexplane_order_keys", "emd_sh_grad_from_factors", "emd_densification_stats",
@@ -413,6 +413,7 @@ def load():
     lib.emd_raster_workspace_size.argtypes = [C.POINTER(EmdDims), C.POINTER(C.c_size_t)]
     lib.emd_raster_forward.argtypes = [C.POINTER(EmdFwdArgs), C.c_void_p]
     lib.emd_raster_backward.argtypes = [C.POINTER(EmdBwdArgs), C.c_void_p]
+    lib.emd_backward_fill_slice.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     lib.emd_raster_export_binning.argtypes = [C.POINTER(EmdDims), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emd_raster_export_geometry.argtypes = [C.POINTER(EmdDims), C.c_void_p, C.c_size_t] + [C.c_void_p] * 7

@@ -144,6 +144,7 @@ template <class P, class A> static void fill_inputs(P& p, const A& a, const Geom
 static void fill_bwd_inputs(PreBwdArgs& p, const EmdBwdArgs& a, const GeomWs& g) {
     fill_inputs(p, a, g);
     p.grad_rec = (float*)a.bwd_ws; p.bwd_stride = emd_bwd_stride(a.num_extra); p.num_extra = a.num_extra;
+    p.shs_prezeroed = 0;
 }
 
 // What both backward entries need of the forward's state, behind check_common: the pointers, num_extra, the device settings, the sizes of geom_ws and bwd_ws
@@ -361,6 +362,12 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     // the two halves of the pass may arrive as two calls (EMD_FLAG_BWD_RENDER_ONLY, then EMD_FLAG_BWD_PROJECT_ONLY on the same workspaces)
     const bool do_render = !(a->flags & EMD_FLAG_BWD_PROJECT_ONLY), do_project = !(a->flags & EMD_FLAG_BWD_RENDER_ONLY);
     if (!do_render && !do_project) { emd_set_error("backward: EMD_FLAG_BWD_RENDER_ONLY and EMD_FLAG_BWD_PROJECT_ONLY exclude each other"); return EMD_ERR_INVALID; }
+    // The dense dL/dshs ([N,16,3]: 192 B per Gaussian, three quarters of them zero rows) is zeroed by K7's own workgroups, a slice each, under its pixel
+    // loops (which leave nine tenths of the HBM bandwidth idle), and K8, behind it on the stream, stores the rows of the contributing Gaussians only.  Only
+    // when this very call runs both kernels, K7 is launched at all (a tile grid exists), its default instantiation runs (the deterministic one does not fill) and
+    // K8 takes its staged path (shs given, 16 coefficients); every other call keeps the dense K8: the two-call form, EMD_FLAG_DETERMINISTIC, the factored SH
+    // gradient (no dL_dshs), M != 16.
+    const bool shs_prefill = do_render && do_project && !det && a->dL_dshs && a->shs && a->sh_coeffs == 16 && N > 0 && gx * gy > 0;
     if (do_render) {
         emd_prof_begin(PROF_OTHER, st);
         if (!(a->flags & EMD_FLAG_BWD_WS_CLEAN)) { int zrc = emd_zero_async(a->bwd_ws, emd_bwd_bytes(N, a->num_extra), st); if (zrc) return zrc; }
@@ -384,6 +391,7 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
         }
         rc = emd_launch_render_backward(a->s, a->settings_dev, a->flags, g, b, im, a->out_color, a->out_depth, a->out_normal, a->dL_dcolor,
                                         a->dL_ddepth, a->dL_dalpha, a->dL_dnormal, &ex, (float*)a->bwd_ws, pose_grad, pose_grad_n,
+                                        shs_prefill ? (float4*)a->dL_dshs : nullptr, shs_prefill ? (size_t)N * 12 : 0,
                                         (unsigned long long*)a->pair_stats, det ? dw.r.rows : nullptr, st);
         if (rc) return rc;
         if (det) {
@@ -408,6 +416,7 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     pb.dL_dscales = a->dL_dscales; pb.dL_drotations = a->dL_drotations; pb.dL_dcov3D = a->dL_dcov3D;
     pb.dL_dactor_pose = a->dL_dactor_pose; pb.dL_dresidual_dx = a->dL_dresidual_dx; pb.dL_dresidual_dq = a->dL_dresidual_dq;
     pb.dL_dsh_color = a->dL_dsh_color;
+    pb.shs_prezeroed = shs_prefill ? 1 : 0;
     for (int k = 0; k < EMD_MAX_EXTRA; k++) pb.dL_dextra[k] = k < a->num_extra ? a->dL_dcolors_extra[k] : nullptr;
     const bool det_pose = det && (a->flags & EMD_FLAG_MOTION) && a->dL_dactor_pose && a->motion.num_actors > 0;
     pb.pose_rows = det_pose ? dw.p.rows : nullptr;
@@ -423,6 +432,12 @@ int emd_raster_backward(const EmdBwdArgs* a, void* hip_stream) {
     emd_prof_end(PROF_PREPROCESS_BWD, st);
     if (rc) return rc;
     return stage_sync(dbg, st, "preprocess_backward");
+}
+
+int emd_backward_fill_slice(uint64_t count, uint32_t grid, uint32_t block, uint64_t out[2]) {
+    if (!out || grid == 0 || block >= grid) { emd_set_error("backward_fill_slice: bad argument (grid=%u block=%u)", grid, block); return EMD_ERR_INVALID; }
+    emd_fill_slice(count, emd_fill_per(count, grid), block, &out[0], &out[1]);
+    return EMD_OK;
 }
 
 static int check_det_dims(const EmdDims* dims, const char* who) {

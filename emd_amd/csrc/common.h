@@ -213,8 +213,24 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
                                const float* out_color, const float* out_depth, const float* out_normal,
                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
                                const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
+                               float4* fill_base, size_t fill_n,
                                unsigned long long* pair_stats, float* det_part, hipStream_t st);  // render.hip (zero_buf: small table cleared by block 0
-                               // for K8; det_part: null, or the deterministic variant -- every row STORED to its survivor's slot there, grad_rec untouched)
+                               // for K8; fill_base / fill_n: null / 0, or fill_n float4 the kernel's workgroups zero, a slice each (emd_fill_slice) -- the dense
+                               // dL/dshs rows, of which K8 then stores the contributing ones only; ignored by the deterministic variant;
+                               // det_part: null, or the deterministic variant -- every row STORED to its survivor's slot there, grad_rec untouched)
+// The slice [lo, hi) of `count` float4 that workgroup `block` of `grid` zeroes for the kernel behind it: per = ceil(count / grid) elements rounded up
+// to whole 64-lane store instructions (1 KB contiguous each), so the slices are disjoint, ascending and cover [0, count) exactly; the workgroups past
+// the end (count < 64 grid leaves most of them without work) get lo == hi == count.  64-bit: count = 12 N passes 2^32 at N = 358 M.  The launcher forms
+// `per` once (a 64-bit division is a loop of some hundred instructions on the device) and the kernel's workgroups take their slice from it.
+__host__ __device__ inline uint64_t emd_fill_per(uint64_t count, uint32_t grid) {
+    const uint64_t g = grid ? grid : 1u;
+    return ((count + g - 1) / g + 63u) & ~(uint64_t)63u;
+}
+__host__ __device__ inline void emd_fill_slice(uint64_t count, uint64_t per, uint32_t block, uint64_t* lo, uint64_t* hi) {
+    const uint64_t a = (uint64_t)block * per;
+    *lo = a < count ? a : count;
+    *hi = count - *lo < per ? count : *lo + per;
+}
 // EMD_FLAG_DETERMINISTIC: keys_in[slot] = Gaussian id of the survivor that owns contribution slot `slot` (below 4 D; 0xFFFFFFFF for the survivors
 // the render backward does not walk), *count = 4 D                                                                                     // render.hip
 int emd_launch_det_render_keys(int num_tiles, const BinWs& b, const EmdStatus* status, uint32_t* keys_in, uint32_t* count, hipStream_t st);
@@ -233,6 +249,8 @@ struct PreBwdArgs {
     float *dL_dmeans3D, *dL_dmeans2D, *dL_dmeans2D_abs, *dL_dshs, *dL_dcolors, *dL_dopacities, *dL_dscales,
         *dL_drotations, *dL_dcov3D, *dL_dactor_pose, *dL_dresidual_dx, *dL_dresidual_dq, *dL_dsh_color;
     const float* sdev;
+    int shs_prezeroed;      // 1: the render backward of this call zeroed every dL/dshs row (emd_launch_render_backward's fill): the staged path stores the
+                            // 16-byte pieces of the compacted Gaussians' rows only.  0: every row is written here
     float* pose_rows;       // EMD_FLAG_DETERMINISTIC: [N][EMD_ACTOR_STRIDE], the pose gradient of every visible actor-bound point is STORED here instead of
                             // being added to dL_dactor_pose with atomics (api.hip sorts the points by actor and sums the rows: segsum.h); else null
 };

@@ -142,6 +142,17 @@ __device__ __forceinline__ uint32_t readlane_u32(uint32_t v, int lane) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
 }
 
+// 16-byte nontemporal accesses: streams touched once per step that must not push the projected records out of the Infinity Cache (the SH rows K1
+// reads, the dense dL/dshs rows K7 zeroes and K8 stores: the cache-policy notes at the top of preprocess.hip)
+typedef float emd_v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 load_f4_nt(const float4* p) {
+    const emd_v4f v = __builtin_nontemporal_load(reinterpret_cast<const emd_v4f*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store_f4_nt(float4* p, float4 v) {
+    __builtin_nontemporal_store((emd_v4f){v.x, v.y, v.z, v.w}, reinterpret_cast<emd_v4f*>(p));
+}
+
 // Block-wide (256 threads = 4 waves) inclusive scan of one uint32 per thread.
 // `smem` needs 4 uint32.  Returns the inclusive prefix; *total gets the block sum.
 __device__ __forceinline__ uint32_t block_scan_add_u32(uint32_t v, uint32_t* smem, uint32_t* total) {

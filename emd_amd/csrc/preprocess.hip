@@ -32,20 +32,17 @@
 //   * K8 compacts the visible Gaussians of a 256-block onto its first lanes (full waves do the work, the others only write zero rows) and
 //     sends the five small gradients through the idle SH tile as whole 16-byte nontemporal stores: K8 0.201 -> 0.193 ms, 799 -> 806 it/s.
 //   * K1 and K8 issue every index-addressed load of a Gaussian together, before the first use (round 5, late).
+//   * the zero rows of the dense dL/dshs -- three quarters of its 384 MB -- are not K8's any more in the one-call default backward: K7's workgroups
+//     zero ALL rows, a slice each, under their pixel loops (render.hip, emd_fill_slice), and K8 (the PZ instantiation) stores the rows of its
+//     compacted Gaussians over them, walking the compaction list.  The dense instantiation serves every other call unchanged: the two-call form,
+//     EMD_FLAG_DETERMINISTIC, M != 16 (profiles/backward_prefill_ab.txt).
 // Tried and not kept: nontemporal loads of the Jacobian in K8 (+10 us there), nontemporal scalar stores of K8's small gradients (+8 us in
 // K8 for -5 in K1), nontemporal stores of the projected records (K1 0.11 -> 0.19 ms: 48-byte pieces; and the render kernels do not care
 // where the records come from: +2 us), the small-gradient tile without the compaction (-3 us in K1, +4 us in K8).
 // Every one of these was a compile-time switch with its A/B recorded in profiles/r05_cache_policy_variants.txt (narrative:
 // docs/history/DESIGN_rounds_1-5.md, "change (knob in csrc/preprocess.hip)"); the switches were retired once settled, and the A/B builds
 // are reproducible from the last commit that carries them (profiles/README.md).
-typedef float emd_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 load_f4_nt(const float4* p) {
-    const emd_v4f v = __builtin_nontemporal_load(reinterpret_cast<const emd_v4f*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void store_f4_nt(float4* p, float4 v) {
-    __builtin_nontemporal_store((emd_v4f){v.x, v.y, v.z, v.w}, reinterpret_cast<emd_v4f*>(p));
-}
+// (load_f4_nt / store_f4_nt: device_utils.h)
 
 namespace {
 
@@ -361,6 +358,8 @@ __global__ void __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_waves_per_eu(
 #define K8_BLOCK 256          // threads per workgroup of K8 (A/B: 64 = one wave per workgroup, no cross-wave barrier coupling)
 #define K8_HALF (K8_BLOCK / 2)
 #define EMD_K8_WAVES 4        // round 3: with the SH rows stored first the live state across the staging barriers needs 112 VGPRs; at 5 waves it spills
+// PZ (PreBwdArgs.shs_prezeroed): the instantiation behind a render backward that zeroed dL/dshs; the dense one is the kernel as it was
+template <bool PZ>
 __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(EMD_K8_WAVES))) k_preprocess_backward(PreBwdArgs a) {
     EmdSettings S = a.s;
     emd_settings_from_device(S, a.sdev, a.flags);
@@ -474,11 +473,24 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
         float* o = a.dL_dshs + (size_t)inat * a.M * 3;
         for (int k = 0; k < 3 * a.M; k++) o[k] = 0.f;
     }
+    // PZ: K7's workgroups zeroed every row of dL/dshs in front of this kernel (api.hip), so only the compacted Gaussians' rows are staged and only their
+    // 16-byte pieces stored: the copy-out walks the compaction list itself (the same `vis_words[i] > 0` flags, in index order: the first s_cscan[0] +
+    // s_cscan[1] entries are the rows of the first half), twelve consecutive threads per row -- one or two trips for the ~30 rows of a half instead of six
+    // over all 128.  A flagged Gaussian's row is written exactly as in the dense form, +-0 included; nobody writes a zero row into the tile, and a half
+    // (so a workgroup) without a contributor skips its staging and its barriers.
+    static_assert(K8_HALF == 128 && K8_BLOCK == 256, "the waves' counts s_cscan[0..1] / s_cscan[2..3] are the two halves' row counts");
     if (sh_staged && a.dL_dshs) {
         const size_t lim4 = (size_t)a.N * 12;
         float4* out = (float4*)a.dL_dshs;
 #pragma unroll
         for (int h = 0; h < 2; h++) {
+            uint32_t k0 = 0, kn = 0;          // PZ: the half's rows are entries k0 .. k0 + kn - 1 of s_list (uniform over the workgroup)
+            if (PZ) {
+                // (read into scalar registers: the kernel has no vector register to spare across the barriers)
+                const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_cscan[0] + s_cscan[1]));
+                k0 = h ? c0 : 0u; kn = h ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(s_cscan[2] + s_cscan[3])) : c0;
+                if (kn == 0) continue;
+            }
             if (in_range && (int)(lrow / K8_HALF) == h) {
                 float g48[48];
 #pragma unroll
@@ -487,16 +499,24 @@ __global__ void __launch_bounds__(K8_BLOCK) __attribute__((amdgpu_waves_per_eu(E
                 for (int j = 0; j < 12; j++)
                     s_sh[(lrow % K8_HALF) * SH_ROW4 + j] = make_float4(g48[4 * j], g48[4 * j + 1], g48[4 * j + 2], g48[4 * j + 3]);
             }
-            if (!nat_vis && (int)(threadIdx.x / K8_HALF) == h) {          // the zero row of an invisible (or absent) Gaussian
+            if (!PZ && !nat_vis && (int)(threadIdx.x / K8_HALF) == h) {          // the zero row of an invisible (or absent) Gaussian
 #pragma unroll
                 for (int j = 0; j < 12; j++) s_sh[(threadIdx.x % K8_HALF) * SH_ROW4 + j] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             __syncthreads();
-            const size_t base4 = ((size_t)blockIdx.x * K8_BLOCK + K8_HALF * h) * 12;
+            if (PZ) {
+                float4* const blk_out = out + (size_t)blockIdx.x * K8_BLOCK * 12;
+                for (uint32_t p = threadIdx.x; p < 12u * kn; p += K8_BLOCK) {
+                    const uint32_t row = s_list[k0 + p / 12u], piece = p % 12u;          // (a compacted row lies below N)
+                    store_f4_nt(blk_out + row * 12u + piece, s_sh[(row % K8_HALF) * SH_ROW4 + piece]);
+                }
+            } else {
+                const size_t base4 = ((size_t)blockIdx.x * K8_BLOCK + K8_HALF * h) * 12;
 #pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const uint32_t idx = threadIdx.x + K8_BLOCK * j;
-                if (base4 + idx < lim4) store_f4_nt(out + base4 + idx, s_sh[(idx / 12) * SH_ROW4 + (idx % 12)]);
+                for (int j = 0; j < 6; j++) {
+                    const uint32_t idx = threadIdx.x + K8_BLOCK * j;
+                    if (base4 + idx < lim4) store_f4_nt(out + base4 + idx, s_sh[(idx / 12) * SH_ROW4 + (idx % 12)]);
+                }
             }
             __syncthreads();
         }
@@ -722,7 +742,8 @@ int emd_launch_preprocess(const PreArgs& a, int part, hipStream_t st) {
 int emd_launch_preprocess_backward(const PreBwdArgs& a, hipStream_t st) {
     if (a.N <= 0) return EMD_OK;
     const int nb = (a.N + K8_BLOCK - 1) / K8_BLOCK;
-    hipLaunchKernelGGL(k_preprocess_backward, dim3(nb), dim3(K8_BLOCK), 0, st, a);
+    if (a.shs_prezeroed) hipLaunchKernelGGL(k_preprocess_backward<true>, dim3(nb), dim3(K8_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL(k_preprocess_backward<false>, dim3(nb), dim3(K8_BLOCK), 0, st, a);
     EMD_LAUNCH_CHECK();
     return EMD_OK;
 }

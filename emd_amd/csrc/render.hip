@@ -385,11 +385,23 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
                                                                 const float* __restrict__ dL_dnormal,
                                                                 float* __restrict__ grad_rec,
                                                                 float* __restrict__ zero_buf, int zero_n,
+                                                                float4* __restrict__ fill_base, unsigned long long fill_n, unsigned long long fill_per,
                                                                 unsigned long long* __restrict__ pair_stats,
                                                                 uint32_t* __restrict__ contrib) {
     // the tiny actor-pose gradient table K8 accumulates into is cleared here (K8 starts after this kernel): no memset launch
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < zero_n; i += EMD_WAVE) zero_buf[i] = 0.f;
+    // ... and so is the dense dL/dshs, 192 bytes per Gaussian of which three quarters stay zero: EVERY workgroup of the launch zeroes its slice of the
+    // fill_n float4 (emd_fill_slice: whole 1 KB store instructions, 14 per wave at 2 M Gaussians), the surplus workgroups of the padded grid and the waves
+    // without a survivor included, and K8 stores the contributing rows over it.  A walking wave issues its slice as the LAST thing it does: stores and loads
+    // share vmcnt, so at the top the fill sits in front of the first waits of the walk (measured: K7 422.3 us against 414.7, profiles/backward_prefill_ab.txt).
+    // Nontemporal, as K8 stores these rows: the projected records stay in the Infinity Cache.  The deterministic kernel does not fill (K8 stays dense there).
+    auto fill_slice = [&]() {
+        if (DET || !fill_base) return;
+        uint64_t lo, hi;
+        emd_fill_slice(fill_n, fill_per, blockIdx.x, &lo, &hi);
+        for (uint64_t i = lo + threadIdx.x; i < hi; i += EMD_WAVE) store_f4_nt(fill_base + i, make_float4(0.f, 0.f, 0.f, 0.f));
+    };
     // Round 3: the forward pass leaves, per quadrant, the ids of the entries whose footprint reaches it ("survivors", in list
     // order) and the number of them in front of its deepest contributor.  The backward walks that list back to front, 64 survivors
     // per batch, every lane keeping ITS entry's record in registers: no scan of the tile list, no footprint test, no queue.
@@ -409,7 +421,7 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
     __shared__ uint32_t s_myn[EMD_WAVE];                        // n_contrib of the quadrant's pixels (half-wave batches read it per lane)
     uint32_t quad;
     const uint32_t tile = ordered_quadrant_block(blockIdx.x, (uint32_t)(d.gx * d.gy), tile_order, &quad);
-    if (tile >= (uint32_t)(d.gx * d.gy)) return;
+    if (tile >= (uint32_t)(d.gx * d.gy)) { fill_slice(); return; }
     const uint32_t lane = threadIdx.x;
     const float tile_x0 = (float)((tile % (uint32_t)d.gx) * EMD_TILE_X), tile_y0 = (float)((tile / (uint32_t)d.gx) * EMD_TILE_Y);
     const float qx0 = tile_x0 + (float)((quad & 1) * 8), qy0 = tile_y0 + (float)((quad >> 1) * 8);
@@ -419,7 +431,7 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
     const bool inside = px < d.W && py < d.H;
     const uint32_t start = ranges[2 * tile], n_tile = ranges[2 * tile + 1] - start;
     const uint32_t wave_n = min(quad_need[4 * tile + quad], n_tile);       // survivors in front of this quadrant's deepest contributor
-    if (wave_n == 0) return;
+    if (wave_n == 0) { fill_slice(); return; }            // (an overflowed call's ranges are empty: all of its waves leave here)
     const uint32_t* const sv = surv + 4 * (size_t)start + (size_t)quad * n_tile;
     const size_t HW = (size_t)d.H * d.W, pix = (size_t)py * d.W + px;
     const uint32_t my_n = inside ? n_contrib[pix] : 0u;                    // 1-based number of the last survivor that contributed to this pixel
@@ -696,6 +708,7 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
             process_batch(std::false_type{}, nb, c0r, c1r, c2r, c3r, cxr, (uint32_t)max(idx, 0), cid);
         }
     }
+    fill_slice();
     if (STATS && lane == 0) { atomicAdd(pair_stats, st_eval); atomicAdd(pair_stats + 1, st_hit); atomicAdd(pair_stats + 2, st_rows); atomicAdd(pair_stats + 3, st_atoms); }
 }
 
@@ -704,8 +717,10 @@ __device__ __forceinline__ void render_backward_body(const RenderDims& d, const 
         const uint32_t *__restrict__ quad_need, const float4 *__restrict__ rec, const float *__restrict__ final_T, const uint32_t *__restrict__ n_contrib, \
         const float *__restrict__ out_color, const float *__restrict__ out_depth, const float *__restrict__ out_normal, const float *__restrict__ dL_dcolor, \
         const float *__restrict__ dL_ddepth, const float *__restrict__ dL_dalpha, const float *__restrict__ dL_dnormal, float *__restrict__ grad_rec,  \
-        float *__restrict__ zero_buf, int zero_n, unsigned long long *__restrict__ pair_stats, uint32_t *__restrict__ contrib
-#define K7_ARGS d, tile_order, ranges, surv, quad_need, rec, final_T, n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, grad_rec, zero_buf, zero_n, pair_stats, contrib
+        float *__restrict__ zero_buf, int zero_n, float4 *__restrict__ fill_base, unsigned long long fill_n, unsigned long long fill_per,                        \
+        unsigned long long *__restrict__ pair_stats,                                                                                                  \
+        uint32_t *__restrict__ contrib
+#define K7_ARGS d, tile_order, ranges, surv, quad_need, rec, final_T, n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dL_dnormal, grad_rec, zero_buf, zero_n, fill_base, fill_n, fill_per, pair_stats, contrib
 template <bool NORMAL, bool ABS, int NX, bool STATS = false>
 __global__ void __launch_bounds__(EMD_WAVE) __attribute__((amdgpu_waves_per_eu(NX == 0 ? 4 : NX == 1 ? 3 : 2))) k_render_backward_q(K7_PARAMS) {
     render_backward_body<NORMAL, ABS, NX, STATS, false>(K7_ARGS);
@@ -783,6 +798,7 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
                                const float* out_color, const float* out_depth, const float* out_normal,
                                const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
                                const float* dL_dnormal, const EmdExtra* x, float* grad_rec, float* zero_buf, int zero_n,
+                               float4* fill_base, size_t fill_n,
                                unsigned long long* pair_stats, float* det_part, hipStream_t st) {
     const RenderDims d = make_dims(s, sdev, x);
     const int T = d.gx * d.gy;
@@ -791,7 +807,8 @@ int emd_launch_render_backward(const EmdSettings& s, const float* sdev, int flag
     const int nx = x ? x->num : 0;
     auto launch = [&](auto kernel, const float* dnormal, float* rows, unsigned long long* stats) {
         hipLaunchKernelGGL(kernel, dim3(4 * padded_tile_grid(T)), dim3(EMD_WAVE), 0, st, d, b.tile_order, b.ranges, b.surv, b.quad_need, g.rec, im.final_T,
-                           im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dnormal, rows, zero_buf, zero_n, stats, g.contrib);
+                           im.n_contrib, out_color, out_depth, out_normal, dL_dcolor, dL_ddepth, dL_dalpha, dnormal, rows, zero_buf, zero_n, fill_base,
+                           (unsigned long long)fill_n, (unsigned long long)emd_fill_per(fill_n, 4 * padded_tile_grid(T)), stats, g.contrib);
     };
     if (!det_part && nx == 0 && pair_stats)          // diagnostic: the plain kernel with the pair counters compiled in
         launch(k_render_backward_q<false, false, 0, true>, nullptr, grad_rec, pair_stats);

@@ -277,7 +277,9 @@ typedef struct EmdBwdArgs {
     float* dL_dmeans3D;           /* [N,3] */
     float* dL_dmeans2D;           /* [N,3]  x,y in NDC-scaled pixel units (x 0.5 W, 0.5 H), z = 0 */
     float* dL_dmeans2D_abs;       /* [N,2]  (EMD_FLAG_ABSGRAD) */
-    float* dL_dshs;               /* [N,sh_coeffs,3] */
+    float* dL_dshs;               /* [N,sh_coeffs,3], 16-byte aligned when sh_coeffs == 16.  Every element is written by every call, no zero fill by the
+                                   * caller: by the projection half alone, except in the one-call default backward with shs and 16 coefficients,
+                                   * where the render half zeroes all rows and the projection half stores those of the contributing Gaussians */
     float* dL_dcolors;            /* [N,3] */
     float* dL_dopacities;         /* [N] */
     float* dL_dscales;            /* [N,3] */
@@ -354,6 +356,12 @@ int emd_raster_workspace_size(const EmdDims* dims, size_t out[4]);
 
 int emd_raster_forward(EmdFwdArgs* args, void* hip_stream);
 int emd_raster_backward(const EmdBwdArgs* args, void* hip_stream);
+
+/* ABI 31 extension (a new entry point only, so the number stays).  Host only, for tests: the slice [out[0], out[1]) of `count` 16-byte elements
+ * that workgroup `block` of the `grid` workgroups of the render backward zeroes when that kernel clears dL_dshs for the projection backward
+ * (csrc/common.h, emd_fill_slice -- the function the kernel calls).  Slices are disjoint, ascending and cover [0, count) exactly; every slice
+ * but the last non-empty one is a multiple of 64 elements long.  EMD_ERR_INVALID for grid == 0, block >= grid or a NULL out. */
+int emd_backward_fill_slice(uint64_t count, uint32_t grid, uint32_t block, uint64_t out[2]);
 
 /* ---- ABI 30 extension: the deterministic backward (opt-in, EMD_FLAG_DETERMINISTIC) ------------------------------------------------------------
  * Bytes of EmdBwdArgs.det_ws for dims (num_gaussians N, bin_capacity C, num_extra x).  R = 4 max(C, 1) contribution slots (one per quadrant
